@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- users/sec of GRAM's generative scoring path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): Beauty item Trie
@@ -47,6 +47,7 @@ MFMA_BF16_PEAK_TF = 2500.0  # dense bf16 MFMA peak
 DEFAULT_PRECISION = "f16x3"
 PIECES = {"f16": 1, "f16x3": 2, "bf16": 1, "bf16x3": 2}   # (bf16*: the PIECE=bf16 build of the library, GRAM_LIB=...)
 NPROD = {"f16": 1, "f16x3": 3, "bf16": 1, "bf16x3": 3}
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -86,7 +87,13 @@ def parse():
                     help="--gpus > 1: also run the reference's all_reduce(SUM) of the metric sums as a cross-check of the all-gather")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal only: all ranks use cuda:0 (with --backend gloo; RCCL needs one GPU per rank)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, rank 0's users; "
+                         "a fixed, seeded sample of users when the whole exceeds 64 MB), to compare two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _strip(row):
@@ -152,6 +159,28 @@ def e2e_runner(model, dev, n_users):
                 "runs": runs}
     finally:
         shutil.rmtree(root, ignore_errors=True)
+
+
+def dump_outputs(out_dir, out, K, hit_rank_all=None):
+    """--dump-outputs: the arrays the timed step's caller receives, per user (sequences (users, K, T) and sequences_scores
+    (users, K), user-major as generate() returns them), as float32 .npy files; token ids are exact in float32.  user_index.npy
+    names the users written: all of them, or a fixed, seeded sample when the whole would exceed DUMP_CAP_BYTES.  Under N > 1
+    ranks this is rank 0's batch, plus hit_rank_all_ranks.npy: the gathered hit ranks of every rank's users, by user index."""
+    seqs = out["sequences"].cpu().numpy()
+    B = seqs.shape[0] // K
+    per_user = {"sequences": seqs.reshape(B, K, -1)}
+    if out["sequences_scores"] is not None:
+        per_user["sequences_scores"] = out["sequences_scores"].cpu().numpy().reshape(B, K)
+    whole = {} if hit_rank_all is None else {"hit_rank_all_ranks": hit_rank_all}
+    budget = DUMP_CAP_BYTES - 1024 - sum(a.size * 4 for a in whole.values())  # (1024: the .npy headers)
+    user_bytes = 4 * (1 + sum(a[0].size for a in per_user.values()))  # (+ its user_index entry)
+    users = np.arange(B)
+    if B * user_bytes > budget:
+        users = np.sort(np.random.default_rng(0).choice(B, max(0, budget // user_bytes), replace=False))
+    arrays = {"user_index": users, **{k: a[users] for k, a in per_user.items()}, **whole}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -324,6 +353,8 @@ def main():
         if distributed:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:  # (outside the timed region)
+        dump_outputs(args.dump_outputs, out, K, allr[np.argsort(rec["user_idx"])] if distributed else None)
 
     users = world * B * args.steps
     result = {

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -37,9 +38,13 @@ def _check(r, n_gpus, steps):
     assert r["output_check"]["all_in_trie"] is True
 
 
-def test_bench_contract_single_process():
-    r = _run([sys.executable, "bench.py", *SMALL, "--cpu-users", "1", "--ragged", "--item-pool", "9"])
+def test_bench_contract_single_process(tmp_path):
+    r = _run([sys.executable, "bench.py", *SMALL, "--cpu-users", "1", "--ragged", "--item-pool", "9", "--dump-outputs", str(tmp_path)])
     _check(r, 1, 2)
+    # --dump-outputs: the last timed step's sequences and scores, per user
+    seqs, scores = np.load(tmp_path / "sequences.npy"), np.load(tmp_path / "sequences_scores.npy")
+    assert seqs.dtype == scores.dtype == np.float32 and scores.shape == (6, 5) and [30, seqs.shape[2]] == r["output_check"]["sequences_shape"]
+    assert np.array_equal(np.load(tmp_path / "user_index.npy"), np.arange(6)) and np.all(np.diff(scores, axis=1) <= 0)
     roof = r["roofline"]
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(roof) and roof["bound"] in ("hbm", "mfma")
     assert abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-9 and roof["achieved"] > 0
@@ -49,13 +54,16 @@ def test_bench_contract_single_process():
     assert ic["pool"] == 9 and ic["passages_from_cache_per_step"] > 0 and ic["passages_encoded_per_step"] >= 6
 
 
-def test_bench_spawns_its_own_ranks_and_exchanges_hit_ranks():
+def test_bench_spawns_its_own_ranks_and_exchanges_hit_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher: the parent starts both ranks before touching the GPU; the timed region ends
     with the hit-rank all-gather + all-reduce cross-check (gloo here: the two ranks share the one test GPU)."""
-    r = _run([sys.executable, "bench.py", "--gpus", "2", *SMALL, "--cpu-users", "0", "--backend", "gloo", "--share-device"])
+    r = _run([sys.executable, "bench.py", "--gpus", "2", *SMALL, "--cpu-users", "0", "--backend", "gloo", "--share-device",
+              "--dump-outputs", str(tmp_path)])
     _check(r, 2, 2)
     ex = r["exchange"]
     assert ex["users_gathered"] == 12 and "all_gather_into_tensor" in ex["collective"]
+    hits = np.load(tmp_path / "hit_rank_all_ranks.npy")  # every rank's users; rank 0's sequences
+    assert hits.shape == (12,) and np.all((hits >= -1) & (hits < 5)) and np.load(tmp_path / "sequences.npy").shape[:2] == (6, 5)
     assert set(ex["metrics_vs_synthetic_gold"]) == {"hit@5", "hit@10", "ndcg@5", "ndcg@10"}
 
 

@@ -261,3 +261,23 @@ def test_error_codes_of_the_c_abi_map_to_messages():
         _lib.check(_lib.E_NONFINITE, "gram_generate")
     with pytest.raises(_lib.GramHipError, match="hipError 719"):
         _lib.check(719, "call")
+
+
+def test_bench_dump_outputs_writes_whole_users_and_a_seeded_sample_past_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 arrays per user; past the size cap a fixed, seeded sample of whole users, rows intact."""
+    import bench
+    B, K, T = 8, 5, 6
+    out = gram_amd.model.gram.GenerateOutput(sequences=torch.arange(B * K * T).view(B * K, T), sequences_scores=torch.randn(B * K))
+    bench.dump_outputs(str(tmp_path / "all"), out, K)
+    seqs, scores = np.load(tmp_path / "all" / "sequences.npy"), np.load(tmp_path / "all" / "sequences_scores.npy")
+    assert seqs.dtype == scores.dtype == np.float32 and seqs.shape == (B, K, T) and scores.shape == (B, K)
+    assert np.array_equal(seqs.reshape(B * K, T), out["sequences"].numpy()) and np.array_equal(scores.ravel(), out["sequences_scores"].numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "user_index.npy"), np.arange(B))
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 1024 + 3 * 4 * (1 + K * T + K))  # room for three users
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, K)
+    users = np.load(tmp_path / "a" / "user_index.npy").astype(int)
+    assert len(users) == 3 and np.array_equal(users, np.load(tmp_path / "b" / "user_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "sequences.npy"), seqs[users])
+    assert np.array_equal(np.load(tmp_path / "a" / "sequences_scores.npy"), scores[users])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_CAP_BYTES
