@@ -164,6 +164,13 @@ SIGNATURES = {
                                               vp, C.c_int, vp]),
     "gram_generate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
                                 vp, i64, vp, vp, C.POINTER(i32), vp]),
+    # teacher-forced decoder pass
+    "gram_workspace_bytes_tf": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gram_teacher_forced": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Compaction), vp, vp, C.c_int, C.c_int, vp, i64,
+                                      vp, vp, vp, vp]),
+    "gram_dec_self_attn_tf_split": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp]),
+    "gram_cross_attn_rows_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, vp, vp, vp]),
+    "gram_label_logprob_split": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
 }
 
 # the `_f16` aliases (gram_hip.h): same signatures as the `_bf16` names

@@ -81,6 +81,7 @@ struct Workspace {
   gram_live_rows_t live;
   int32_t* width;
   uint32_t* key_bits;  // [B][128]  the cross-attention's bit view of the mask (gram_mask_key_bits), once per generate
+  int32_t* rowmap;     // teacher-forced pass only: gram_cross_attn_rows_split's row tables [B * (1 + 2 * GRAM_MAX_BEAMS)]
   int64_t bytes;
   // two-piece mode (gram_split_t): what a GEMM reads (h, attn, u, hd, attnd, ud) is ONE interleaved buffer of twice the row length;
   // what only attention kernels read (qkv, the bank, qkvd, qx, the cache) is `pieces` planar copies, these many elements apart
@@ -666,4 +667,188 @@ extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids,
     if (host[1] != 0) return GRAM_E_BEAM;
   }
   return 0;
+}
+
+// ---- teacher-forced decoder pass (gram_teacher_forced) -----------------------------------------------------------------------------
+namespace {
+
+int check_shapes_tf(const gram_model* m, int B, int N, int L, int C, int T) {
+  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > GRAM_MAX_PASSAGE_LEN || (L & 31) || N * L > 4096 || C < 1 ||
+      T < 1 || T > GRAM_MAX_DEC_LEN || (int64_t)B * C * T > INT32_MAX / 4)
+    return GRAM_E_ARG;
+  return 0;
+}
+
+// The bank and the small tables first; then the encoder's buffers, and the decoder's R = B*C*T rows IN THE SAME BYTES: the encoder's
+// activations are dead once the bank GEMM has read w.h (stream order), and the two together would be most of a large call's workspace.
+Workspace carve_tf(const gram_model* m, void* ws, int B, int N, int L, int C, int T) {
+  const gram_model_desc_t& c = m->d;
+  const int64_t d = c.d_model, inner = (int64_t)c.n_heads * 64, F = c.d_ff, V = c.vocab;
+  const int64_t Me = (int64_t)B * N * L, S = (int64_t)N * L, R = (int64_t)B * C * T, nl = c.n_dec_layers;
+  Carve cv(ws);
+  Workspace w{};
+  const int64_t P = c.pieces > 1 ? c.pieces : 1;
+  w.pieces = (int)P;
+  w.ps_qkv = Me * 3 * inner;
+  w.ps_bank = nl * B * c.n_heads * S * 64;
+  w.ps_qkvd = R * 3 * inner;
+  w.ps_qx = R * inner;
+  w.key_bits = cv.take<uint32_t>((int64_t)B * 128);
+  w.rowmap = cv.take<int32_t>((int64_t)B * (1 + 2 * GRAM_MAX_BEAMS));
+  w.bank_k = cv.take<p16>(P * w.ps_bank);
+  w.bank_vt = cv.take<p16>(P * w.ps_bank);
+  const int64_t shared = cv.off;
+  w.x = cv.take<float>(Me * d);
+  w.h = cv.take<p16>(P * Me * d);
+  w.qkv = cv.take<p16>(P * w.ps_qkv);
+  w.attn = cv.take<p16>(P * Me * inner);
+  w.u = cv.take<p16>(P * Me * F);
+  w.ss = cv.take<float>(ss_floats(Me, d));
+  w.rs = cv.take<float>(Me);
+  w.xs[0] = cv.take<float>(Me);
+  w.xs[1] = cv.take<float>(Me);
+  const int64_t enc_end = cv.off;
+  cv.off = shared;
+  w.xd = cv.take<float>(R * d);
+  w.hd = cv.take<p16>(P * R * d);
+  w.qkvd = cv.take<p16>(P * w.ps_qkvd);
+  w.attnd = cv.take<p16>(P * R * inner);
+  w.qx = cv.take<p16>(P * w.ps_qx);
+  w.ud = cv.take<p16>(P * R * F);
+  w.ssd = cv.take<float>(ss_floats(R, d));
+  w.rsd = cv.take<float>(R);
+  w.xsd[0] = cv.take<float>(R);
+  w.xsd[1] = cv.take<float>(R);
+  w.lse = cv.take<float>(R);
+  w.lse_part = cv.take<float>(R * (V / 64) * 2);
+  const int64_t end = cv.off > enc_end ? cv.off : enc_end;
+  w.bytes = (end + 255) & ~(int64_t)255;
+  return w;
+}
+
+// The decoder layers over R = B * Q rows (Q = C * T per user): decode_step's GEMMs, norm fusion and stage caps, with the stepped
+// self-attention replaced by the whole-sequence one and the cross-attention taking all Q rows of a user; then the final norm with the
+// tied-embedding scale and the lm_head GEMM with its LSE partials (logits stored when given).
+int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, const uint8_t* mask, int B, int N, int L, int Q, int T,
+               float* logits, void* st) {
+  const gram_model_desc_t& c = m->d;
+  const int d = c.d_model, inner = c.n_heads * 64, F = c.d_ff, H = c.n_heads, V = c.vocab;
+  const int R = B * Q, S = N * L;
+  auto self_attn = [&]() { return gram_dec_self_attn_tf_split(w.qkvd, c.dec_bias_f32, w.attnd, R / T, T, H, w.pieces, w.ps_qkvd, st); };
+  const size_t bank_layer = (size_t)B * H * S * 64;
+  auto cross_attn = [&](int i) {
+    return gram_cross_attn_rows_split(w.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, w.attnd, B, Q, H, S, w.pieces,
+                                      w.ps_qx, w.ps_bank, w.key_bits, w.rowmap, st);
+  };
+  if (c.fold_norm) {
+    const int quarter = R <= gram_gemm_stream_max_m() && d % 128 == 0 && inner % 128 == 0 && F % 128 == 0;
+    const bool pre_rs = R >= kPrecomputedRsRows;  // see encoder_layers
+    int np = 0;
+    auto produce = [&]() { return gram_norm_fusion_t{w.hd, w.ssd, nullptr, 0, 0, 0.f, quarter, w.xsd[np & 1], nullptr}; };
+    auto consume = [&](bool from_embed) {
+      const gram_norm_fusion_t nf = pre_rs ? gram_norm_fusion_t{nullptr, nullptr, w.rsd, 0, d, c.eps, 0, nullptr, nullptr}
+                                           : gram_norm_fusion_t{nullptr, nullptr, w.ssd, d / 64, d, c.eps, from_embed ? 0 : quarter,
+                                                                w.xsd[np & 1], w.xsd[(np + 1) & 1]};
+      return nf;
+    };
+    auto norm_point = [&]() -> int {
+      return pre_rs ? gram_row_rscale_xs(w.ssd, w.rsd, w.xsd[np & 1], w.xsd[(np + 1) & 1], R, d / 64, d, c.eps, st) : 0;
+    };
+    TRY(gram_embed_ex_xs(c.embed_f32, tokens, 0, w.xd, w.hd, w.ssd, w.xsd[0], d / 64, R, d, w.pieces, st));
+    for (int i = 0; i < c.n_dec_layers; ++i) {
+      TRY(norm_point());
+      TRY(cap_inter(w, w.hd, R, d, GRAM_STAGE_DEC_SELF, st));
+      {
+        const gram_norm_fusion_t nf = consume(i == 0);
+        TRY(linear(w, w.hd, m->dec_wqkv[i], m->s_dec_wqkv[i], w.qkvd, C_PLANAR, w.ps_qkvd, R, 3 * inner, d, GRAM_EPI_BF16, nullptr, &nf, st));
+      }
+      ++np;
+      TRY(cap_planar(w, w.qkvd, w.ps_qkvd, GRAM_STAGE_DEC_SELF, st));
+      TRY(self_attn());
+      TRY(cap_inter(w, w.attnd, R, inner, GRAM_STAGE_DEC_SELF, st));
+      {
+        const gram_norm_fusion_t nf = produce();
+        TRY(linear(w, w.attnd, m->dec_wo[i], m->s_dec_wo[i], w.xd, C_NONE, 0, R, d, inner, GRAM_EPI_F32_ADD, nullptr, &nf, st));
+      }
+      TRY(norm_point());
+      TRY(cap_inter(w, w.hd, R, d, GRAM_STAGE_DEC_CROSS, st));
+      {
+        const gram_norm_fusion_t nf = consume(false);
+        TRY(linear(w, w.hd, m->dec_wq_x[i], m->s_dec_wq_x[i], w.qx, C_PLANAR, w.ps_qx, R, inner, d, GRAM_EPI_BF16, nullptr, &nf, st));
+      }
+      ++np;
+      TRY(cap_planar(w, w.qx, w.ps_qx, GRAM_STAGE_DEC_CROSS, st));
+      TRY(cross_attn(i));
+      TRY(cap_inter(w, w.attnd, R, inner, GRAM_STAGE_DEC_CROSS, st));
+      {
+        const gram_norm_fusion_t nf = produce();
+        TRY(linear(w, w.attnd, m->dec_wo_x[i], m->s_dec_wo_x[i], w.xd, C_NONE, 0, R, d, inner, GRAM_EPI_F32_ADD, nullptr, &nf, st));
+      }
+      TRY(norm_point());
+      TRY(cap_inter(w, w.hd, R, d, GRAM_STAGE_DEC_FFN, st));
+      {
+        const gram_norm_fusion_t nf = consume(false);
+        TRY(linear(w, w.hd, m->dec_wi[i], m->s_dec_wi[i], w.ud, C_INTER, 0, R, F, d, GRAM_EPI_BF16_RELU, nullptr, &nf, st));
+      }
+      ++np;
+      TRY(cap_inter(w, w.ud, R, F, GRAM_STAGE_DEC_FFN, st));
+      {
+        const gram_norm_fusion_t nf = produce();
+        TRY(linear(w, w.ud, m->dec_wo2[i], m->s_dec_wo2[i], w.xd, C_NONE, 0, R, d, F, GRAM_EPI_F32_ADD, nullptr, &nf, st));
+      }
+    }
+  } else {  // (one piece only)
+    TRY(gram_embed_i32(c.embed_f32, tokens, w.xd, R, d, st));
+    for (int i = 0; i < c.n_dec_layers; ++i) {
+      TRY(gram_rmsnorm_bf16_split(w.xd, m->dec_ln1[i], w.hd, R, d, c.eps, 1.f, nullptr, 1, 1, nullptr, 1, st));
+      TRY(linear(w, w.hd, m->dec_wqkv[i], m->s_dec_wqkv[i], w.qkvd, C_PLANAR, 0, R, 3 * inner, d, GRAM_EPI_BF16, nullptr, nullptr, st));
+      TRY(self_attn());
+      TRY(linear(w, w.attnd, m->dec_wo[i], m->s_dec_wo[i], w.xd, C_NONE, 0, R, d, inner, GRAM_EPI_F32_ADD, nullptr, nullptr, st));
+      TRY(gram_rmsnorm_bf16_split(w.xd, m->dec_ln2[i], w.hd, R, d, c.eps, 1.f, nullptr, 1, 1, nullptr, 1, st));
+      TRY(linear(w, w.hd, m->dec_wq_x[i], m->s_dec_wq_x[i], w.qx, C_PLANAR, 0, R, inner, d, GRAM_EPI_BF16, nullptr, nullptr, st));
+      TRY(cross_attn(i));
+      TRY(linear(w, w.attnd, m->dec_wo_x[i], m->s_dec_wo_x[i], w.xd, C_NONE, 0, R, d, inner, GRAM_EPI_F32_ADD, nullptr, nullptr, st));
+      TRY(gram_rmsnorm_bf16_split(w.xd, m->dec_ln3[i], w.hd, R, d, c.eps, 1.f, nullptr, 1, 1, nullptr, 1, st));
+      TRY(linear(w, w.hd, m->dec_wi[i], m->s_dec_wi[i], w.ud, C_PLANAR, 0, R, F, d, GRAM_EPI_BF16_RELU, nullptr, nullptr, st));
+      TRY(linear(w, w.ud, m->dec_wo2[i], m->s_dec_wo2[i], w.xd, C_NONE, 0, R, d, F, GRAM_EPI_F32_ADD, nullptr, nullptr, st));
+    }
+  }
+  const float scale = c.tie_word_embeddings ? 1.0f / sqrtf((float)d) : 1.f;  // gram_t5.py:249-252
+  TRY(gram_rmsnorm_bf16_split(w.xd, c.dec_final_ln, w.hd, R, d, c.eps, scale, nullptr, 1, 1, nullptr, w.pieces, st));
+  TRY(cap_inter(w, w.hd, R, d, GRAM_STAGE_LM_HEAD, st));
+  const gram_split_t sp{w.pieces, 0, 0, 0, m->s_lm};
+  TRY(gram_gemm_bf16_lse_split(w.hd, c.lm_head_bf16, logits, w.lse_part, R, V, d, w.pieces * d, V, &sp, st));
+  return gram_lse_combine(w.lse_part, w.lse, R, V / 64, st);
+}
+
+}  // namespace
+
+extern "C" int64_t gram_workspace_bytes_tf(const gram_model_t* m, int B, int N, int L, int C, int T) {
+  if (check_shapes_tf(m, B, N, L, C, T)) return GRAM_E_ARG;
+  return carve_tf(m, nullptr, B, N, L, C, T).bytes;
+}
+
+extern "C" int gram_teacher_forced(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                                   const gram_compaction_t* comp, const int32_t* dec_ids, const int32_t* labels, int C, int T,
+                                   void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
+                                   void* stream) {
+  TRY(check_shapes_tf(m, B, N, L, C, T));
+  if (!mask || !dec_ids || !labels || !token_logp || !seq_logp || (!comp && !input_ids)) return GRAM_E_ARG;
+  if (comp) {  // (as gram_generate_ex)
+    const int n_enc = comp->n_active - comp->n_cached;
+    if (comp->n_active < B || comp->n_active > B * N || !comp->passage_map || comp->n_cached < 0 || n_enc < 0) return GRAM_E_ARG;
+    if (n_enc > 0 && (!comp->ids || !comp->mask)) return GRAM_E_ARG;
+    if (comp->n_cached > 0 && (!comp->cache_x || !comp->cache_slot || comp->cache_L < 1)) return GRAM_E_ARG;
+  }
+  Workspace w = carve_tf(m, workspace, B, N, L, C, T);
+  if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
+  const gram_model_desc_t& c = m->d;
+  if (comp)
+    TRY(encode(m, w, comp->ids, comp->mask, mask, B, N, L, comp->n_active, comp->passage_map,
+               CachedPassages{comp->n_cached, comp->cache_L, comp->cache_x, comp->cache_slot}, stream));
+  else
+    TRY(encode(m, w, input_ids, mask, mask, B, N, L, B * N, nullptr, CachedPassages{0, 0, nullptr, nullptr}, stream));
+  TRY(decoder_tf(m, w, dec_ids, mask, B, N, L, C * T, T, logits, stream));
+  return gram_label_logprob_split(w.hd, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, labels, B * C, T, c.vocab, w.pieces,
+                                  token_logp, seq_logp, stream);
 }

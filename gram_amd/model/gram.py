@@ -7,7 +7,9 @@ Same constructor (``GRAM(config)``), same state-dict key layout (SURVEY.md §3.4
 late fusion, the beam-shared KV bank, and the Trie-constrained beam search all stay on the
 device; there is no PyTorch-op or CPU fallback.
 
-Out of scope here (training half): ``forward`` with labels.
+``forward(input_ids, attention_mask, labels=...)`` -- the reference runners' loss call -- and ``score_sequences`` (log p(item | user)
+for given candidates) run the teacher-forced decoder pass on the device (``gram_teacher_forced``).  Out of scope (SURVEY.md §8,
+training half): the backward pass -- ``loss.backward()`` raises.
 """
 from __future__ import annotations
 
@@ -29,6 +31,41 @@ class GenerateOutput(dict):
     (single_runner_gram.py:654-655)."""
 
     __getattr__ = dict.get
+
+
+class ForwardOutput(dict):
+    """What ``GRAM.forward`` returns unless ``return_dict=False``: ``.loss`` (None without labels) and ``.logits`` (B, T, V), like
+    HF's Seq2SeqLMOutput; integer indexing walks the non-None fields in that order (``out[0]`` is the loss when there is one)."""
+
+    __getattr__ = dict.get
+
+    def to_tuple(self):
+        return tuple(v for v in (self.get("loss"), self.get("logits")) if v is not None)
+
+    def __getitem__(self, k):
+        return self.to_tuple()[k] if isinstance(k, (int, slice)) else dict.__getitem__(self, k)
+
+
+def shift_right(labels: torch.Tensor, start_token: int = 0, pad_token: int = 0) -> torch.Tensor:
+    """T5's ``_shift_right`` (gram_t5_modeling.py:935-964): the decoder inputs of teacher forcing -- the start token, then the labels
+    without their last position, with the ignored label -100 replaced by the pad token."""
+    out = labels.new_zeros(labels.shape)
+    out[..., 1:] = labels[..., :-1]
+    out[..., 0] = start_token
+    return out.masked_fill(out == -100, pad_token)
+
+
+class _NoBackward(torch.autograd.Function):
+    """Carries the teacher-forced loss into autograd so that ``loss.backward()`` fails loudly instead of with torch's "does not
+    require grad": the HIP path has no backward yet."""
+
+    @staticmethod
+    def forward(ctx, loss, anchor):
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise NotImplementedError("backward is not implemented on the HIP path")
 
 
 class _Node(nn.Module):
@@ -245,11 +282,140 @@ class GRAM(nn.Module):
     def set_checkpoint(self, use_checkpoint):
         pass
 
-    def forward(self, input_ids=None, attention_mask=None, **kwargs):
-        raise NotImplementedError(
-            "gram_amd implements the generative *scoring* path (GRAM.generate). The teacher-forced training "
-            "forward/backward (SURVEY.md §8f N4) is out of scope of this build."
-        )
+    def forward(self, input_ids=None, attention_mask=None, labels=None, decoder_input_ids=None, decoder_attention_mask=None,
+                return_dict=None, output_attentions=None, output_hidden_states=None, **kwargs):
+        """GRAM.forward (gram.py:50-60) -> T5ForConditionalGeneration_GRAM.forward (gram_t5.py:181-263) on the device, teacher forced.
+
+        input_ids / attention_mask (B, N, L); labels (B, T) with -100 for ignored positions; decoder_input_ids (B, T) default to
+        ``shift_right(labels)``.  ``return_dict=False`` gives ``(loss, logits)`` -- ``(logits,)`` without labels --, anything else a
+        ``ForwardOutput`` with ``.loss`` / ``.logits``.  The loss is CrossEntropyLoss(ignore_index=-100): the mean over the labels
+        that are not ignored.  ``past_key_values`` and the encoder states are not returned.  There is no backward pass: with grad
+        enabled and trainable parameters, ``loss.backward()`` raises NotImplementedError."""
+        if self._device().type != "cuda":
+            raise NotImplementedError("gram_amd.GRAM.forward runs on a ROCm device (model.to('cuda')); there is no CPU path")
+        if output_attentions or output_hidden_states:
+            raise NotImplementedError("output_attentions / output_hidden_states are not returned by the HIP path")
+        if decoder_attention_mask is not None and not bool(torch.as_tensor(decoder_attention_mask).ne(0).all()):
+            raise NotImplementedError("a decoder_attention_mask with masked positions is not supported: the HIP decoder is causal only, "
+                                      "as the reference's forward(labels) is")
+        for k, v in kwargs.items():
+            if v is not None and k not in ("use_cache",):
+                raise NotImplementedError(f"forward({k}=...) is not supported by the HIP path")
+        if labels is None and decoder_input_ids is None:
+            raise ValueError("forward needs labels or decoder_input_ids (as HF's T5ForConditionalGeneration)")
+        if input_ids is None or input_ids.dim() != 3:
+            raise ValueError("input_ids must be (B, N, L)")
+        dev = self._device()
+        lab = None if labels is None else self._check_labels(labels.to(dev))
+        if lab is not None and lab.dim() != 2:
+            raise ValueError("labels must be (B, T)")
+        dec = shift_right(lab) if decoder_input_ids is None else decoder_input_ids.to(dev)
+        if dec.dim() != 2 or dec.shape[0] != input_ids.shape[0] or (lab is not None and lab.shape != dec.shape):
+            raise ValueError("decoder_input_ids / labels must be (B, T) with B = input_ids.shape[0]")
+        lab_k = lab if lab is not None else torch.full_like(dec, -100)
+        logits, tok, _seq = self._teacher_forced(input_ids, attention_mask, dec[:, None, :], lab_k[:, None, :], want_logits=True)
+        logits = logits[:, 0]
+        loss = None
+        if lab is not None:
+            n = int(lab.ne(-100).sum())
+            loss = -(tok.double().sum() / n).float() if n else torch.full((), float("nan"), device=dev)
+            anchor = self.get_parameter("shared.weight")
+            if torch.is_grad_enabled() and anchor.requires_grad:
+                loss = _NoBackward.apply(loss, anchor)
+        if return_dict is False:
+            return (logits,) if loss is None else (loss, logits)
+        return ForwardOutput(loss=loss, logits=logits)
+
+    @torch.no_grad()
+    def score_sequences(self, input_ids, attention_mask, labels, return_tokens: bool = False, users_per_call: Optional[int] = None):
+        """log p(sequence | user) of given candidates, teacher forced: re-ranking a retrieval stage, sampled-negative evaluation,
+        checking a beam's ``sequences_scores``.  input_ids / attention_mask (B, N, L); labels (B, C, T) in label form -- no start
+        token, -100 after the end.  Returns the (B, C) fp32 sums of the token log-probs (full-vocabulary log_softmax, as a beam's
+        running score), and with ``return_tokens`` also the (B, C, T) token log-probs (0 at ignored positions).  Users are scored
+        in chunks whose workspace fits the free HBM (``users_per_call`` overrides); a user's scores do not depend on the chunk."""
+        if self._device().type != "cuda":
+            raise NotImplementedError("gram_amd.GRAM.score_sequences runs on a ROCm device (model.to('cuda')); there is no CPU path")
+        if input_ids.dim() != 3 or labels.dim() != 3 or labels.shape[0] != input_ids.shape[0]:
+            raise ValueError("input_ids must be (B, N, L) and labels (B, C, T)")
+        lab = self._check_labels(labels.to(self._device()))
+        _logits, tok, seq = self._teacher_forced(input_ids, attention_mask, shift_right(lab), lab, want_logits=False,
+                                                 users_per_call=users_per_call)
+        return (seq, tok) if return_tokens else seq
+
+    def _check_labels(self, labels: torch.Tensor) -> torch.Tensor:
+        V = self.config.vocab_size
+        if labels.numel() and not bool(((labels >= 0) & (labels < V) | (labels == -100)).all()):
+            raise ValueError(f"labels must lie in [0, {V}) or be -100 (ignored)")
+        return labels
+
+    def max_users_per_call_tf(self, N: int, L: int, C_: int, T: int, want_logits: bool = False, limit: int = 1 << 20,
+                              headroom: float = 0.9) -> int:
+        """Largest B <= limit whose teacher-forced workspace (gram_workspace_bytes_tf) and outputs fit the free HBM, net of what a
+        reserved passage cache will still allocate (``reserve_passage_cache``)."""
+        handle = self._pack()
+        lib = _lib.load()
+        dev = self._device()
+        Lp = (int(L) + 31) // 32 * 32
+        free, _total = torch.cuda.mem_get_info(dev)
+        if self._workspace is not None and self._workspace.device == dev:
+            free += self._workspace.numel()
+        pc_have = 0 if self._pcache is None else int(self._pcache["x"].shape[0])
+        pc_more = max(0, int(getattr(self, "_pcache_reserve", 0)) - pc_have)
+        budget = int(free * headroom) - pc_more * self._CACHE_L * (self.config.d_model * 4 + 4)
+        per_user_out = C_ * T * 4 * (2 + (self.config.vocab_size if want_logits else 0))
+
+        def need(b):
+            w = lib.gram_workspace_bytes_tf(handle, b, N, Lp, C_, T)
+            return -1 if w < 0 else w + b * per_user_out
+
+        lo, hi = 1, max(1, int(limit))
+        if 0 <= need(hi) <= budget:
+            return hi
+        while lo < hi:  # bytes grow monotonically with B
+            mid = (lo + hi + 1) // 2
+            if 0 <= need(mid) <= budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
+    def _teacher_forced(self, input_ids, attention_mask, dec, lab, want_logits: bool, users_per_call: Optional[int] = None):
+        """(logits (B,C,T,V) or empty, token log-probs (B,C,T), sequence sums (B,C)) over user chunks of torch.ops.gram.teacher_forced."""
+        handle = self._pack()
+        lib = _lib.load()
+        dev = self._device()
+        B, N, L = input_ids.shape
+        _, Cn, T = dec.shape
+        if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN:
+            raise ValueError(f"sequences of 1..{_lib.GRAM_MAX_DEC_LEN} positions are supported (got {T})")
+        ids = input_ids.to(dev, torch.int64)
+        mask = attention_mask.to(dev).ne(0).view(torch.uint8) if attention_mask.dtype != torch.bool else attention_mask.to(dev).view(torch.uint8)
+        Lp = (L + 31) // 32 * 32  # masked padding is invisible to attention: pad L to the kernel tile (as generate)
+        if Lp != L:
+            ids = torch.nn.functional.pad(ids, (0, Lp - L))
+            mask = torch.nn.functional.pad(mask, (0, Lp - L))
+        dec = dec.to(dev, torch.int32).contiguous()
+        lab = lab.to(dev, torch.int32).contiguous()
+        step = int(users_per_call) if users_per_call else self.max_users_per_call_tf(N, Lp, Cn, T, want_logits, limit=B)
+        from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
+        outs = []
+        for b0 in range(0, B, max(1, step)):
+            b1 = min(B, b0 + max(1, step))
+            nb = b1 - b0
+            cid, cmask = ids[b0:b1].contiguous(), mask[b0:b1].contiguous()
+            comp, _harvest = self._plan(cid, cmask, nb, N, Lp)
+            need = lib.gram_workspace_bytes_tf(handle, nb, N, Lp, Cn, T)
+            if need < 0:
+                raise _lib.GramHipError(f"unsupported problem size B={nb} N={N} L={Lp} C={Cn} T={T} (N <= max_item_num+1, L <= 128, "
+                                        f"N*L <= 4096, T <= {_lib.GRAM_MAX_DEC_LEN})")
+            ws = self._ensure_workspace(need)
+            ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
+            outs.append(torch.ops.gram.teacher_forced(
+                cid, cmask, int(handle), ws, dec[b0:b1], lab[b0:b1], int(self.config.vocab_size), bool(want_logits), ct["comp_map"],
+                ct["comp_ids"], ct["comp_mask"], ct["cache_slot"], ct["cache_x"], int(ct["n_cached"]), int(ct["cache_L"])))
+        if len(outs) == 1:
+            return outs[0]
+        return tuple(torch.cat([o[i] for o in outs]) if (i or want_logits) else outs[0][0] for i in range(3))
 
     # ------------------------------------------------------------------ device packing
     def _device(self) -> torch.device:
@@ -404,6 +570,9 @@ class GRAM(nn.Module):
                 f"unsupported problem size B={B} N={N} L={L} K={K} max_length={max_length} "
                 f"(N <= max_item_num+1, L <= 128, K <= 64, max_length <= {_lib.GRAM_MAX_DEC_LEN})"
             )
+        return self._ensure_workspace(need)
+
+    def _ensure_workspace(self, need: int) -> torch.Tensor:
         dev = self._device()
         if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
             self._workspace = None

@@ -6,6 +6,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
 (there is no CPU path in gram_amd; the CPU restatement lives in oracle/ and is test infrastructure).
 
     torch.ops.gram.generate          GRAM.generate's whole path (gram_generate_ex) -- what ``GRAM.generate`` calls
+    torch.ops.gram.teacher_forced    the teacher-forced decoder pass (gram_teacher_forced) -- ``GRAM.forward(labels=...)`` and
+                                     ``GRAM.score_sequences``
     torch.ops.gram.linear            nn.Linear without bias: A @ W^T on the 16-bit MFMA (gram_gemm_bf16, 16-bit epilogue)
     torch.ops.gram.enc_self_attn     T5Attention self branch on (P*L, 3*inner) q|k|v rows (gram_enc_self_attn)
     torch.ops.gram.cross_attn_decode the fusion read of one decoder layer and step over the beam-shared bank
@@ -87,6 +89,57 @@ def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_t
     return (input_ids.new_empty(B * num_return_sequences, max_length),
             input_ids.new_empty(B * num_return_sequences if num_beams > 1 else 0, dtype=torch.float32),
             torch.empty(1, dtype=torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------- teacher-forced pass
+@torch.library.custom_op("gram::teacher_forced", mutates_args=("workspace",), device_types="cuda")
+def teacher_forced(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, decoder_input_ids: Tensor, labels: Tensor,
+                   vocab_size: int, want_logits: bool, comp_map: Optional[Tensor], comp_ids: Optional[Tensor],
+                   comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor], n_cached: int,
+                   cache_L: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """input_ids i64 (B,N,L), attention_mask u8 (B,N,L), ``handle`` a gram_model_t* as int, ``workspace`` a u8 scratch tensor of
+    gram_workspace_bytes_tf; decoder_input_ids i32 (B,C,T) in [0, vocab_size), labels i32 (B,C,T) < vocab_size (< 0 = ignored);
+    comp_* / cache_* the gram_compaction_t fields (None = off).  Returns (logits f32 (B,C,T,V) -- empty unless want_logits --,
+    token log-probs f32 (B,C,T) -- 0 where the label is ignored --, their per-sequence sums f32 (B,C))."""
+    lib = _lib.load()
+    dev = input_ids.device
+    if input_ids.dim() != 3 or decoder_input_ids.dim() != 3:
+        raise ValueError("teacher_forced: input_ids must be (B, N, L) and decoder_input_ids (B, C, T)")
+    B, N, L = input_ids.shape
+    Bd, Cn, T = decoder_input_ids.shape
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    _check("decoder_input_ids", decoder_input_ids, torch.int32, (B, None, None), dev)
+    _check("labels", labels, torch.int32, (B, Cn, T), dev)
+    if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN or Cn < 1:
+        raise ValueError(f"teacher_forced: need 1 <= T <= {_lib.GRAM_MAX_DEC_LEN} and C >= 1 (got C={Cn}, T={T})")
+    # token ids index the embedding and lm_head tables on the device: out-of-range ones are refused here, not read there
+    lo_d, hi_d, hi_l = torch.stack([decoder_input_ids.min(), decoder_input_ids.max(), labels.max()]).tolist()
+    if lo_d < 0 or hi_d >= vocab_size or hi_l >= vocab_size:
+        raise ValueError(f"teacher_forced: decoder_input_ids must lie in [0, {vocab_size}) and labels below {vocab_size}")
+    comp = None
+    if comp_map is not None:
+        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
+                               _p(cache_slot))
+    logits = torch.empty((B, Cn, T, vocab_size) if want_logits else (0,), dtype=torch.float32, device=dev)
+    tok = torch.empty(B, Cn, T, dtype=torch.float32, device=dev)
+    seq = torch.empty(B, Cn, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.gram_teacher_forced(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
+                                     C.byref(comp) if comp is not None else None, decoder_input_ids.data_ptr(), labels.data_ptr(),
+                                     Cn, T, workspace.data_ptr(), workspace.numel(), logits.data_ptr() if want_logits else None,
+                                     tok.data_ptr(), seq.data_ptr(), _stream(input_ids))
+    _lib.check(rc, "gram_teacher_forced")
+    return logits, tok, seq
+
+
+@teacher_forced.register_fake
+def _(input_ids, attention_mask, handle, workspace, decoder_input_ids, labels, vocab_size, want_logits, comp_map, comp_ids, comp_mask,
+      cache_slot, cache_x, n_cached, cache_L):
+    B, Cn, T = decoder_input_ids.shape
+    f = dict(dtype=torch.float32)
+    return (decoder_input_ids.new_empty((B, Cn, T, vocab_size) if want_logits else (0,), **f),
+            decoder_input_ids.new_empty(B, Cn, T, **f), decoder_input_ids.new_empty(B, Cn, **f))
 
 
 # ---------------------------------------------------------------------------------------------- linear
@@ -222,4 +275,4 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
-__all__ = ["generate", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]
+__all__ = ["generate", "teacher_forced", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]

@@ -468,6 +468,48 @@ int64_t gram_workspace_encoder_x_offset(const gram_model_t* m, int B, int N, int
 int gram_gather_passage_x(const float* cache_x, const int32_t* slot, float* x, int n, int L, int cache_L, int d,
                           void* stream);
 
+/* ---- teacher-forced decoder pass (forward(labels) loss, sequence scores) ---------------------------------------------------
+ * T5ForConditionalGeneration_GRAM.forward with labels (gram_t5.py:181-263, reached through GRAM.forward gram.py:50-60): the decoder
+ * runs once over whole sequences -- decoder_input_ids = _shift_right(labels) (gram_t5_modeling.py:935-964), causal self-attention
+ * only (no decoder mask), cross-attention over the late-fused encoder states, final norm with the tied-embedding scale, lm_head --
+ * instead of one token per step.  The reference's CrossEntropyLoss(ignore_index=-100) (gram_t5.py:256-260) and a candidate's
+ * log p(item | user) are sums of the per-token log-probs returned here.
+ * Rows are user-major (b, c, t): B users x C sequences per user x T positions, R = B * C * T. */
+
+/* Bytes of scratch gram_teacher_forced needs for this problem size; < 0: GRAM_E_ARG. */
+int64_t gram_workspace_bytes_tf(const gram_model_t* m, int B, int N, int L, int C, int T);
+
+/* The encoder as gram_generate_ex runs it (compaction_host as there: ragged batches and the passage cache; NULL = every passage),
+ * then the decoder over the R rows.  dec_ids i32 [R] (decoder input tokens, in [0, vocab)), labels i32 [R] (< vocab; < 0 = ignored:
+ * token_logp 0, not counted in seq_logp).  logits f32 [R][vocab] or NULL (not materialised); token_logp f32 [R] = log_softmax(logits)
+ * [label]; seq_logp f32 [B * C] = the sum of a sequence's token_logp in position order.  T <= GRAM_MAX_DEC_LEN, C >= 1; shapes are
+ * checked before any launch (GRAM_E_ARG). */
+int gram_teacher_forced(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                        const gram_compaction_t* compaction_host, const int32_t* dec_ids, const int32_t* labels, int C, int T,
+                        void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp, void* stream);
+
+/* Causal self-attention of n_seq decoder sequences of T <= 64 positions, every position at once (T5Attention.forward self branch,
+ * unidirectional relative bias of layer 0 and causal mask, gram_t5_modeling.py:586-593).  qkv: planar pieces [n_seq * T][3 * inner]
+ * (row = seq * T + t), qkv_pstride elements apart; bias f32 [H][GRAM_MAX_DEC_LEN] by distance; out as gram_dec_self_attn_split's
+ * (interleaved [rows][2 * inner] when pieces = 2). */
+int gram_dec_self_attn_tf_split(const void* qkv, const float* bias, void* out, int n_seq, int T, int H, int pieces,
+                                int64_t qkv_pstride, void* stream);
+
+/* Cross-attention of Q query rows per user (row = b * Q + i) over that user's bank (gram_cross_attn_decode_split's arguments with
+ * K = Q).  Q <= GRAM_MAX_BEAMS is one gram_cross_attn_decode_split call; above, one call per group of <= GRAM_MAX_BEAMS rows, which
+ * needs rowmap: device scratch i32 [B * (1 + 2 * GRAM_MAX_BEAMS)] (may be NULL when Q <= GRAM_MAX_BEAMS). */
+int gram_cross_attn_rows_split(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out, int B, int Q,
+                               int H, int S, int pieces, int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits,
+                               int32_t* rowmap, void* stream);
+
+/* Label log-probs from the final hidden rows: token_logp[r] = hidden[r] . E[labels[r]] - lse[r] for labels[r] >= 0 (0 otherwise),
+ * the dot product being gram_beam_step_sparse_split's (E = lm_head_f32 when pieces = 2, lm_head_bf16 when 1), lse from
+ * gram_gemm_bf16_lse_split + gram_lse_combine; seq_logp[s] = sum over t of token_logp[s * T + t] with labels >= 0, in position
+ * order (deterministic: no atomics).  hidden as the lm_head GEMM's A operand ([R][pieces * d], interleaved when pieces = 2). */
+int gram_label_logprob_split(const void* hidden, const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse,
+                             const int32_t* labels, int n_seq, int T, int V, int pieces, float* token_logp, float* seq_logp,
+                             void* stream);
+
 /* ---- live per-kernel timing (bench.py) ------------------------------------------------ */
 enum gram_kernel_kind {
   GRAM_K_GEMM = 0,          /* work = 2*M*N*K flops per launch                              */
