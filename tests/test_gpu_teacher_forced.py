@@ -151,7 +151,7 @@ def test_score_sequences_many_rows_per_user(gpu):
 
 
 # ---------------------------------------------------------------------------------------------------------- 3. the kernels
-@pytest.mark.parametrize("pieces,T", [(1, 10), (2, 10), (2, 64), (1, 1)])
+@pytest.mark.parametrize("pieces,T", [(1, 10), (2, 10), (2, 64), (1, 1), (1, 64), (2, 33)])
 def test_dec_self_attn_tf_kernel_vs_fp64(gpu, pieces, T):
     torch.manual_seed(T)
     n_seq, H = 5, 4
@@ -177,44 +177,67 @@ def test_dec_self_attn_tf_kernel_vs_fp64(gpu, pieces, T):
     assert err < (2e-5 if pieces == 2 else 3e-3)
 
 
-@pytest.mark.parametrize("Q", [10, 64, 200])
-def test_cross_attn_rows_vs_decode_kernel_and_fp64(gpu, Q):
+@pytest.mark.parametrize("pieces,Q", [pytest.param(1, 10, id="10"), pytest.param(1, 64, id="64"), pytest.param(1, 200, id="200"),
+                                       (1, 65), (1, 128), (2, 10), (2, 65), (2, 128), (2, 200)])
+def test_cross_attn_rows_vs_decode_kernel_and_fp64(gpu, pieces, Q):
+    """Q = 65: a 1-row tail group; Q = 128: two full groups, no tail.  Two pieces: planar q / bank pieces and the interleaved output, as
+    gram_teacher_forced passes them (set up as tests/test_gpu_split.py test_split_cross_attn)."""
     torch.manual_seed(Q)
     B, H, S = 3, 2, 96
     inner = H * 64
-    q = (torch.randn(B * Q, inner, device=DEV) * 0.3).to(U.DT).contiguous()
-    kb = (torch.randn(B, H, S, 64, device=DEV) * 0.3).to(U.DT).contiguous()
-    vb = torch.randn(B, H, S, 64, device=DEV).to(U.DT)
-    vt = vb.view(B, H, S // 32, 32, 64).transpose(-1, -2).contiguous()  # (B, H, S/32, 64, 32)
+    if pieces == 1:
+        q = (torch.randn(B * Q, inner, device=DEV) * 0.3).to(U.DT).contiguous()
+        kb = (torch.randn(B, H, S, 64, device=DEV) * 0.3).to(U.DT).contiguous()
+        vb = torch.randn(B, H, S, 64, device=DEV).to(U.DT)
+        vt = vb.view(B, H, S // 32, 32, 64).transpose(-1, -2).contiguous()  # (B, H, S/32, 64, 32)
+        q_ps = bank_ps = 0
+    else:
+        q32, k32 = torch.randn(B * Q, inner, device=DEV) * 0.3, torch.randn(B, H, S, 64, device=DEV) * 0.3
+        v32 = torch.randn(B, H, S, 64, device=DEV)
+        q, kb, vt = U.pieces_of(q32), U.pieces_of(k32), U.pieces_of(U.vt_blocked(v32.transpose(2, 3).contiguous()))  # planar [2][...]
+        q_ps, bank_ps = q[0].numel(), kb[0].numel()
     mask = torch.ones(B, S, dtype=torch.uint8, device=DEV)
     mask[1, 70:] = 0
     mask[2, 10:40] = 0
     rowmap = torch.empty(B * (1 + 2 * _lib.GRAM_MAX_BEAMS), dtype=torch.int32, device=DEV)
-    out = torch.zeros_like(q)
+    out = torch.zeros(B * Q, pieces * inner, dtype=U.DT, device=DEV)  # (two pieces: interleaved)
     _lib.check(U.lib().gram_cross_attn_rows_split(q.data_ptr(), kb.data_ptr(), vt.data_ptr(), mask.data_ptr(), out.data_ptr(), B, Q, H, S,
-                                                  1, 0, 0, None, rowmap.data_ptr(), U.stream()), "gram_cross_attn_rows_split")
+                                                  pieces, q_ps, bank_ps, None, rowmap.data_ptr(), U.stream()), "gram_cross_attn_rows_split")
     torch.cuda.synchronize()
-    s = torch.einsum("bqhd,bhsd->bhqs", q.double().view(B, Q, H, 64), kb.double())
+    if pieces == 1:
+        qd, kd, vd, got = q.double(), kb.double(), vb.double(), out.double()
+    else:
+        qd, kd, vd, got = U.join(q), U.join(kb), U.vt_unblocked(U.join(vt)).transpose(2, 3), U.join_inter(out)
+    s = torch.einsum("bqhd,bhsd->bhqs", qd.view(B, Q, H, 64), kd)
     s = s.masked_fill(mask.bool().logical_not()[:, None, None, :], float("-inf"))
-    ref = torch.einsum("bhqs,bhsd->bqhd", torch.softmax(s, -1), vb.double()).reshape(B * Q, inner)
-    err = float((out.double() - ref).abs().max())
-    print(f"cross rows Q={Q}: vs fp64 {err:.2e}")
-    assert err < 3e-3
+    ref = torch.einsum("bhqs,bhsd->bqhd", torch.softmax(s, -1), vd).reshape(B * Q, inner)
+    err = float((got - ref).abs().max())
+    print(f"cross rows pieces={pieces} Q={Q}: vs fp64 {err:.2e}")
+    assert err < (2e-5 * X if pieces == 2 else 3e-3)
     if Q > 64:  # each group of <= 64 rows against the decode kernel on that group alone: the same bits
         for r0 in range(0, Q, 64):
             kc = min(64, Q - r0)
-            qg = q.view(B, Q, inner)[:, r0:r0 + kc].contiguous().view(B * kc, inner)
-            og = torch.zeros_like(qg)
-            _lib.check(U.lib().gram_cross_attn_decode(qg.data_ptr(), kb.data_ptr(), vt.data_ptr(), mask.data_ptr(), og.data_ptr(), B, kc, H,
-                                                      S, U.stream()), "gram_cross_attn_decode")
+            if pieces == 1:
+                qg = q.view(B, Q, inner)[:, r0:r0 + kc].contiguous().view(B * kc, inner)
+                og = torch.zeros_like(qg)
+                _lib.check(U.lib().gram_cross_attn_decode(qg.data_ptr(), kb.data_ptr(), vt.data_ptr(), mask.data_ptr(), og.data_ptr(), B,
+                                                          kc, H, S, U.stream()), "gram_cross_attn_decode")
+            else:
+                qg = q.view(2, B, Q, inner)[:, :, r0:r0 + kc].contiguous()
+                og = torch.zeros(B * kc, 2 * inner, dtype=U.DT, device=DEV)
+                _lib.check(U.lib().gram_cross_attn_decode_split(qg.data_ptr(), kb.data_ptr(), vt.data_ptr(), mask.data_ptr(),
+                                                                og.data_ptr(), B, kc, H, S, None, None, 2, qg[0].numel(), bank_ps, None,
+                                                                U.stream()), "gram_cross_attn_decode_split")
             torch.cuda.synchronize()
-            assert torch.equal(og.view(B, kc, inner), out.view(B, Q, inner)[:, r0:r0 + kc])
+            assert torch.equal(og.view(B, kc, -1), out.view(B, Q, -1)[:, r0:r0 + kc])
 
 
-@pytest.mark.parametrize("pieces", [1, 2])
-def test_label_logprob_vs_log_softmax_of_gemm_logits(gpu, pieces):
+@pytest.mark.parametrize("pieces,T", [pytest.param(1, 12, id="1"), pytest.param(2, 12, id="2"), (1, 40), (2, 40)])
+def test_label_logprob_vs_log_softmax_of_gemm_logits(gpu, pieces, T):
+    """T = 40: the kernel's second trip of 32 positions, with a sequence whose only label sits in it"""
     torch.manual_seed(pieces)
-    n_seq, T, d, V = 6, 12, 256, 512
+    n_seq, d, V = 6, 256, 512
+    cut = 9 if T == 12 else 37  # labels from position `cut` on are ignored
     R = n_seq * T
     h = torch.randn(R, d, device=DEV)
     E = torch.randn(V, d, device=DEV) * 0.05
@@ -232,8 +255,11 @@ def test_label_logprob_vs_log_softmax_of_gemm_logits(gpu, pieces):
     _lib.check(L.gram_lse_combine(part.data_ptr(), lse.data_ptr(), R, V // 64, U.stream()), "lse combine")
     g = torch.Generator().manual_seed(3)
     lab = torch.randint(0, V, (n_seq, T), generator=g)
-    lab[:, 9:] = -100
+    lab[:, cut:] = -100
     lab[0, :] = -100
+    if T > 32:
+        lab[1, :] = -100
+        lab[1, 34] = 5
     lab = lab.to(DEV, torch.int32).contiguous()
     tok = torch.full((R,), 7.0, device=DEV)
     seq = torch.full((n_seq,), 7.0, device=DEV)
@@ -246,9 +272,11 @@ def test_label_logprob_vs_log_softmax_of_gemm_logits(gpu, pieces):
     ref = torch.where(lf >= 0, ref, torch.zeros((), dtype=ref.dtype, device=DEV))
     err = float((tok.double() - ref).abs().max())
     serr = float((seq.double() - ref.view(n_seq, T).sum(1)).abs().max())
-    print(f"label logprob pieces={pieces}: token {err:.2e}, sequence {serr:.2e}")
+    print(f"label logprob pieces={pieces} T={T}: token {err:.2e}, sequence {serr:.2e}")
     assert err < 1e-3 and serr < 1e-2
-    assert float(seq[0]) == 0.0 and torch.equal(tok.view(n_seq, T)[:, 9:], torch.zeros(n_seq, T - 9, device=DEV))
+    assert float(seq[0]) == 0.0 and torch.equal(tok.view(n_seq, T)[:, cut:], torch.zeros(n_seq, T - cut, device=DEV))
+    if T > 32:
+        assert float(tok[T + 34]) != 0.0 and float(seq[1]) == float(tok[T + 34])
 
 
 # ---------------------------------------------------------------------------------------------------------- 4. teacher forced vs stepped
