@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- users/sec of GRAM's generative scoring path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): Beauty item Trie
@@ -22,6 +22,12 @@ One JSON line is printed by rank 0.  Besides the contract keys it carries
   roofline_cross_attn   the north star's named roofline: the fusion cross-attention kernel
                 against the HBM peak, algorithmic bytes = B*H*S*64*2(K,V)*2 B per launch
   kernel_ms_per_step    device-time breakdown by kernel kind
+A plain run does only what these need: set up, warm up, time the steps, write --dump-outputs, print.
+With --full it also runs, after the timed region, what takes work of its own:
+  output_check  every returned sequence is a member of the Trie
+  roofline_cross_attn.stream_read_gbs_this_box   a streaming read of 4 GiB, this box's HBM rate
+  extras        rank 0 at N = 1: the same batch with every row decoded, B = 1 latency, the other
+                precision modes, the drop-in runner end to end (--no-extras skips them)
   cpu_baseline  the CPU oracle (reference-faithful mode: beam-replicated KV, per-step cache
                 reorder, B = 1 per call like the reference runner) timed on this host's cores on a
                 bounded sample, rank 0 at N = 1 only
@@ -61,7 +67,10 @@ def parse():
     ap.add_argument("--passages", type=int, default=3)
     ap.add_argument("--passage-len", type=int, default=128)
     ap.add_argument("--beams", type=int, default=20)
-    ap.add_argument("--cpu-users", type=int, default=16, help="users in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements and checks: output_check, the streaming-read probe, "
+                         "extras and cpu_baseline (a plain run does only what its headline figure needs)")
+    ap.add_argument("--cpu-users", type=int, default=16, help="--full: users in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--precision", default=DEFAULT_PRECISION, choices=sorted(PIECES),
                     help="operand arithmetic (gram_split_t): f16 = one IEEE-half piece per value (11 significant bits); f16x3 = two pieces, "
                          "3 MFMA products per product (~2^-22, fp32-class); accumulation, residual stream, softmax and scores are fp32 in both")
@@ -72,9 +81,9 @@ def parse():
                          "compaction drops it (96 instead of 108 cross-attention launches per generate).  With peaky attention the beams "
                          "depend on the passages as a trained model's do and the last step keeps the few percent of live rows the Trie implies")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements of the N = 1 run (all-rows decode, B = 1 latency, the other precision modes)")
+                    help="--full: skip the secondary measurements of the N = 1 run (all-rows decode, B = 1 latency, the other precision modes)")
     ap.add_argument("--e2e-users", type=int, default=22363,
-                    help="users of the synthetic dataset directory the drop-in runner scores end to end in `extras` (Beauty has 22 363; 0 = skip)")
+                    help="--full: users of the synthetic dataset directory the drop-in runner scores end to end in `extras` (Beauty has 22 363; 0 = skip)")
     ap.add_argument("--no-prof", action="store_true", help="do not record per-kernel HIP events in the timed region")
     ap.add_argument("--ragged", action="store_true",
                     help="realistic batch: passage counts drawn from the dataset's histogram (padded to --passages), valid "
@@ -217,7 +226,8 @@ def main():
             for name, p_ in model.named_parameters():
                 if name.endswith(".q.weight"):
                     p_.mul_(args.q_sharpen)
-    state = {k: v.detach().clone() for k, v in model.state_dict().items()} if (rank == 0 and args.cpu_users > 0 and world == 1) else None
+    cpu_baseline = args.full and rank == 0 and args.cpu_users > 0 and world == 1
+    state = {k: v.detach().clone() for k, v in model.state_dict().items()} if cpu_baseline else None
     model = model.to(dev).eval()
     model.set_precision(args.precision)
 
@@ -276,12 +286,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # synthetic gold item per user (uniform over the candidates, seeded per rank) -> hit rank in the returned top-K
-    gold_idx = torch.randint(0, len(cands), (B,), generator=g)
-    gold = torch.zeros(B, max_length, dtype=torch.int64)
-    for b, gi in enumerate(gold_idx.tolist()):
-        gold[b, : len(cands[gi])] = torch.tensor(cands[gi])
-    gold_d = gold.to(dev)
+    # N > 1: synthetic gold item per user (uniform over the candidates, seeded per rank) -> hit rank in the returned top-K
+    if distributed:
+        gold_idx = torch.randint(0, len(cands), (B,), generator=g)
+        gold = torch.zeros(B, max_length, dtype=torch.int64)
+        for b, gi in enumerate(gold_idx.tolist()):
+            gold[b, : len(cands[gi])] = torch.tensor(cands[gi])
+        gold_d = gold.to(dev)
 
     def hit_ranks(out):
         seq = out["sequences"]
@@ -386,9 +397,10 @@ def main():
                       "mode on each population (plain, attention-sharpened; 4 096 with ragged masks); profiles/r03*_precision_*.json",
         },
         "exchange": exchange,
-        "output_check": {"sequences_shape": list(out["sequences"].shape),
-                         "all_in_trie": bool(set(map(_strip, out["sequences"].cpu().tolist())) <= {tuple(c) for c in cands})},
     }
+    if args.full:
+        result["output_check"] = {"sequences_shape": list(out["sequences"].shape),
+                                  "all_in_trie": bool(set(map(_strip, out["sequences"].cpu().tolist())) <= {tuple(c) for c in cands})}
     if kernel:
         # decode steps that actually launched the cross-attention (the live-row compaction drops a step whose rows are all dead)
         result["config"]["cross_attn_launches_per_generate"] = kernel["cross_attn"]["launches"] // args.steps
@@ -420,25 +432,25 @@ def main():
                    "avg_launch_us": 1e3 * xa["ms"] / max(xa["launches"], 1),
                    "algorithmic_bytes_per_launch": xa["work"] / max(xa["launches"], 1),
                    "share_of_kernel_time": xa["ms"] / max(sum(v["ms"] for v in kernel.values()), 1e-9)}
-        # calibration: what a plain streaming read reaches on THIS box (4 GiB swept once per launch by every CU)
-        try:
-            from gram_amd import _lib as _L
-            probe = torch.empty(4 << 30, dtype=torch.uint8, device=dev).fill_(1)
-            st_ = torch.cuda.current_stream().cuda_stream
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            _L.check(_L.load().gram_debug_stream_read(probe.data_ptr(), probe.numel(), None, st_), "stream_read")
-            e0.record()
-            for _ in range(3):
-                _L.check(_L.load().gram_debug_stream_read(probe.data_ptr(), probe.numel(), None, st_), "stream_read")
-            e1.record()
-            torch.cuda.synchronize()
-            sweep = 3 * probe.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
-            roof_xa["stream_read_gbs_this_box"] = round(sweep, 1)
-            roof_xa["frac_of_stream_read"] = round(xa_gbs / sweep, 4)
-            del probe
-        except Exception as ex:  # the probe is informational
-            roof_xa["stream_read_gbs_this_box"] = None
-            roof_xa["stream_read_error"] = str(ex)[:100]
+        # --full: calibration, what a plain streaming read reaches on THIS box (4 GiB swept once per launch by every CU)
+        if args.full:
+            try:
+                probe = torch.empty(4 << 30, dtype=torch.uint8, device=dev).fill_(1)
+                st_ = torch.cuda.current_stream().cuda_stream
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                _lib.check(lib.gram_debug_stream_read(probe.data_ptr(), probe.numel(), None, st_), "stream_read")
+                e0.record()
+                for _ in range(3):
+                    _lib.check(lib.gram_debug_stream_read(probe.data_ptr(), probe.numel(), None, st_), "stream_read")
+                e1.record()
+                torch.cuda.synchronize()
+                sweep = 3 * probe.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
+                roof_xa["stream_read_gbs_this_box"] = round(sweep, 1)
+                roof_xa["frac_of_stream_read"] = round(xa_gbs / sweep, 4)
+                del probe
+            except Exception as ex:  # the probe is informational
+                roof_xa["stream_read_gbs_this_box"] = None
+                roof_xa["stream_read_error"] = str(ex)[:100]
         # HBM traffic per launch from the PMC counters (FETCH_SIZE/WRITE_SIZE, separate rocprofv3 passes of this
         # same command, gfx950 correction applied; profiles/*_pmc_traffic.json) -- only for the matching batch size
         try:
@@ -465,7 +477,7 @@ def main():
                                    "cross_attn_bytes_per_user_16bit_kv": xa_bytes_user // PIECES[args.precision],
                                    "frac_16bit_kv_definition": result["value"] / (world * HBM_PEAK_GBS * 1e9 / (xa_bytes_user // PIECES[args.precision]))}
 
-    if rank == 0 and world == 1 and not args.no_extras and not item_cache and not args.ragged:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not item_cache and not args.ragged:
         # secondary measurements, outside the timed region (value / ms_per_step above are the headline)
         def timed(fn_, n):
             torch.cuda.synchronize()
@@ -517,7 +529,7 @@ def main():
                 extras["e2e_runner"] = {"error": f"{type(ex).__name__}: {str(ex)[:200]}"}
         result["extras"] = extras
 
-    if state is not None:
+    if cpu_baseline:
         from oracle import gram_oracle as O
         oc = O.OracleConfig.named(args.backbone)
         ofn = O.prefix_allowed_tokens_fn(O.Trie(cands))

@@ -1,6 +1,7 @@
 """-m gpu: the bench.py contract the driver depends on (one JSON line with the keys of the round prompt), on a small
 configuration so that it runs in seconds: single process, and two ranks over gloo sharing the one GPU of the test box
-(the N > 1 code path: barrier, MAX over ranks, whole-job value)."""
+(the N > 1 code path: barrier, MAX over ranks, whole-job value).  A plain run prints the headline alone; --full adds the
+secondary measurements and checks."""
 import json
 import os
 import subprocess
@@ -39,7 +40,8 @@ def _check(r, n_gpus, steps):
 
 
 def test_bench_contract_single_process(tmp_path):
-    r = _run([sys.executable, "bench.py", *SMALL, "--cpu-users", "1", "--ragged", "--item-pool", "9", "--dump-outputs", str(tmp_path)])
+    r = _run([sys.executable, "bench.py", *SMALL, "--full", "--cpu-users", "1", "--ragged", "--item-pool", "9", "--dump-outputs",
+              str(tmp_path)])
     _check(r, 1, 2)
     # --dump-outputs: the last timed step's sequences and scores, per user
     seqs, scores = np.load(tmp_path / "sequences.npy"), np.load(tmp_path / "sequences_scores.npy")
@@ -54,10 +56,22 @@ def test_bench_contract_single_process(tmp_path):
     assert ic["pool"] == 9 and ic["passages_from_cache_per_step"] > 0 and ic["passages_encoded_per_step"] >= 6
 
 
+def test_bench_plain_run_measures_only_the_headline(tmp_path):
+    """Without --full: the contract keys and the timed region's own per-kernel figures, the dumped outputs, and none of what
+    --full runs after the timed region (output_check, the streaming-read probe, extras, cpu_baseline)."""
+    r = _run([sys.executable, "bench.py", *SMALL, "--dump-outputs", str(tmp_path)])
+    assert CONTRACT <= set(r) and r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["dtype"] == "f16x3"
+    assert abs(r["value"] - 6 * 2 / (r["ms_per_step"] * 2 / 1e3)) < 1e-6 * r["value"]
+    assert not {"output_check", "extras", "cpu_baseline"} & set(r)
+    assert "stream_read_gbs_this_box" not in r["roofline_cross_attn"] and r["kernel_ms_per_step"]["sum"] > 0
+    seqs, scores = np.load(tmp_path / "sequences.npy"), np.load(tmp_path / "sequences_scores.npy")
+    assert seqs.shape[:2] == (6, 5) and scores.shape == (6, 5) and np.all(np.diff(scores, axis=1) <= 0)
+
+
 def test_bench_spawns_its_own_ranks_and_exchanges_hit_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher: the parent starts both ranks before touching the GPU; the timed region ends
     with the hit-rank all-gather + all-reduce cross-check (gloo here: the two ranks share the one test GPU)."""
-    r = _run([sys.executable, "bench.py", "--gpus", "2", *SMALL, "--cpu-users", "0", "--backend", "gloo", "--share-device",
+    r = _run([sys.executable, "bench.py", "--gpus", "2", *SMALL, "--full", "--cpu-users", "0", "--backend", "gloo", "--share-device",
               "--dump-outputs", str(tmp_path)])
     _check(r, 2, 2)
     ex = r["exchange"]
@@ -69,6 +83,7 @@ def test_bench_spawns_its_own_ranks_and_exchanges_hit_ranks(tmp_path):
 
 def test_bench_contract_two_ranks_gloo_one_device():
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-              "--master-port", "29531", "bench.py", "--gpus", "2", *SMALL, "--cpu-users", "0", "--backend", "gloo", "--share-device"])
+              "--master-port", "29531", "bench.py", "--gpus", "2", *SMALL, "--full", "--cpu-users", "0", "--backend", "gloo",
+              "--share-device"])
     _check(r, 2, 2)
     assert "cpu_baseline" not in r  # rank 0 at N = 1 only

@@ -1,4 +1,4 @@
-"""A Beauty-sized SYNTHETIC dataset directory for end-to-end runs of the drop-in runners (bench.py `extras.e2e_runner`,
+"""A Beauty-sized SYNTHETIC dataset directory for end-to-end runs of the drop-in runners (`bench.py --full`: `extras.e2e_runner`,
 tests/test_gpu_runner.py): no tokenizer, dataset or checkpoint exists offline, so the files the reference's data path reads
 (src/utils/indexing.py:132-213, src/data/test_dataset_gram.py:83-218) are generated with the SHAPE of BASELINE.json configs[1]:
 
