@@ -40,22 +40,14 @@
 
 namespace {
 
-#ifndef GRAM_PP_RES_NT
-#define GRAM_PP_RES_NT 0  // A/B build hook: the ping-pong kernel's residual read with the nt hint
-#endif
 // Ablation builds of the ping-pong kernel (`make ABL=n` -> libgram_hip_abl<n>.so, loaded by tests/bench_gemm_x3.py through GRAM_LIB;
 // the product library is built with 0 and contains none of it).  Bits: 1 = no tile-end epilogue (results wrong), 2 = no operand DMA
-// after the prologue, 4 = no LDS fragment reads after the prologue, (8: was the clock stamps, now always on: gram_prof_pp_clock), 16 = the tile-end epilogue without its
-// global stores (fp32: without the stores, the bf16 copy and the partials; the residual loads stay), 32 = the fp32-residual tile-end
-// epilogue without its fp32 store (the 16-bit copy, the partials and the residual load stay).
+// after the prologue, 4 = no LDS fragment reads after the prologue, 16 = the tile-end epilogue without its global stores (fp32:
+// without the stores, the bf16 copy and the partials; the residual loads stay), 32 = the fp32-residual tile-end epilogue without its
+// fp32 store (the 16-bit copy, the partials and the residual load stay).  Bit 8 is unused (it once switched the clock stamps, which
+// gram_prof_pp_clock_enable now does at run time).
 #ifndef GRAM_PP_ABL
 #define GRAM_PP_ABL 0
-#endif
-#ifndef GRAM_PP_PASS_PRIO
-#define GRAM_PP_PASS_PRIO 2  // A/B build hook: wave priority of the in-load-slot epilogue's passes (the MFMA slots run at 1)
-#endif
-#ifndef GRAM_PP_INSL
-#define GRAM_PP_INSL 0  // A/B build hook: 1 = two-piece 16-bit outputs from inside the pipeline (measured: no gain, profiles/r03h, r03i)
 #endif
 // In-kernel clock of the ping-pong GEMM (MI355X_MICROARCH.md, DVFS item 6) -- a DIAGNOSTIC, off unless gram_prof_pp_clock_enable(1)
 // (bench.py switches it on for its timed region): every workgroup then stamps s_memtime (shader cycles) and s_memrealtime (100-MHz
@@ -131,12 +123,16 @@ __device__ __forceinline__ void store8(void* p, uint2 v, bool nt) {
   else *reinterpret_cast<uint2*>(p) = v;
 }
 
-// XCD-aware bijective remap of the 1-D workgroup id -> (m-tile, n-tile), n fastest.
-__device__ __forceinline__ void tile_of_block(int ntn, int& mt, int& nt) {
+// XCD-aware bijective remap of the 1-D workgroup id (ids i and i+8 share an XCD): XCD x gets a contiguous range of the new ids
+__device__ __forceinline__ int xcd_remap() {
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int xcd = bid & 7, local = bid >> 3;
   const int q = nwg >> 3, r = nwg & 7;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+}
+// ... -> (m-tile, n-tile), n fastest.
+__device__ __forceinline__ void tile_of_block(int ntn, int& mt, int& nt) {
+  const int id = xcd_remap();
   mt = id / ntn;
   nt = id - mt * ntn;
 }
@@ -1000,8 +996,7 @@ __device__ __forceinline__ void pp_barrier() {
 }
 
 // Store the wave's output rows of m-tiles j0, j0+1 (32 rows x 64 columns) through its LDS patch as whole
-// 128-B (bf16) / 256-B (fp32) row segments, 16 rows per pass.  Runs inside a LOAD slot of the ping-pong
-// kernel.  All global addresses are a wave-uniform base (this wave's first row / first column of the tile, so it
+// 128-B row segments of a 16-bit output, 16 rows per pass (fp32 outputs: pp_store_tile_f32).  All global addresses are a wave-uniform base (this wave's first row / first column of the tile, so it
 // lives in SGPRs) + a 32-bit per-lane offset.  rows = number of valid rows from the wave's first row on.
 // rs: this wave group's 128 row scales in LDS (folded T5LayerNorm), or nullptr.
 struct PPOut {
@@ -1018,11 +1013,12 @@ struct PPOut {
   bool inter;           // bf16 C interleaved (c = C + (m_first * ldc + 2 * n_first) * 2, ldc_b the physical row stride); xb always is when split == 2
   bool nt;              // streaming (nt) stores for the bf16 rows (A/B hook GRAM_GEMM_NT7)
   float scale;          // EpiArgs.out_scale
-  long q_ps;            // in-load-slot epilogue: bytes from piece 0 to piece 1 of a quadrant's row segment (interleaved C: 64)
-  uint32_t q_step;      // ... and from the n0 quadrants' segment to the n1 quadrants' (interleaved C: 128, planar: 64)
+  long q_ps;            // (unused)
+  uint32_t q_step;      // (unused)
 };
 template <int EPI, bool FULL>
 __device__ __forceinline__ void pp_store_rows_impl(f32x4 (&acc)[4][8], int j0, char* patch, const PPOut& o, int lane_, const float* rs) {
+  static_assert(EPI == GRAM_EPI_BF16 || EPI == GRAM_EPI_BF16_RELU, "16-bit outputs only: the fp32 outputs go through pp_store_tile_f32");
   // opaque copy of the lane id: keeps hipcc from hoisting every store address of the tile out of the k-loop
   // (loop-invariant, 2 VGPRs each) and spilling them -- a scratch reload inside a load slot is a vmcnt(0) drain
   int lane = lane_;
@@ -1031,79 +1027,41 @@ __device__ __forceinline__ void pp_store_rows_impl(f32x4 (&acc)[4][8], int j0, c
 #pragma unroll
   for (int jj = 0; jj < 2; ++jj) {
     const int j = j0 + jj;
-    if constexpr (EPI == GRAM_EPI_BF16 || EPI == GRAM_EPI_BF16_RELU) {
-      // 16 rows x 64 cols bf16: patch[16][128 B], chunk c (16 B) at c ^ (row & 7); one pass per bf16 piece of the output
-      const float sc = (rs ? rs[j * 16 + r16] : 1.f) * o.scale;
-      f32x4 v[4];
+    // 16 rows x 64 cols bf16: patch[16][128 B], chunk c (16 B) at c ^ (row & 7); one pass per bf16 piece of the output
+    const float sc = (rs ? rs[j * 16 + r16] : 1.f) * o.scale;
+    f32x4 v[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        v[i] = acc[i][j] * sc;
-        if constexpr (EPI == GRAM_EPI_BF16_RELU) {
+    for (int i = 0; i < 4; ++i) {
+      v[i] = acc[i][j] * sc;
+      if constexpr (EPI == GRAM_EPI_BF16_RELU) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[i][e] = fmaxf(v[i][e], 0.f);
-        }
+        for (int e = 0; e < 4; ++e) v[i][e] = fmaxf(v[i][e], 0.f);
       }
-      uint2 pcs[2][4];  // the values' pieces (both at once in the two-piece mode: split2x4)
-      if (o.split == 2) {
+    }
+    uint2 pcs[2][4];  // the values' pieces (both at once in the two-piece mode: split2x4)
+    if (o.split == 2) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) split2x4(v[i], pcs[0][i], pcs[1][i]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pcs[0][i] = pcs[1][i] = pack_bf16x4(v[i]);
-      }
-      for (int pc = 0; pc < o.split; ++pc) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int chunk = (i * 2 + (g >> 1)) ^ (r16 & 7);
-          *reinterpret_cast<uint2*>(patch + r16 * 128 + chunk * 16 + (g & 1) * 8) = pc == 0 ? pcs[0][i] : pcs[1][i];
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-          const int row = it * 8 + (lane >> 3), c = lane & 7;
-          const uint4 val = *reinterpret_cast<const uint4*>(patch + row * 128 + ((c ^ (row & 7)) * 16));
-          const int mr = j * 16 + row;
-          // planar: the piece's 128-B row segment; interleaved: its two 64-B halves, side by side with the other piece's
-          const uint32_t coff = o.inter ? (uint32_t)((c >> 2) * 128 + pc * 64 + (c & 3) * 16) : (uint32_t)(c * 16);
-          if ((FULL || mr < o.rows) && (!(GRAM_PP_ABL & 16) || o.rows < -12345))  // (ablation bit 16: everything but the global stores)
-            store16(o.c + (o.inter ? 0 : pc * o.c_ps_b) + ((uint32_t)mr * o.ldc_b + coff), val, o.nt);
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
+      for (int i = 0; i < 4; ++i) split2x4(v[i], pcs[0][i], pcs[1][i]);
     } else {
-      // 16 rows x 64 cols fp32: patch[16][256 B], chunk c (16 B) at c ^ row
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pcs[0][i] = pcs[1][i] = pack_bf16x4(v[i]);
+    }
+    for (int pc = 0; pc < o.split; ++pc) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int chunk = (i * 4 + g) ^ r16;
-        *reinterpret_cast<f32x4*>(patch + r16 * 256 + chunk * 16) = acc[i][j];
+        const int chunk = (i * 2 + (g >> 1)) ^ (r16 & 7);
+        *reinterpret_cast<uint2*>(patch + r16 * 128 + chunk * 16 + (g & 1) * 8) = pc == 0 ? pcs[0][i] : pcs[1][i];
       }
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int row = it * 4 + (lane >> 4), c = lane & 15;
-        f32x4 val = *reinterpret_cast<const f32x4*>(patch + row * 256 + ((c ^ row) * 16)) * o.scale;
+      for (int it = 0; it < 2; ++it) {
+        const int row = it * 8 + (lane >> 3), c = lane & 7;
+        const uint4 val = *reinterpret_cast<const uint4*>(patch + row * 128 + ((c ^ (row & 7)) * 16));
         const int mr = j * 16 + row;
-        float ssq = 0.f;
-        if (FULL || mr < o.rows) {
-          f32x4* pc = reinterpret_cast<f32x4*>(o.c + ((uint32_t)mr * o.ldc_b + c * 16));
-          if constexpr (EPI == GRAM_EPI_F32_ADD) val += *pc;
-          *pc = val;
-          if constexpr (EPI == GRAM_EPI_F32_ADD) {
-            if (o.xb) {
-              *reinterpret_cast<uint2*>(o.xb + ((uint32_t)mr * o.ldx_b + c * 8)) = pack_bf16x4(o.xs ? val * o.xs[mr] : val);
-              ssq = sumsq4(val);
-            }
-          }
-        }
-        if constexpr (EPI == GRAM_EPI_F32_ADD) {
-          if (o.ss) {  // the 16 lanes of a row cover exactly one 64-column block
-            ssq += __shfl_xor(ssq, 1, 64);
-            ssq += __shfl_xor(ssq, 2, 64);
-            ssq += __shfl_xor(ssq, 4, 64);
-            ssq += __shfl_xor(ssq, 8, 64);
-            if (c == 0 && (FULL || mr < o.rows)) o.ss[(uint32_t)mr * o.ss_nblk] = ssq;
-          }
-        }
+        // planar: the piece's 128-B row segment; interleaved: its two 64-B halves, side by side with the other piece's
+        const uint32_t coff = o.inter ? (uint32_t)((c >> 2) * 128 + pc * 64 + (c & 3) * 16) : (uint32_t)(c * 16);
+        if ((FULL || mr < o.rows) && (!(GRAM_PP_ABL & 16) || o.rows < -12345))  // (ablation bit 16: everything but the global stores)
+          store16(o.c + (o.inter ? 0 : pc * o.c_ps_b) + ((uint32_t)mr * o.ldc_b + coff), val, o.nt);
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -1132,11 +1090,7 @@ __device__ __forceinline__ void pp_store_tile_f32(f32x4 (&acc)[4][8], char* patc
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int mr = min(half * 64 + q * 4 + (lane >> 4), o.rows - 1);  // rows past M inside the block: clamped, never stored
-#if GRAM_PP_RES_NT
-          res[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(o.c + ((uint32_t)mr * o.ldc_b + (lane & 15) * 16)));
-#else
           res[q] = *reinterpret_cast<const f32x4*>(o.c + ((uint32_t)mr * o.ldc_b + (lane & 15) * 16));
-#endif
         }
       }
     }
@@ -1232,12 +1186,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
   // loads out of the DMA queue's way) and every X3 output (two pieces per value: a store count the in-slot jobs' counted waits do
   // not cover; with 1.5x the MFMAs per k-tile the tile-end placement costs less than it does in the plain kernel, where in-slot
   // bf16 stores measured 1 105 vs 1 035 TFLOP/s on the encoder QKV shape)
-  // INSL: the two-piece 16-bit outputs (QKV, FFN-in) leave from INSIDE the pipeline, in the LOAD slots around the tile boundary -- see
-  // "in-load-slot epilogue" below.  (GRAM_PP_INSL=0: A/B build with the tile-end epilogue.)
-  constexpr bool INSL = GRAM_PP_INSL && X3 && (EPI == GRAM_EPI_BF16 || EPI == GRAM_EPI_BF16_RELU);
-  constexpr bool TEND = (EPI == GRAM_EPI_F32 || EPI == GRAM_EPI_F32_ADD) || LSE || (X3 && !INSL);
-  constexpr int PATCHB = INSL ? 6144 : 4096;   // bytes of a patch shared by waves w and w + 4 (INSL: three 2-KiB passes in flight)
-  constexpr int RS_OFF = 8 * HT + 4 * PATCHB;  // bf16 epilogues: 2 x 1 KiB of row scales behind the patches
+  constexpr bool TEND = F32OUT || LSE || X3;
+  constexpr int RS_OFF = 8 * HT + 4 * PATCH;  // bf16 epilogues: 2 x 1 KiB of row scales behind the patches
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 8 half-tile buffers + epilogue patches (+ row scales)
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1253,20 +1203,17 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
       return ntl;
     }
   };
-  const int G = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, local = bid >> 3, q = G >> 3, rr = G & 7;
-  const int slot = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + local;
+  const int G = gridDim.x;
+  const int slot = xcd_remap();
+  const int xcd = blockIdx.x & 7;  // (the start stagger below de-phases by XCD)
   if (slot >= ntiles) return;
   const int nkt = K / BK;  // even, >= 4 (checked by the launcher)
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const uint32_t wave_lds = __builtin_amdgcn_readfirstlane(lds0 + wave * 2048);  // this wave's 2 pieces (16 rows) of a half-tile
   const char* const Ab = reinterpret_cast<const char*>(A);
   const char* const Wb = reinterpret_cast<const char*>(W);
-  char* const patch = smem + 8 * HT + (F32OUT ? wave * PATCH : TEND ? wave * 2048 : (wave & 3) * PATCHB);
+  char* const patch = smem + 8 * HT + (F32OUT ? wave * PATCH : TEND ? wave * 2048 : (wave & 3) * PATCH);
   const bool has_rs = !F32OUT && ep.ss_in != nullptr;  // ss_nblk == 0 (1/rms per row), checked by the launcher
-  if constexpr (INSL) {  // its passes always multiply by a row scale from the RS area: all ones for a GEMM without (published by the prologue's barrier)
-    if (!has_rs) reinterpret_cast<float*>(smem + RS_OFF)[tid] = 1.f;
-  }
 
   // tile index -> (m-tile, n-tile column).  gm <= 1: n fastest.  gm > 1: groups of gm m-tiles, m fastest inside a group, so
   // that the 32 tiles an XCD works on at a time cover gm m-tiles x 32/gm n-tiles (fewer distinct A + W panels per round).
@@ -1601,131 +1548,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
     __builtin_amdgcn_sched_barrier(0);
     pp_barrier();
   };
-  // ---- in-load-slot epilogue (INSL).  The tile-end epilogue of a two-piece 16-bit output costs 13-14 % of these GEMMs (both wave
-  // groups stop, 32 KiB per wave through a 2-KiB patch, then 256 KiB per CU through a vector-store path that moves ~32 B/clk; nothing of
-  // it overlaps an MFMA: profiles/r03d, r03f).  Here a quadrant's results leave in "passes" -- one m-tile (16 rows) x the quadrant's 32
-  // columns x both pieces: scale / ReLU / split, 4 ds_write_b64 into a 2-KiB patch laid out [16 rows][piece 0: 64 B | piece 1: 64 B]
-  // (for an interleaved output that IS the row's 128 B), 2 ds_read_b128, 2 row-contiguous 1-KiB stores -- placed in the LOAD slots
-  // between the quadrant's last MFMA slot of this tile and its first of the next one, where the wave otherwise waits for its SIMD
-  // partner's MFMA slot.  With the quadrant order of the last (odd) k-tile 01 00 10 11 and of the next tile's first (even) 00 01 11 10:
-  //   load slot before   | O:00   | O:10    | O:11        || E:00        | E:01        | E:11    | E:10
-  //   passes (quadrant.j)| 01.0 1 | 01.2 00.0| 01.3 00.1 2 || 00.3 11.0 10.0| 11.1 2 10.1 | 11.3 10.2| 10.3
-  // A quadrant is zeroed behind its last pass.  The patch is the 4 KiB waves w and w + 4 share (they are never in a load slot at the
-  // same time).  Stores count in vmcnt with the DMAs, in issue order: the counted wait of a load slot adds the stores of the last six
-  // load slots (exact for a wave whose 128 rows all exist; a partial wave counts none, which only makes its waits stricter).
-  // Extra stores in flight at the end of each load slot (sum over the last six load slots, the slot's own included), by position:
-  //   pairs of MODE 1 (first pair behind a tile of a full wave):  even k-tile 20 26 30 26, odd k-tile 22 16 10 4
-  //     (previous pair's last three slots 4 + 4 + 6, then 6 6 4 0: the single pass of the fourth slot is left out of the count)
-  //   pairs of MODE 2 (last pair of a tile of a full wave):       odd k-tile 0 4 8 14
-  auto end_load_slot_st = [&](bool full, auto Nc) {  // N = that sum for a full wave (a partial wave counts none of its stores)
-    constexpr int N = decltype(Nc)::value;
-    static_assert(N >= 0 && 12 + N <= 63, "vmcnt is a 6-bit count");
-    if constexpr ((GRAM_PP_ABL & 1) != 0) full = false;
-    if (full) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(12 + N) : "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    pp_barrier();
-  };
-  // up to three passes as ONE straight-line group (no branch between them: a basic-block boundary makes hipcc drain lgkmcnt): all splits
-  // and patch writes, then all patch reads, then the stores as their data arrives.  P = mq * 8 + nq * 4 + j-in-quadrant, -1 = none;
-  // pass u uses the 2 KiB at pt + 2048 u.  rs always points at row scales (all 1.0 when the GEMM has none: see the RS area's fill).
-  auto passes = [&](const PPOut& o, const float* rs, char* pt, auto P0c, auto P1c, auto P2c) {
-    using U0 = std::integral_constant<int, 0>;
-    using U1 = std::integral_constant<int, 1>;
-    using U2 = std::integral_constant<int, 2>;
-    if constexpr ((GRAM_PP_ABL & 1) != 0) {  // ablation: keep the accumulators live, store (almost) never
-      auto keep = [&](auto Pc) {
-        constexpr int P = decltype(Pc)::value;
-        if constexpr (P >= 0) {
-          constexpr int nq = (P >> 2) & 1, j = (P >> 3) * 4 + (P & 3);
-          const f32x4 t4 = acc[nq * 2][j] + acc[nq * 2 + 1][j];
-          const float t = (t4[0] + t4[1]) + (t4[2] + t4[3]);
-          if (t == 12345.678f) reinterpret_cast<float*>(ep.C)[lane] = t;
-        }
-      };
-      keep(P0c);
-      keep(P1c);
-      keep(P2c);
-      return;
-    }
-    // The SIMD partner is in its MFMA slot at priority 1: at priority 0 this wave's ~45 vector instructions per pass would only issue
-    // once the partner has run out of MFMAs (MI355X_MICROARCH.md, "Two waves per SIMD", item 2), i.e. behind the slot instead of beside it
-    __builtin_amdgcn_s_setprio(GRAM_PP_PASS_PRIO);
-    int ln = lane;
-    asm volatile("" : "+v"(ln));  // opaque: the lane constants are recomputed here, not kept live (or spilled) across the k-loop
-    const int lr = ln & 15, lg = ln >> 4;
-    // patch row lr: logical 16-B chunk piece * 4 + n-tile * 2 + (lg >> 1) at chunk ^ (lr & 7), 8-B half lg & 1
-    char* const wb = pt + lr * 128 + (lg & 1) * 8;
-    const int sw = lr & 7, gh = lg >> 1;
-    auto split_write = [&](auto Uc, auto Pc) {
-      constexpr int u = decltype(Uc)::value, P = decltype(Pc)::value;
-      if constexpr (P >= 0) {
-        constexpr int nq = (P >> 2) & 1, j = (P >> 3) * 4 + (P & 3);
-        const float sc = rs[j * 16 + lr] * o.scale;
-        f32x4 v0 = acc[nq * 2][j] * sc, v1 = acc[nq * 2 + 1][j] * sc;
-        // (the ROUNDED products are what is split into pieces, as in every other kernel: keep hipcc from contracting acc * sc - hi into an fma)
-        asm volatile("" : "+v"(v0), "+v"(v1));
-        if constexpr (EPI == GRAM_EPI_BF16_RELU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v0[e] = fmaxf(v0[e], 0.f);
-            v1[e] = fmaxf(v1[e], 0.f);
-          }
-        }
-        uint2 h0, h1, l0, l1;
-        split2x4(v0, h0, l0);
-        split2x4(v1, h1, l1);
-        *reinterpret_cast<uint2*>(wb + u * 2048 + (((0 + gh) ^ sw) << 4)) = h0;
-        *reinterpret_cast<uint2*>(wb + u * 2048 + (((2 + gh) ^ sw) << 4)) = h1;
-        *reinterpret_cast<uint2*>(wb + u * 2048 + (((4 + gh) ^ sw) << 4)) = l0;
-        *reinterpret_cast<uint2*>(wb + u * 2048 + (((6 + gh) ^ sw) << 4)) = l1;
-      }
-    };
-    split_write(U0{}, P0c);
-    split_write(U1{}, P1c);
-    split_write(U2{}, P2c);
-    __builtin_amdgcn_wave_barrier();
-    const int row = ln >> 3, c = ln & 7;
-    const char* const gb = pt + row * 128 + ((c ^ (row & 7)) << 4);
-    uint4 val[3][2];
-    auto read_back = [&](auto Uc, auto Pc) {
-      constexpr int u = decltype(Uc)::value;
-      if constexpr (decltype(Pc)::value >= 0) {
-        val[u][0] = *reinterpret_cast<const uint4*>(gb + u * 2048);
-        val[u][1] = *reinterpret_cast<const uint4*>(gb + u * 2048 + 1024);
-      }
-    };
-    read_back(U0{}, P0c);
-    read_back(U1{}, P1c);
-    read_back(U2{}, P2c);
-    // a quadrant's 32 columns of a row: chunks 0..3 = piece 0 (64 B), 4..7 = piece 1, `o.q_ps` bytes further (interleaved C: 64, i.e. the
-    // row's 128 contiguous bytes; planar C: the piece stride); the n1 quadrants `o.q_step` bytes further (128 / 64)
-    char* const cb = o.c + ((c & 3) * 16 + (c >> 2) * o.q_ps);
-    auto store_rows = [&](auto Uc, auto Pc) {
-      constexpr int u = decltype(Uc)::value, P = decltype(Pc)::value;
-      if constexpr (P >= 0) {
-        constexpr int nq = (P >> 2) & 1, j = (P >> 3) * 4 + (P & 3);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-          const int mr = j * 16 + it * 8 + row;
-          if (mr < o.rows && (!(GRAM_PP_ABL & 16) || o.rows < -12345))  // (ablation bit 16: everything but the global stores)
-            *reinterpret_cast<uint4*>(cb + ((uint32_t)mr * o.ldc_b + (uint32_t)nq * o.q_step)) = val[u][it];
-        }
-      }
-    };
-    store_rows(U0{}, P0c);
-    store_rows(U1{}, P1c);
-    store_rows(U2{}, P2c);
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto zero_q = [&](int mq, int nq) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[nq * 2 + i][mq * 4 + j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  };
   auto zero_half = [&](int mq) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -1833,155 +1655,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
   // form is correct but 0.4-0.5 % slower in the bench (two more SGPR spills and a scratch reload behind a vmcnt(0) in the entry block:
   // profiles/r04x_stamp_reads_ab.txt), so the two scalar reads stay unconditional.)
   const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-  if constexpr (INSL) {
-    const float *rs_cur = nullptr, *rs_prev = nullptr;
-    auto set_tile = [&]() {
-      int mt, nr;
-      decode(tile, mt, nr);
-      m0 = mt * TB;
-      n0 = nt_of(nr) * TB;
-      rs_cur = reinterpret_cast<const float*>(smem + RS_OFF) + tpar * 256 + wr * 128;  // (all 1.0 when the GEMM has no row scales)
-      rs_prev = reinterpret_cast<const float*>(smem + RS_OFF) + (tpar ^ 1) * 256 + wr * 128;
-    };
-    // two-piece 16-bit outputs: the passes of the in-load-slot epilogue (schedule above) around the same eight phases.  The k-tile
-    // pairs of a tile come in three compile-time flavours -- the first one behind a previous tile (MODE 1: that tile's last passes),
-    // plain ones (MODE 0: exactly the loop of the other kernels, no epilogue code or branches in it), the last one (MODE 2: this
-    // tile's first passes) -- so the steady state is not touched.  nkt >= 4: the first and the last pair are different pairs.
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    const std::false_type NT{};
-    char* const PT = patch;
-    auto pair_body = [&](auto MODEc, bool first) {
-      constexpr int MODE = decltype(MODEc)::value;
-      // exact store counts: all 128 rows of the wave exist in the tile being stored (its output addressing is rebuilt in every slot
-      // that stores -- a handful of scalar operations -- rather than kept live across the pair)
-      const bool full = MODE == 1 ? M - (pm0 + wr * 128) >= 128 : MODE == 2 ? M - (m0 + wr * 128) >= 128 : false;
-      // ================= even k-tile (buffers 0): quadrants 00, 01, 11, 10
-      if constexpr (MODE == 1) {
-        issue(1, 0);  // W_n0(kk+2)
-        const PPOut o = make_out(pm0, pn0);
-        passes(o, rs_prev, PT, std::integral_constant<int, 3>{}, std::integral_constant<int, 12>{}, std::integral_constant<int, 8>{});
-        zero_q(0, 0);
-        read_a(0, 0);
-        end_load_slot_st(full, std::integral_constant<int, 20>{});
-      } else {
-        read_a(0, 0);
-        issue(1, 0);
-        end_load_slot(0);
-      }
-      mma(0, 0, NT);
-      if constexpr (MODE == 1) {
-        issue(0, 0);  // A_m0(kk+2)
-        const PPOut o = make_out(pm0, pn0);
-        passes(o, rs_prev, PT, std::integral_constant<int, 13>{}, std::integral_constant<int, 14>{}, std::integral_constant<int, 9>{});
-        read_w(0, 1);
-        end_load_slot_st(full, std::integral_constant<int, 26>{});
-      } else {
-        read_w(0, 1);
-        issue(0, 0);
-        end_load_slot(0);
-      }
-      mma(0, 1, NT);
-      if (first && has_rs && wave < 4) {  // this tile's 256 row scales -> LDS by DMA (64 rows per wave); first read in the tile's last pair
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        dma4_asm(lds0 + RS_OFF + tpar * 1024 + wave * 256, (uint32_t)min(m0 + wave * 64 + ln, M - 1) * 4u,
-                 reinterpret_cast<const char*>(ep.ss_in));
-      }
-      if constexpr (MODE == 1) {
-        issue(2, 0);  // W_n1(kk+2)
-        const PPOut o = make_out(pm0, pn0);
-        passes(o, rs_prev, PT, std::integral_constant<int, 15>{}, std::integral_constant<int, 10>{}, std::integral_constant<int, -1>{});
-        zero_q(1, 1);
-        read_a(0, 1);
-        end_load_slot_st(full, std::integral_constant<int, 30>{});
-      } else {
-        read_a(0, 1);
-        issue(2, 0);
-        end_load_slot(0);
-      }
-      mma(1, 1, NT);
-      if constexpr (MODE == 1) {
-        issue(3, 0);  // A_m1(kk+2)
-        const PPOut o = make_out(pm0, pn0);
-        passes(o, rs_prev, PT, std::integral_constant<int, 11>{}, std::integral_constant<int, -1>{}, std::integral_constant<int, -1>{});
-        zero_q(1, 0);
-        read_w(1, 1);  // W_n1 of the odd k-tile that follows
-        end_load_slot_st(full, std::integral_constant<int, 26>{});
-      } else {
-        read_w(1, 1);
-        issue(3, 0);
-        end_load_slot(0);
-      }
-      mma(1, 0, NT);
-      advance();
-      // ================= odd k-tile (buffers 1): quadrants 01, 00, 10, 11
-      read_a(1, 0);
-      issue(2, 1);  // W_n1(kk+3)
-      if constexpr (MODE == 1) end_load_slot_st(full, std::integral_constant<int, 22>{});
-      else end_load_slot(0);
-      mma(0, 1, NT);
-      if constexpr (MODE == 2) {  // this tile's quadrant 01 is final
-        issue(0, 1);  // A_m0(kk+3)
-        const PPOut o = make_out(m0, n0);
-        passes(o, rs_cur, PT, std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{}, std::integral_constant<int, -1>{});
-        read_w(1, 0);
-        end_load_slot_st(full, std::integral_constant<int, 4>{});
-      } else {
-        read_w(1, 0);
-        issue(0, 1);
-        if constexpr (MODE == 1) end_load_slot_st(full, std::integral_constant<int, 16>{});
-        else end_load_slot(0);
-      }
-      mma(0, 0, NT);
-      if constexpr (MODE == 2) {  // ... and 00
-        issue(1, 1);  // W_n0(kk+3)
-        const PPOut o = make_out(m0, n0);
-        passes(o, rs_cur, PT, std::integral_constant<int, 6>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, -1>{});
-        read_a(1, 1);
-        end_load_slot_st(full, std::integral_constant<int, 8>{});
-      } else {
-        read_a(1, 1);
-        issue(1, 1);
-        if constexpr (MODE == 1) end_load_slot_st(full, std::integral_constant<int, 10>{});
-        else end_load_slot(0);
-      }
-      mma(1, 0, NT);
-      if constexpr (MODE == 2) {
-        issue(3, 1);  // A_m1(kk+3)
-        const PPOut o = make_out(m0, n0);
-        passes(o, rs_cur, PT, std::integral_constant<int, 7>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
-        zero_q(0, 1);
-        read_w(0, 0);  // W_n0 of the even k-tile that follows
-        end_load_slot_st(full, std::integral_constant<int, 14>{});
-      } else {
-        read_w(0, 0);
-        issue(3, 1);
-        if constexpr (MODE == 1) end_load_slot_st(full, std::integral_constant<int, 4>{});
-        else end_load_slot(0);
-      }
-      mma(1, 1, NT);
-      advance();
-    };
-    // The tile loop is rotated -- [plain pairs | last pair | next tile's first pair] -- so that no two flavours of a pair meet at a
-    // join (a join of two 190-register states makes hipcc copy and spill them).
-    set_tile();
-    pair_body(I0{}, true);
-    while (true) {
-      for (int kt = 2; kt + 2 < nkt; kt += 2) pair_body(I0{}, false);
-      pair_body(I2{}, false);
-      const bool more = tile + G < ntiles;
-      pending = true;
-      pm0 = m0;
-      pn0 = n0;
-      tpar ^= 1;
-      if (!more) break;
-      tile += G;
-      set_tile();
-      pair_body(I1{}, true);
-    }
-  } else {
   while (true) {
     {
       int mt, nr;
@@ -1992,7 +1665,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
     }
     const float* rs_cur = has_rs ? reinterpret_cast<const float*>(smem + RS_OFF) + tpar * 256 + wr * 128 : nullptr;
     const float* rs_prev = has_rs ? reinterpret_cast<const float*>(smem + RS_OFF) + (tpar ^ 1) * 256 + wr * 128 : nullptr;
-    {
     for (int kt = 0; kt < nkt; kt += 2) {
       const bool first = kt == 0, last = kt + 2 >= nkt;
       // bf16 epilogues of FULL tiles issue exactly 4 stores per store slot (the slots p2, p3 of a tile's last k-tile
@@ -2049,7 +1721,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
       run_slot(1, 1, !TEND && st_cur, std::integral_constant<int, 2>{}, m0, n0, rs_cur);
       if (last && !TEND) zero_half(0);
       advance();
-    }
     }
     const bool more = tile + G < ntiles;
     if constexpr (TEND) {
@@ -2147,15 +1818,15 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
           }
         }
       } else {
-      const PPOut o = make_out(m0, n0);
-      if constexpr (F32OUT) {
-        pp_store_tile_f32<EPI>(acc, patch, o, lane);
-      } else {
-        pp_store_rows<EPI>(acc, 0, patch, o, lane, rs_cur);
-        pp_store_rows<EPI>(acc, 2, patch, o, lane, rs_cur);
-        pp_store_rows<EPI>(acc, 4, patch, o, lane, rs_cur);
-        pp_store_rows<EPI>(acc, 6, patch, o, lane, rs_cur);
-      }
+        const PPOut o = make_out(m0, n0);
+        if constexpr (F32OUT) {
+          pp_store_tile_f32<EPI>(acc, patch, o, lane);
+        } else {
+          pp_store_rows<EPI>(acc, 0, patch, o, lane, rs_cur);
+          pp_store_rows<EPI>(acc, 2, patch, o, lane, rs_cur);
+          pp_store_rows<EPI>(acc, 4, patch, o, lane, rs_cur);
+          pp_store_rows<EPI>(acc, 6, patch, o, lane, rs_cur);
+        }
       }
       zero_half(0);
       zero_half(1);
@@ -2169,7 +1840,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
     if (!more) break;
     tile += G;
   }
-  }
   if (clk_on && tid == 0) {
     atomicAdd(&g_pp_clk[0], (unsigned long long)__builtin_amdgcn_s_memtime() - clk_t0);
     atomicAdd(&g_pp_clk[1], (unsigned long long)__builtin_amdgcn_s_memrealtime() - clk_r0);
@@ -2181,14 +1851,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   pp_barrier();
-  if constexpr (INSL) {  // what the in-load-slot epilogue of a next tile would have stored: 00's last m-tile, quadrants 11 and 10
-    const float* rs_prev = reinterpret_cast<const float*>(smem + RS_OFF) + (tpar ^ 1) * 256 + wr * 128;
-    const PPOut o = make_out(pm0, pn0);
-    char* const PT = smem + wave * 6144;  // (the half-tile buffers are dead: private patches)
-    passes(o, rs_prev, PT, std::integral_constant<int, 3>{}, std::integral_constant<int, 12>{}, std::integral_constant<int, 13>{});
-    passes(o, rs_prev, PT, std::integral_constant<int, 14>{}, std::integral_constant<int, 15>{}, std::integral_constant<int, 8>{});
-    passes(o, rs_prev, PT, std::integral_constant<int, 9>{}, std::integral_constant<int, 10>{}, std::integral_constant<int, 11>{});
-  } else if constexpr (!TEND) {  // (TEND: stored at the end of every tile)
+  if constexpr (!TEND) {  // (TEND: stored at the end of every tile)
     const float* rs_prev = has_rs ? reinterpret_cast<const float*>(smem + RS_OFF) + (tpar ^ 1) * 256 + wr * 128 : nullptr;
     if constexpr (KV) {
 #pragma unroll
@@ -2321,6 +1984,19 @@ int launch_dma(const void* A, const void* W, int M, int N, int K, int lda, EpiAr
 
 constexpr int V_SKINNY = 30, V_STREAM = 32;
 
+// the 128-row-tile kernels: variant id (pick_variant) -> instantiation
+template <int EPI, bool X3>
+int launch_dma_variant(int v, const void* A, const void* W, int M, int N, int K, int lda, const EpiArgs& ep, hipStream_t st) {
+  switch (v) {
+    case V_DMA_M64: return launch_dma<EPI, 1, 1, X3>(A, W, M, N, K, lda, ep, st);
+    case V_RING_M64: return launch_dma<EPI, 1, 6, X3>(A, W, M, N, K, lda, ep, st);
+    case V_RING_M128: return launch_dma<EPI, 2, 4, X3>(A, W, M, N, K, lda, ep, st);
+    case V_PP:  // (a shape the ping-pong kernel declined)
+    case V_DMA_M256: return launch_dma<EPI, 4, 1, X3>(A, W, M, N, K, lda, ep, st);
+    default: return launch_dma<EPI, 2, 1, X3>(A, W, M, N, K, lda, ep, st);  // V_DMA: 128 x 128 tiles
+  }
+}
+
 template <int EPI, bool X3>
 int launch(const void* A, const void* W, int M, int N, int K, int lda, EpiArgs ep, hipStream_t st) {
   gram_prof::Scope prof(GRAM_K_GEMM, st, (X3 ? 3.0 : 2.0) * M * N * K);  // EXECUTED MFMA flops: K = physical columns; X3: 3 products per 2 of them
@@ -2347,32 +2023,20 @@ int launch(const void* A, const void* W, int M, int N, int K, int lda, EpiArgs e
       const int r = pp();
       if (r != GRAM_E_ARG) return r;
     }
-    const int pv = pick_variant(M, N, K);
-    return pv == V_RING_M64    ? launch_dma<EPI, 1, 6, X3>(A, W, M, N, K, lda, ep, st)
-           : pv == V_RING_M128 ? launch_dma<EPI, 2, 4, X3>(A, W, M, N, K, lda, ep, st)
-           : pv == V_DMA_M64   ? launch_dma<EPI, 1, 1, X3>(A, W, M, N, K, lda, ep, st)
-           : pv == V_DMA   ? launch_dma<EPI, 2, 1, X3>(A, W, M, N, K, lda, ep, st)
-                           : launch_dma<EPI, 4, 1, X3>(A, W, M, N, K, lda, ep, st);
+    return launch_dma_variant<EPI, X3>(pick_variant(M, N, K), A, W, M, N, K, lda, ep, st);
   } else {
-  if constexpr (EPI == GRAM_EPI_F32_ADD) {  // big-M residual GEMMs: the ping-pong kernel with its tile-end epilogue, whatever N and K
-    if (g_force_variant < 0 && pp_ok && M >= pp_min_m()) {
-      const int r = pp();
-      if (r != GRAM_E_ARG) return r;
-    }
-  }
-  switch (pick_variant(M, N, K)) {
-    case V_DMA_M64: return launch_dma<EPI, 1, 1, X3>(A, W, M, N, K, lda, ep, st);
-    case V_RING_M64: return launch_dma<EPI, 1, 6, X3>(A, W, M, N, K, lda, ep, st);
-    case V_RING_M128: return launch_dma<EPI, 2, 4, X3>(A, W, M, N, K, lda, ep, st);
-    case V_PP:
-      if (g_force_variant == V_PP || pp_ok) {
+    if constexpr (EPI == GRAM_EPI_F32_ADD) {  // big-M residual GEMMs: the ping-pong kernel with its tile-end epilogue, whatever N and K
+      if (g_force_variant < 0 && pp_ok && M >= pp_min_m()) {
         const int r = pp();
-        if (r != GRAM_E_ARG || g_force_variant == V_PP) return r;
+        if (r != GRAM_E_ARG) return r;
       }
-      [[fallthrough]];
-    case V_DMA_M256: return launch_dma<EPI, 4, 1, X3>(A, W, M, N, K, lda, ep, st);
-    default: return launch_dma<EPI, 2, 1, X3>(A, W, M, N, K, lda, ep, st);  // V_DMA: 128 x 128 tiles
-  }
+    }
+    const int pv = pick_variant(M, N, K);
+    if (pv == V_PP && (g_force_variant == V_PP || pp_ok)) {
+      const int r = pp();
+      if (r != GRAM_E_ARG || g_force_variant == V_PP) return r;
+    }
+    return launch_dma_variant<EPI, X3>(pv, A, W, M, N, K, lda, ep, st);
   }
 }
 

@@ -1,6 +1,7 @@
-"""Race screen for the TWO-PIECE ping-pong GEMM (not a pytest; companion of stress_gemm_pp.py): its 16-bit outputs leave in the load
-slots around the tile boundary with stores counted into the DMA waits (gemm.hip, "in-load-slot epilogue") -- a wrong count reads a
-half-tile before its DMA has landed only when the timing allows it, so the schedule is screened over many shapes and runs.  Random
+"""Race screen for the TWO-PIECE ping-pong GEMM (not a pytest; companion of stress_gemm_pp.py): every result leaves in the tile-end
+epilogue, both wave groups in step, while the operand DMAs of the next tile are in flight under counted waits (gemm.hip, gemm_pp_kernel)
+-- a wrong count or a missing barrier reads a half-tile before its DMA has landed only when the timing allows it, so the schedule is
+screened over many shapes and runs.  Random
 shapes / epilogues / layouts; every output of variant 22 must equal the 256x128-tile kernel's (variant 3) bit for bit, repeatedly.
     python tests/stress_gemm_pp_x3.py [seconds]"""
 import ctypes as ct
