@@ -105,6 +105,19 @@ def device_beam_search(logits_per_step, flat_trie, B, K, max_length, lp=1.0, nre
     return seqs[:, :w].cpu(), scores.cpu(), int(keep["error"][0]), trace
 
 
+def device_live_rows(st, ctrie):
+    """gram_live_rows on a beam state -> (rows [n_rows], rowpos [R], users [n_users]) as device int32 tensors.  The buffers are
+    prefilled with -7, so anything the kernel left unwritten shows."""
+    R = st.B * st.K
+    i32 = dict(dtype=torch.int32, device=DEV)
+    o = dict(rows=torch.full((R,), -7, **i32), rowpos=torch.full((R,), -7, **i32), users=torch.full((st.B,), -7, **i32),
+             tokens=torch.full((R,), -7, **i32), counts=torch.full((4,), -7, **i32))
+    live = _lib.LiveRows(**{k: v.data_ptr() for k, v in o.items()})
+    _lib.check(lib().gram_live_rows(C.byref(st), C.byref(ctrie), C.byref(live), stream()), "gram_live_rows")
+    n_rows, n_users = o["counts"][:2].tolist()
+    return o["rows"][:n_rows], o["rowpos"], o["users"][:n_users]
+
+
 def vt_blocked(vt):
     """[..., 64, S] (V transposed) -> the bank's layout [..., S/32, 64, 32]: V^T blocked by 32 keys, so that the 64 x 32 tile of a
     32-key step is 4 KiB contiguous (include/gram_hip.h, gram_kv_bank_t)."""
