@@ -9,7 +9,9 @@
 //                                       (one D2H sync per beam per step) disappears
 //   + beam_scores, topk(2K) over K*V -> bitonic sort in LDS of the <= K*max_fanout finite
 //                                       candidates (64-bit keys: orderable score | ~flat index,
-//                                       so ties resolve to the lower flat index) + -inf fillers
+//                                       so ties resolve to the lower flat index) + -inf fillers;
+//                                       more candidates than the LDS holds stream through a fixed key
+//                                       array, the best so far carried along (beam_step_chunked_kernel)
 //   BeamSearchScorer.process         -> one thread walks the 2K ranked candidates
 //   input_ids gather / _reorder_cache-> sequences and the self-attention ancestor table are
 //                                       advanced in place; K/V caches are never moved
@@ -111,34 +113,48 @@ __global__ void beam_init_kernel(gram_beam_state_t st, gram_trie_t tr, int start
   st.node[r] = e < 0 ? -1 : tr.child_node[e];
 }
 
-// NTHR threads per workgroup (= per user): 256 for batches that fill the chip with workgroups; 1 024 for small batches, where one user's
-// sparse logits (a trip computes NTHR / 4 candidates' dot products, each on its 8 lanes) and sort stages are the step's latency
-template <int NTHR>
-__global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
-                                                        const float* __restrict__ lse, int V, int cur_len, int nc_max, int rows_per_user,
-                                                        const p16* __restrict__ hd, const p16* __restrict__ emb, int d,
-                                                        const int32_t* __restrict__ rowpos, int pieces,
-                                                        const float* __restrict__ emb32, const float* __restrict__ pre) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nc_max]
-  float* s_log = reinterpret_cast<float*>(keys + nc_max);                   // [max_fanout, rounded up to 4] shared step-0 logits
-  // [K][Tmax] + [Tmax][K]: the advanced sequences / ancestor table on their way back to HBM (sized by the call, not by the maxima)
-  int* new_seq = reinterpret_cast<int*>(smem + (size_t)nc_max * 8 + ((size_t)tr.max_fanout * 4 + 15) / 16 * 16);
-  int* new_anc = new_seq + st.K * st.Tmax;
-  __shared__ int s_pre[GRAM_MAX_BEAMS + 1];
-  __shared__ int s_C, s_NC, s_isdone;
-  __shared__ float sel_score[GRAM_MAX_BEAMS];
-  __shared__ int sel_tok[GRAM_MAX_BEAMS], sel_par[GRAM_MAX_BEAMS], sel_node[GRAM_MAX_BEAMS];
-  __shared__ int s_edge[2 * GRAM_MAX_BEAMS];
-  __shared__ int s_off[GRAM_MAX_BEAMS], s_cnt[GRAM_MAX_BEAMS], s_lr[GRAM_MAX_BEAMS];
+// ---- the search step, in pieces shared by its two kernels: beam_step_kernel (every candidate of a user in LDS at once) and
+// beam_step_chunked_kernel (candidates streamed through a fixed key array).  Both build the same keys with the same arithmetic, run
+// the same top-P selection and finish with the same code, so they return the same bits wherever both can run.
 
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int K = st.K, T = st.Tmax, R = st.B * K;
-  const int row0 = b * K;
-  const int t = cur_len - 1;  // decode step whose K/V were just written
+// the step's operands (the kernels' parameters, handed on by reference)
+struct StepArgs {
+  const gram_beam_state_t& st;
+  const gram_trie_t& tr;
+  const float* __restrict__ logits;
+  const float* __restrict__ lse;
+  int V, cur_len, rows_per_user;
+  const p16* __restrict__ hd;
+  const p16* __restrict__ emb;
+  int d;
+  const int32_t* __restrict__ rowpos;
+  int pieces;
+  const float* __restrict__ emb32;
+  const float* __restrict__ pre;
+  int pre_stride;
+};
 
-  // per beam: first child edge, child count, hidden-state row -- K threads at once (one thread walking the K beams was K dependent
-  // node -> offsets round trips, ~20 us of a 100-us step at K = 20)
+// the step's small per-user tables (static LDS, ~3 KB)
+struct StepShared {
+  int pre[GRAM_MAX_BEAMS + 1];
+  int C, NC, isdone;
+  float sel_score[GRAM_MAX_BEAMS];
+  int sel_tok[GRAM_MAX_BEAMS], sel_par[GRAM_MAX_BEAMS], sel_node[GRAM_MAX_BEAMS];
+  int edge[2 * GRAM_MAX_BEAMS];
+  int off[GRAM_MAX_BEAMS], cnt[GRAM_MAX_BEAMS], lr[GRAM_MAX_BEAMS];
+};
+
+__device__ __forceinline__ unsigned long long cand_key(float sc, int k, int V, int tok) {
+  return ((unsigned long long)f2ord(sc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(k * V + tok));
+}
+
+// per beam: first child edge, child count, hidden-state row; then the prefix sums of the counts: candidate ci of the user is child
+// ci - pre[k] of beam k, pre[k] <= ci < pre[k + 1].  nc_max > 0: more candidates than that is error 2 (the one-shot kernel's key array)
+__device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, int b, int tid, int nc_max) {
+  const gram_beam_state_t& st = a.st;
+  const gram_trie_t& tr = a.tr;
+  const int K = st.K, row0 = b * K;
+  // K threads at once (one thread walking the K beams was K dependent node -> offsets round trips, ~20 us of a 100-us step at K = 20)
   if (tid < K) {
     const int nd = st.node[row0 + tid];
     const int done = st.done[b];
@@ -147,174 +163,214 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
       o0 = tr.child_off[nd];
       cnt = tr.child_off[nd + 1] - o0;
     }
-    s_off[tid] = o0;
-    s_cnt[tid] = cnt;
-    s_lr[tid] = rowpos ? rowpos[row0 + tid] : row0 + tid;  // live-row step: hidden/lse are indexed by compact row
-    if (tid == 0) s_isdone = done;
+    sh.off[tid] = o0;
+    sh.cnt[tid] = cnt;
+    sh.lr[tid] = a.rowpos ? a.rowpos[row0 + tid] : row0 + tid;  // live-row step: hidden/lse are indexed by compact row
+    if (tid == 0) sh.isdone = done;
   }
   gram_sync();
   if (tid == 0) {
     int acc = 0;
     for (int k = 0; k < K; ++k) {
-      s_pre[k] = acc;
-      acc += s_cnt[k];
+      sh.pre[k] = acc;
+      acc += sh.cnt[k];
     }
-    s_pre[K] = acc;
-    s_C = acc;
+    sh.pre[K] = acc;
+    sh.C = acc;
     int nc = 64;
-    while (nc < acc) nc <<= 1;
-    s_NC = nc;
-    if (acc > nc_max) { st.error[0] = 2; s_C = 0; s_NC = 64; s_pre[K] = 0; }
+    while (nc < acc && nc < (1 << 30)) nc <<= 1;
+    sh.NC = nc;
+    if (nc_max > 0 && acc > nc_max) { st.error[0] = 2; sh.C = 0; sh.NC = 64; sh.pre[K] = 0; }
   }
   gram_sync();
-  const int C = s_C, NC = s_NC;
-  const bool isdone = s_isdone != 0;
+}
 
-  if (!isdone && logits == nullptr) {
-    // SPARSE mode: the lm_head GEMM stored only the softmax partials (lse); the logits of the <= K*fan-out
-    // allowed tokens are recomputed here as h[row] . E[tok] (bf16 operands, fp32 accumulate; 8 lanes per
-    // candidate, 16-byte loads).  The [rows][V] logits tensor (5 GB per step at B = 2048) is never written.
-    for (int ci = C + tid; ci < NC; ci += NTHR) keys[ci] = 0ull;
-    const int sub = tid & 7, grp = tid >> 3;
-    const bool shared0 = rows_per_user == 1;  // step 0: all K beams sit on the same node and the same row
-    const int nuniq = shared0 ? s_pre[1] : C;
-    // (beam, token) of every candidate first, all threads at once, parked in the candidate's key slot: the dot products below then
-    // start from LDS instead of a node -> edge -> token chain of global loads per batch
-    for (int ci = tid; ci < nuniq; ci += NTHR) {
+// SPARSE mode: the lm_head GEMM stored only the softmax partials (lse); the logits of the allowed tokens are recomputed here as
+// h[row] . E[tok] (bf16 operands, fp32 accumulate; 8 lanes per candidate, 16-byte loads).  The [rows][V] logits tensor (5 GB per step
+// at B = 2048) is never written.  Candidates [c0, c0 + n) of the user's list go to kw[0, n) as keys; shared0 (step 0: all K beams sit
+// on the same node and the same row): children [c0, c0 + n) of that node, their logits go to s_log[0, n) and shared0_keys makes the
+// K keys of each.  The caller puts a barrier behind it.
+template <int NTHR>
+__device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, float* s_log, int b, int tid,
+                                              int c0, int n, bool shared0) {
+  const gram_beam_state_t& st = a.st;
+  const gram_trie_t& tr = a.tr;
+  const int row0 = b * st.K, V = a.V;
+  const int sub = tid & 7, grp = tid >> 3;
+  // (beam, token) of every candidate first, all threads at once, parked in the candidate's key slot: the dot products below then
+  // start from LDS instead of a node -> edge -> token chain of global loads per batch
+  for (int i = tid; i < n; i += NTHR) {
+    const int ci = c0 + i;
+    int k = 0;
+    if (!shared0)
+      while (sh.pre[k + 1] <= ci) ++k;
+    const int tok = tr.child_tok[sh.off[k] + (ci - sh.pre[k])];
+    kw[i] = ((unsigned long long)(uint32_t)k << 32) | (unsigned long long)(uint32_t)tok;
+  }
+  gram_sync();
+  auto dot = [&](bool act, int lr, int tok, int ci) -> float {
+    if (a.pre) return act ? a.pre[(size_t)b * a.pre_stride + ci] : 0.f;  // (computed by sparse_logits_kernel: the same function, the same bits)
+    return sparse_dot(act, lr, tok, sub, a.hd, a.emb, a.emb32, a.d, a.pieces);
+  };
+  // two candidates per 8-lane group and trip (NTHR / 4 per workgroup): their loads are independent and overlap
+  constexpr int NG = NTHR / 8;
+  for (int base = 0; base < n; base += 2 * NG) {
+    int i2[2], k2[2], tok2[2], lr2[2];
+    bool act2[2];
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+      i2[w] = base + NG * w + grp;
+      act2[w] = i2[w] < n;
+      const unsigned long long kt = act2[w] ? kw[i2[w]] : 0ull;
+      k2[w] = (int)(kt >> 32);
+      tok2[w] = (int)(kt & 0xffffffffull);
+      lr2[w] = shared0 ? b : sh.lr[k2[w]];
+    }
+    float acc2[2];
+#pragma unroll
+    for (int w = 0; w < 2; ++w) acc2[w] = dot(act2[w], lr2[w], tok2[w], c0 + i2[w]);
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+      if (act2[w] && sub == 0) {
+        if (shared0) {
+          s_log[i2[w]] = acc2[w];
+        } else {
+          const float sc = (acc2[w] - a.lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
+          kw[i2[w]] = cand_key(sc, k2[w], V, tok2[w]);
+        }
+      }
+    }
+  }
+}
+
+// step 0's shared row: the keys of beams [k0, k0 + kg) x children [j0, j0 + nj) of the shared node, from the nj logits that
+// sparse_window left in s_log: kw[(k - k0) * nj + (j - j0)].  (k0 = j0 = 0, kg = K, nj = the node's fan-out: the user's whole list
+// in its flat-index order)
+template <int NTHR>
+__device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared& sh, unsigned long long* kw, const float* s_log, int b,
+                                             int tid, int j0, int nj, int k0, int kg) {
+  const gram_beam_state_t& st = a.st;
+  const gram_trie_t& tr = a.tr;
+  const int row0 = b * st.K;
+  const int cnt0 = sh.pre[1];
+  const int off0 = cnt0 > 0 ? tr.child_off[st.node[row0]] : 0;
+  for (int i = tid; i < kg * nj; i += NTHR) {
+    const int kk = i / nj, jj = i - kk * nj;
+    const int k = k0 + kk;
+    const int tok = tr.child_tok[off0 + j0 + jj];
+    const float sc = (s_log[jj] - a.lse[b]) + st.beam_scores[row0 + k];
+    kw[i] = cand_key(sc, k, a.V, tok);
+  }
+}
+
+// DENSE mode, gather: log_softmax at the allowed tokens + running beam score.  Candidates [c0, c0 + n) -> kw[0, n); kw[n, npad) = 0
+template <int NTHR>
+__device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, int b, int tid, int c0, int n,
+                                             int npad) {
+  const gram_beam_state_t& st = a.st;
+  const gram_trie_t& tr = a.tr;
+  const int row0 = b * st.K, V = a.V;
+  for (int i = tid; i < npad; i += NTHR) {
+    unsigned long long key = 0ull;
+    if (i < n) {
+      const int ci = c0 + i;
       int k = 0;
-      if (!shared0)
-        while (s_pre[k + 1] <= ci) ++k;
-      const int tok = tr.child_tok[s_off[k] + (ci - s_pre[k])];
-      keys[ci] = ((unsigned long long)(uint32_t)k << 32) | (unsigned long long)(uint32_t)tok;
+      while (sh.pre[k + 1] <= ci) ++k;
+      const int r = row0 + k;
+      const int e = tr.child_off[st.node[r]] + (ci - sh.pre[k]);
+      const int tok = tr.child_tok[e];
+      // rows_per_user == 1: the K beams of a user share one logits row (step 0: identical beams)
+      const int lr = a.rows_per_user == 1 ? b : r;
+      const float sc = (a.logits[(size_t)lr * V + tok] - a.lse[lr]) + st.beam_scores[r];
+      key = cand_key(sc, k, V, tok);
     }
-    gram_sync();
-    auto dot = [&](bool act, int lr, int tok, int ci) -> float {
-      if (pre) return act ? pre[(size_t)b * nc_max + ci] : 0.f;  // (computed by sparse_logits_kernel: the same function, the same bits)
-      return sparse_dot(act, lr, tok, sub, hd, emb, emb32, d, pieces);
-    };
-    // two candidates per 8-lane group and trip (NTHR / 4 per workgroup): their loads are independent and overlap
-    constexpr int NG = NTHR / 8;
-    for (int base = 0; base < nuniq; base += 2 * NG) {
-      int ci2[2], k2[2], tok2[2], lr2[2];
-      bool act2[2];
-#pragma unroll
-      for (int w = 0; w < 2; ++w) {
-        ci2[w] = base + NG * w + grp;
-        act2[w] = ci2[w] < nuniq;
-        const unsigned long long kt = act2[w] ? keys[ci2[w]] : 0ull;
-        k2[w] = (int)(kt >> 32);
-        tok2[w] = (int)(kt & 0xffffffffull);
-        lr2[w] = shared0 ? b : s_lr[k2[w]];
-      }
-      float acc2[2];
-#pragma unroll
-      for (int w = 0; w < 2; ++w) acc2[w] = dot(act2[w], lr2[w], tok2[w], ci2[w]);
-#pragma unroll
-      for (int w = 0; w < 2; ++w) {
-        if (act2[w] && sub == 0) {
-          if (shared0) {
-            s_log[ci2[w]] = acc2[w];
-          } else {
-            const float sc = (acc2[w] - lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
-            keys[ci2[w]] = ((unsigned long long)f2ord(sc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(k2[w] * V + tok2[w]));
-          }
+    kw[i] = key;
+  }
+}
+
+// Non-finite arithmetic is flagged HERE, at its source (GRAM_E_NONFINITE), not at the returned scores: a NaN candidate sorts above
+// +inf (positive NaN) or below -inf (negative NaN) and would be picked first or never, a row whose normaliser is +inf / NaN turns
+// all its candidates into -inf / NaN -- either way the search would go on and return an ordinary-looking ranking without them.
+// -inf candidates are legitimate (HF's -inf refills of finished beams).  Every candidate's key passes through here before the
+// selection can drop it.
+template <int NTHR>
+__device__ __forceinline__ void flag_nonfinite_keys(const StepArgs& a, const unsigned long long* kw, int n, int tid) {
+  for (int i = tid; i < n; i += NTHR) {
+    const uint32_t o = (uint32_t)(kw[i] >> 32);
+    if (o >= 0xff800000u || o < 0x007fffffu) a.st.error[0] = 4;  // f2ord(+inf) = 0xff800000, f2ord(-inf) = 0x007fffff
+  }
+}
+__device__ __forceinline__ void flag_nonfinite_lse(const StepArgs& a, const StepShared& sh, int b, int tid) {
+  if (tid < a.st.K && sh.cnt[tid] > 0) {
+    const int lr = a.rows_per_user == 1 ? b : sh.lr[tid];
+    if (lr >= 0 && !(fabsf(a.lse[lr]) < 3.0e38f)) a.st.error[0] = 4;
+  }
+}
+
+// Only the best 2K candidates are looked at (topk(2K) in beam_search), in descending order: a bitonic TOP-P
+// selection, P = the power of two >= 2K.  Sort every P-block (directions alternating, as in a full bitonic sort
+// stopped at stage P), then halve the array round by round: a descending block followed by an ascending one is a
+// bitonic sequence, so the elementwise maxima of the pair are a bitonic block that holds the pair's P largest keys;
+// re-sort it (log2 P merge stages) and go on until one block is left.  ~3x fewer compare-exchanges than sorting
+// all NC keys; keys are unique (flat index in the low word), so the result is the full sort's prefix: keys[0, min(NC, P)) descending.
+// NC: a power of two, 64 <= NC <= MAXN.  Ends behind a barrier.
+template <int NTHR, int MAXN>
+__device__ __forceinline__ void top_p_select(unsigned long long* keys, int NC, int P, int tid) {
+  const int top = NC < P ? NC : P;
+  auto stage = [&](int n, int kk, int j) {
+    for (int i = tid; i < n; i += NTHR) {
+      const int ixj = i ^ j;
+      if (ixj > i) {
+        const unsigned long long a = keys[i], c = keys[ixj];
+        const bool desc = (i & kk) == 0;
+        if (desc ? (a < c) : (a > c)) {
+          keys[i] = c;
+          keys[ixj] = a;
         }
       }
     }
-    if (shared0) {
-      gram_sync();
-      const int cnt0 = s_pre[1];
-      const int off0 = cnt0 > 0 ? tr.child_off[st.node[row0]] : 0;
-      for (int ci = tid; ci < C; ci += NTHR) {
-        const int k = ci / cnt0, j = ci - k * cnt0;
-        const int tok = tr.child_tok[off0 + j];
-        const float sc = (s_log[j] - lse[b]) + st.beam_scores[row0 + k];
-        keys[ci] = ((unsigned long long)f2ord(sc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(k * V + tok));
+    gram_sync();
+  };
+  for (int kk = 2; kk <= top; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) stage(NC, kk, j);
+  for (int n = NC; n > P; n >>= 1) {
+    // blocks (2q, 2q+1) -> block q of the half-size array; every thread reads its pairs before anyone writes
+    const int half = n >> 1;
+    constexpr int NMX = MAXN / 2 / NTHR;  // half / NTHR <= MAXN / 2 / NTHR; statically indexed: stays in registers
+    unsigned long long mx[NMX];
+#pragma unroll
+    for (int c = 0; c < NMX; ++c) {
+      const int o = tid + c * NTHR;
+      if (o < half) {
+        const int q = o / P, i = o - q * P;
+        const unsigned long long a = keys[(2 * q) * P + i], b2 = keys[(2 * q + 1) * P + i];
+        mx[c] = a > b2 ? a : b2;
       }
     }
     gram_sync();
-  }
-  if (!isdone && logits != nullptr) {
-    // gather: log_softmax at the allowed tokens + running beam score
-    for (int ci = tid; ci < NC; ci += NTHR) {
-      unsigned long long key = 0ull;
-      if (ci < C) {
-        int k = 0;
-        while (s_pre[k + 1] <= ci) ++k;
-        const int r = row0 + k;
-        const int e = tr.child_off[st.node[r]] + (ci - s_pre[k]);
-        const int tok = tr.child_tok[e];
-        // rows_per_user == 1: the K beams of a user share one logits row (step 0: identical beams)
-        const int lr = rows_per_user == 1 ? b : r;
-        const float sc = (logits[(size_t)lr * V + tok] - lse[lr]) + st.beam_scores[r];
-        key = ((unsigned long long)f2ord(sc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(k * V + tok));
-      }
-      keys[ci] = key;
+#pragma unroll
+    for (int c = 0; c < NMX; ++c) {
+      const int o = tid + c * NTHR;
+      if (o < half) keys[o] = mx[c];
     }
     gram_sync();
+    for (int j = P >> 1; j > 0; j >>= 1) stage(half, P, j);  // bitonic blocks -> sorted, directions alternating again
   }
-  if (!isdone) {
-    // Non-finite arithmetic is flagged HERE, at its source (GRAM_E_NONFINITE), not at the returned scores: a NaN candidate sorts above
-    // +inf (positive NaN) or below -inf (negative NaN) and would be picked first or never, a row whose normaliser is +inf / NaN turns
-    // all its candidates into -inf / NaN -- either way the search would go on and return an ordinary-looking ranking without them.
-    // -inf candidates are legitimate (HF's -inf refills of finished beams).
-    for (int ci = tid; ci < C; ci += NTHR) {
-      const uint32_t o = (uint32_t)(keys[ci] >> 32);
-      if (o >= 0xff800000u || o < 0x007fffffu) st.error[0] = 4;  // f2ord(+inf) = 0xff800000, f2ord(-inf) = 0x007fffff
-    }
-    if (tid < K && s_cnt[tid] > 0) {
-      const int lr = rows_per_user == 1 ? b : s_lr[tid];
-      if (lr >= 0 && !(fabsf(lse[lr]) < 3.0e38f)) st.error[0] = 4;
-    }
-    // Only the best 2K candidates are looked at (topk(2K) in beam_search), in descending order: a bitonic TOP-P
-    // selection, P = the power of two >= 2K.  Sort every P-block (directions alternating, as in a full bitonic sort
-    // stopped at stage P), then halve the array round by round: a descending block followed by an ascending one is a
-    // bitonic sequence, so the elementwise maxima of the pair are a bitonic block that holds the pair's P largest keys;
-    // re-sort it (log2 P merge stages) and go on until one block is left.  ~3x fewer compare-exchanges than sorting
-    // all NC <= 16 384 keys; keys are unique (flat index in the low word), so the result is the full sort's prefix.
-    int P = 64;
-    while (P < 2 * K) P <<= 1;
-    const int top = NC < P ? NC : P;
-    auto stage = [&](int n, int kk, int j) {
-      for (int i = tid; i < n; i += NTHR) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], c = keys[ixj];
-          const bool desc = (i & kk) == 0;
-          if (desc ? (a < c) : (a > c)) {
-            keys[i] = c;
-            keys[ixj] = a;
-          }
-        }
-      }
-      gram_sync();
-    };
-    for (int kk = 2; kk <= top; kk <<= 1)
-      for (int j = kk >> 1; j > 0; j >>= 1) stage(NC, kk, j);
-    for (int n = NC; n > P; n >>= 1) {
-      // blocks (2q, 2q+1) -> block q of the half-size array; every thread reads its pairs before anyone writes
-      const int half = n >> 1;
-      constexpr int NMX = 8192 / NTHR;  // half / NTHR <= 8192 / NTHR (K * max_fanout <= 16 384); statically indexed: stays in registers
-      unsigned long long mx[NMX];
-#pragma unroll
-      for (int c = 0; c < NMX; ++c) {
-        const int o = tid + c * NTHR;
-        if (o < half) {
-          const int q = o / P, i = o - q * P;
-          const unsigned long long a = keys[(2 * q) * P + i], b2 = keys[(2 * q + 1) * P + i];
-          mx[c] = a > b2 ? a : b2;
-        }
-      }
-      gram_sync();
-#pragma unroll
-      for (int c = 0; c < NMX; ++c) {
-        const int o = tid + c * NTHR;
-        if (o < half) keys[o] = mx[c];
-      }
-      gram_sync();
-      for (int j = P >> 1; j > 0; j >>= 1) stage(half, P, j);  // bitonic blocks -> sorted, directions alternating again
-    }
-  }
+}
+
+// Everything behind the selection: keys[0, min(C, 2K)) hold the user's best candidates in descending order (C = sh.C of them in
+// all).  BeamSearchScorer.process on one thread, then the sequences / ancestor table / per-row state are advanced through
+// new_seq [K][Tmax] / new_anc [Tmax][K] (LDS).
+template <int NTHR>
+__device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int* new_seq, int* new_anc,
+                                            int b, int tid) {
+  const gram_beam_state_t& st = a.st;
+  const gram_trie_t& tr = a.tr;
+  const int K = st.K, T = st.Tmax, R = st.B * K, V = a.V, cur_len = a.cur_len;
+  const int row0 = b * K;
+  const int t = cur_len - 1;  // decode step whose K/V were just written
+  const int C = sh.C;
+  const bool isdone = sh.isdone != 0;
 
   // the Trie edge of every ranked candidate, looked up by 2K threads at once (one binary search each; the walk below ran them one
   // after the other: up to K dependent searches of ~6 global loads each on a single thread)
@@ -327,7 +383,7 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
         const int k = (int)(flat / (uint32_t)V), tok = (int)(flat % (uint32_t)V);
         if (tok != st.eos) e = find_child(tr, st.node[row0 + k], tok);
       }
-      s_edge[rank] = e;
+      sh.edge[rank] = e;
     }
     gram_sync();
   }
@@ -336,10 +392,10 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
     if (isdone) {
       // BeamSearchScorer.process pads a finished user
       for (int j = 0; j < K; ++j) {
-        sel_score[j] = 0.f;
-        sel_tok[j] = st.pad;
-        sel_par[j] = j;
-        sel_node[j] = -1;
+        sh.sel_score[j] = 0.f;
+        sh.sel_tok[j] = st.pad;
+        sh.sel_par[j] = j;
+        sh.sel_node[j] = -1;
       }
     } else {
       int j = 0;
@@ -366,17 +422,17 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
           if (rank >= K) continue;
           hyp_add(st, b, st.seq + (size_t)(row0 + k) * T, cur_len, sc);
         } else {
-          const int e = (rank < C) ? s_edge[rank] : -1;
-          sel_score[j] = sc;
-          sel_tok[j] = tok;
-          sel_par[j] = k;
-          sel_node[j] = e < 0 ? -1 : tr.child_node[e];
+          const int e = (rank < C) ? sh.edge[rank] : -1;
+          sh.sel_score[j] = sc;
+          sh.sel_tok[j] = tok;
+          sh.sel_par[j] = k;
+          sh.sel_node[j] = e < 0 ? -1 : tr.child_node[e];
           ++j;
         }
       }
       if (j < K) {
         st.error[0] = 1;  // HF raises ValueError here
-        for (; j < K; ++j) { sel_score[j] = -INFINITY; sel_tok[j] = st.pad; sel_par[j] = 0; sel_node[j] = -1; }
+        for (; j < K; ++j) { sh.sel_score[j] = -INFINITY; sh.sel_tok[j] = st.pad; sh.sel_par[j] = 0; sh.sel_node[j] = -1; }
       }
       // BeamHypotheses.is_done(best_sum_logprobs = next_scores.max(), cur_len)
       if (st.n_hyps[b] >= K) {
@@ -391,15 +447,15 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
   for (int idx = tid; idx < K * T; idx += NTHR) {
     const int j = idx / T, p = idx - j * T;
     int v = 0;
-    if (p < cur_len) v = st.seq[(size_t)(row0 + sel_par[j]) * T + p];
-    else if (p == cur_len) v = sel_tok[j];
+    if (p < cur_len) v = st.seq[(size_t)(row0 + sh.sel_par[j]) * T + p];
+    else if (p == cur_len) v = sh.sel_tok[j];
     new_seq[idx] = v;
   }
   for (int idx = tid; idx < T * K; idx += NTHR) {
     const int p = idx / K, j = idx - p * K;
     int v;
-    if (p < t) v = st.anc[(size_t)p * R + row0 + sel_par[j]];
-    else if (p == t) v = rows_per_user == 1 ? b : row0 + sel_par[j];  // compact step: slot t holds one row per user
+    if (p < t) v = st.anc[(size_t)p * R + row0 + sh.sel_par[j]];
+    else if (p == t) v = a.rows_per_user == 1 ? b : row0 + sh.sel_par[j];  // compact step: slot t holds one row per user
     else v = row0 + j;
     new_anc[idx] = v;
   }
@@ -410,10 +466,148 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
     st.anc[(size_t)p * R + row0 + j] = new_anc[idx];
   }
   if (tid < K) {
-    st.beam_scores[row0 + tid] = sel_score[tid];
-    st.tokens[row0 + tid] = sel_tok[tid];
-    st.node[row0 + tid] = sel_node[tid];
+    st.beam_scores[row0 + tid] = sh.sel_score[tid];
+    st.tokens[row0 + tid] = sh.sel_tok[tid];
+    st.node[row0 + tid] = sh.sel_node[tid];
   }
+}
+
+constexpr int kOneShotMaxKeys = 16384;  // K * max_fanout the one-shot kernel takes (128 KB of keys)
+
+// ONE-SHOT form: all of a user's candidates in LDS at once (K * max_fanout <= 16 384 and the LDS sum below within the CU's 160 KB).
+// NTHR threads per workgroup (= per user): 256 for batches that fill the chip with workgroups; 1 024 for small batches, where one user's
+// sparse logits (a trip computes NTHR / 4 candidates' dot products, each on its 8 lanes) and sort stages are the step's latency
+template <int NTHR>
+__global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
+                                                        const float* __restrict__ lse, int V, int cur_len, int nc_max, int rows_per_user,
+                                                        const p16* __restrict__ hd, const p16* __restrict__ emb, int d,
+                                                        const int32_t* __restrict__ rowpos, int pieces,
+                                                        const float* __restrict__ emb32, const float* __restrict__ pre) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nc_max]
+  float* s_log = reinterpret_cast<float*>(keys + nc_max);                   // [max_fanout, rounded up to 4] shared step-0 logits
+  // [K][Tmax] + [Tmax][K]: the advanced sequences / ancestor table on their way back to HBM (sized by the call, not by the maxima)
+  int* new_seq = reinterpret_cast<int*>(smem + (size_t)nc_max * 8 + ((size_t)tr.max_fanout * 4 + 15) / 16 * 16);
+  int* new_anc = new_seq + st.K * st.Tmax;
+  __shared__ StepShared sh;
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max};
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int K = st.K;
+  step_setup(a, sh, b, tid, nc_max);
+  const int C = sh.C, NC = sh.NC;
+  const bool isdone = sh.isdone != 0;
+
+  if (!isdone && logits == nullptr) {
+    for (int ci = C + tid; ci < NC; ci += NTHR) keys[ci] = 0ull;
+    const bool shared0 = rows_per_user == 1;
+    sparse_window<NTHR>(a, sh, keys, s_log, b, tid, 0, shared0 ? sh.pre[1] : C, shared0);
+    if (shared0) {
+      gram_sync();
+      shared0_keys<NTHR>(a, sh, keys, s_log, b, tid, 0, sh.pre[1], 0, K);
+    }
+    gram_sync();
+  }
+  if (!isdone && logits != nullptr) {
+    dense_window<NTHR>(a, sh, keys, b, tid, 0, C, NC);
+    gram_sync();
+  }
+  if (!isdone) {
+    flag_nonfinite_keys<NTHR>(a, keys, C, tid);
+    flag_nonfinite_lse(a, sh, b, tid);
+    int P = 64;
+    while (P < 2 * K) P <<= 1;
+    top_p_select<NTHR, kOneShotMaxKeys>(keys, NC, P, tid);
+  }
+  step_finish<NTHR>(a, sh, keys, new_seq, new_anc, b, tid);
+}
+
+// CHUNKED form: any fan-out.  The candidates stream through a fixed key array: keys[0, P) carry the best P keys so far (descending;
+// zero keys -- below every real key, whose low word is never 0 -- while fewer have been seen), keys[P, P + n) take the next n <= cap
+// candidates, the same top-P selection runs over the power of two >= P + n, and so on until the list is exhausted.  The keys are
+// unique and the order total, so what is carried is always the P best of everything seen: at the end keys[0, 2K) are the full
+// sort's prefix, the one-shot kernel's bits.  The order in which candidates arrive is free; step 0's shared row uses that: it takes
+// the shared node's children kChunkLog at a time (their logits in s_log) and makes the keys of as many beams per round as fit.
+//
+// LDS, independent of max_fanout:   keys   [kChunkKeys] u64     32 KB
+//                                   s_log  [kChunkLog]  f32      8 KB
+//                                   new_seq / new_anc   2 * K * Tmax * 4 B (3.8 KB at K = 20, Tmax = 12; 64 KB at K = 64, Tmax = 64)
+//                                   static tables                ~3 KB
+// 4 096 keys: at the runners' shapes (K = 20) a 256-thread workgroup takes ~47 KB, so three of them (12 wavefronts) share a CU's
+// 160 KB; 8 192 keys (~83 KB) would leave one workgroup, 4 wavefronts, per CU -- and the one-shot kernel at K * fan-out > 4 096 is
+// there already -- while 2 048 keys would give 6 workgroups but twice the rounds, each with its barriers and its carried block
+// (P of the array: 1/32 at P = 128, kChunkKeys = 4 096).  The selection's compare-exchange count per candidate does not depend on
+// the array size (log^2 P block stages + the halvings), so the array only has to be large enough to keep the rounds few.  The
+// worst case, K = 64 and Tmax = 64, is 32 + 8 + 64 + 3 = 107 KB: one workgroup per CU, and it fits.
+constexpr int kChunkKeys = 4096;
+constexpr int kChunkLog = 2048;
+
+template <int NTHR>
+__global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
+                                                                const float* __restrict__ lse, int V, int cur_len, int cap,
+                                                                int rows_per_user, const p16* __restrict__ hd,
+                                                                const p16* __restrict__ emb, int d, const int32_t* __restrict__ rowpos,
+                                                                int pieces, const float* __restrict__ emb32) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [kChunkKeys]
+  float* s_log = reinterpret_cast<float*>(keys + kChunkKeys);              // [kChunkLog]
+  int* new_seq = reinterpret_cast<int*>(s_log + kChunkLog);                // [K][Tmax] + [Tmax][K], as in the one-shot kernel
+  int* new_anc = new_seq + st.K * st.Tmax;
+  __shared__ StepShared sh;
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0};
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int K = st.K;
+  step_setup(a, sh, b, tid, 0);
+  const int C = sh.C;
+  const bool isdone = sh.isdone != 0;
+
+  if (!isdone) {
+    flag_nonfinite_lse(a, sh, b, tid);
+    int P = 64;
+    while (P < 2 * K) P <<= 1;
+    if (cap > kChunkKeys - P) cap = kChunkKeys - P;  // (the launcher's job; a wrong value must not reach past the array)
+    if (cap < 1) cap = 1;
+    unsigned long long* kw = keys + P;
+    for (int i = tid; i < P; i += NTHR) keys[i] = 0ull;  // nothing carried yet
+    // kw[0, n) hold fresh keys (all threads behind a barrier or not: one follows the padding)
+    auto merge = [&](int n) {
+      int na = 2 * P;  // the power of two >= P + n
+      while (na < P + n) na <<= 1;
+      for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
+      gram_sync();
+      flag_nonfinite_keys<NTHR>(a, kw, n, tid);
+      top_p_select<NTHR, kChunkKeys>(keys, na, P, tid);
+    };
+    if (logits != nullptr) {
+      for (int c0 = 0; c0 < C; c0 += cap) {
+        const int n = C - c0 < cap ? C - c0 : cap;
+        dense_window<NTHR>(a, sh, kw, b, tid, c0, n, n);
+        merge(n);
+      }
+    } else if (rows_per_user != 1) {
+      for (int c0 = 0; c0 < C; c0 += cap) {
+        const int n = C - c0 < cap ? C - c0 : cap;
+        sparse_window<NTHR>(a, sh, kw, s_log, b, tid, c0, n, false);
+        merge(n);
+      }
+    } else {
+      const int cnt0 = sh.pre[1];
+      const int njmax = cap < kChunkLog ? cap : kChunkLog;
+      for (int j0 = 0; j0 < cnt0; j0 += njmax) {
+        const int nj = cnt0 - j0 < njmax ? cnt0 - j0 : njmax;
+        sparse_window<NTHR>(a, sh, kw, s_log, b, tid, j0, nj, true);
+        gram_sync();
+        const int kgmax = cap / nj;  // >= 1
+        for (int k0 = 0; k0 < K; k0 += kgmax) {
+          const int kg = K - k0 < kgmax ? K - k0 : kgmax;
+          shared0_keys<NTHR>(a, sh, kw, s_log, b, tid, j0, nj, k0, kg);
+          merge(kg * nj);
+        }
+      }
+    }
+  }
+  step_finish<NTHR>(a, sh, keys, new_seq, new_anc, b, tid);
 }
 
 // The sparse logits of a search step, computed by MANY workgroups (a handful of users: beam_step_kernel's one workgroup per user pulls
@@ -659,6 +853,20 @@ extern "C" int gram_beam_init(const gram_beam_state_t* st, const gram_trie_t* tr
   return 0;
 }
 
+// gram_debug_set_beam_chunked / gram_debug_set_beam_chunk_capacity (gram_hip.h): which form of the search step runs, and a test hook
+static int g_beam_chunked = -1;  // -1 / 0: by shape; 1: always the chunked kernel
+static int g_beam_chunk_cap = 0;  // 0: what the key array holds; n: at most n fresh candidates per round
+extern "C" int gram_debug_set_beam_chunked(int mode) {
+  if (mode < -1 || mode > 1) return GRAM_E_ARG;
+  g_beam_chunked = mode;
+  return 0;
+}
+extern "C" int gram_debug_set_beam_chunk_capacity(int candidates) {
+  if (candidates < 0) return GRAM_E_ARG;
+  g_beam_chunk_cap = candidates;
+  return 0;
+}
+
 static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                             int cur_len, int rows_per_user, const void* hd, const void* emb, int d, const int32_t* rowpos,
                             void* stream, int pieces = 1, const float* emb32 = nullptr) {
@@ -666,11 +874,47 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
   if (!tr || !lse || cur_len < 1 || cur_len >= st->Tmax || V < 2 || (rows_per_user != 1 && rows_per_user != st->K)) return GRAM_E_ARG;
   if (!logits && (!hd || (!emb && !emb32) || d < 64 || (d & 63))) return GRAM_E_ARG;
   if (pieces < 1 || pieces > GRAM_MAX_PIECES || (pieces > 1 && (!emb32 || (d & 63)))) return GRAM_E_ARG;  // (8 lanes x 8-element loads inside 32-column blocks)
+  if (tr->max_fanout < 0) return GRAM_E_ARG;
   long long need = (long long)st->K * tr->max_fanout;
   int nc = 64;
-  while (nc < need) nc <<= 1;
-  const size_t smem = (size_t)nc * 8 + ((size_t)tr->max_fanout * 4 + 15) / 16 * 16 + (size_t)2 * st->K * st->Tmax * 4;
-  if (smem > 152 * 1024) return GRAM_E_ARG;  // (+ ~3 KB of static arrays: the CU's 160 KB)
+  while (nc < need && nc < kOneShotMaxKeys) nc <<= 1;
+  const size_t seq_bytes = (size_t)2 * st->K * st->Tmax * 4;
+  const size_t smem_one = (size_t)nc * 8 + ((size_t)tr->max_fanout * 4 + 15) / 16 * 16 + seq_bytes;
+  // one-shot: every candidate of a user in LDS at once (+ ~3 KB of static arrays: the CU's 160 KB); everything else streams
+  const bool chunked = g_beam_chunked == 1 || need > kOneShotMaxKeys || smem_one > 152 * 1024;
+  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
+  // few users: one workgroup per user leaves the chip empty and the step is that workgroup's latency -> 1 024 threads per user
+  // (same per-candidate arithmetic, same total order of the keys: identical results; GRAM_BEAM_WIDE_MAXB: A/B hook, 0 = never)
+  static const int wide_max_b = getenv("GRAM_BEAM_WIDE_MAXB") ? atoi(getenv("GRAM_BEAM_WIDE_MAXB")) : 128;
+  if (chunked) {
+    // 32-bit scalar state of the kernel: the flat index k * V + tok < K * V, and the candidate count and its prefix sums <= K * V
+    // (a node has at most V children)
+    if ((long long)st->K * V > INT32_MAX || tr->max_fanout > V) return GRAM_E_ARG;
+    int P = 64;
+    while (P < 2 * st->K) P <<= 1;
+    int cap = kChunkKeys - P;
+    if (g_beam_chunk_cap > 0 && g_beam_chunk_cap < cap) cap = g_beam_chunk_cap;
+    const size_t smem = (size_t)kChunkKeys * 8 + (size_t)kChunkLog * 4 + seq_bytes;  // <= 40 KB + 64 KB
+    static size_t attr_bytes = 0;
+    if (smem > attr_bytes) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_kernel<256>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)smem);
+      if (e != hipSuccess) return (int)e;
+      attr_bytes = smem;
+    }
+    if (st->B <= wide_max_b)
+      hipLaunchKernelGGL(beam_step_chunked_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse, V,
+                         cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32);
+    else
+      hipLaunchKernelGGL(beam_step_chunked_kernel<256>, dim3(st->B), dim3(256), smem, (hipStream_t)stream, *st, *tr, logits, lse, V,
+                         cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32);
+    GRAM_CHECK_LAUNCH();
+    return 0;
+  }
+  const size_t smem = smem_one;
   static size_t attr_bytes = 0;
   if (smem > attr_bytes) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -680,10 +924,6 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
     if (e != hipSuccess) return (int)e;
     attr_bytes = smem;
   }
-  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
-  // few users: one workgroup per user leaves the chip empty and the step is that workgroup's latency -> 1 024 threads per user
-  // (same per-candidate arithmetic, same total order of the keys: identical results; GRAM_BEAM_WIDE_MAXB: A/B hook, 0 = never)
-  static const int wide_max_b = getenv("GRAM_BEAM_WIDE_MAXB") ? atoi(getenv("GRAM_BEAM_WIDE_MAXB")) : 128;
   // a handful of users: the sparse logits by their own kernel over many CUs (sparse_logits_kernel), the search step reads them
   // (gram_beam_state_t.cand_logits: caller-provided scratch; GRAM_BEAM_PRE_MAXB: A/B hook, 0 = never)
   static const int pre_max_b = getenv("GRAM_BEAM_PRE_MAXB") ? atoi(getenv("GRAM_BEAM_PRE_MAXB")) : 16;

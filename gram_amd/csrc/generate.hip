@@ -147,7 +147,7 @@ Workspace carve(const gram_model* m, void* ws, int B, int N, int L, int K, int T
   s.hyp_len = cv.take<int32_t>((int64_t)B * (K + 1));
   s.hyp_tok = cv.take<int32_t>((int64_t)B * (K + 1) * Tmax);
   s.error = cv.take<int32_t>(4);
-  // scratch of the small-batch sparse-logits kernel (gram_beam_state_t.cand_logits): 16 384 >= any K * max_fanout the search accepts
+  // scratch of the small-batch sparse-logits kernel (gram_beam_state_t.cand_logits): 16 384 >= any K * max_fanout of the one-shot search step (wider steps stream: no scratch)
   s.cand_logits_users = B < 16 ? B : 16;
   s.cand_logits_stride = 16384;
   s.cand_logits = cv.take<float>((int64_t)s.cand_logits_users * s.cand_logits_stride);
@@ -651,7 +651,6 @@ extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids,
     if (comp->n_cached > 0 && (!comp->cache_x || !comp->cache_slot || comp->cache_L < 1)) return GRAM_E_ARG;
   }
   if (!trie || nret < 1 || nret > K || !sequences || (!scores && K != 1)) return GRAM_E_ARG;
-  if ((long long)K * trie->max_fanout > 16384) return GRAM_E_ARG;
   Workspace w = carve(m, workspace, B, N, L, K, max_length);
   if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
   w.beam.length_penalty = length_penalty;

@@ -568,7 +568,8 @@ class GRAM(nn.Module):
         if need < 0:
             raise _lib.GramHipError(
                 f"unsupported problem size B={B} N={N} L={L} K={K} max_length={max_length} "
-                f"(N <= max_item_num+1, L <= 128, K <= 64, max_length <= {_lib.GRAM_MAX_DEC_LEN})"
+                f"(N <= max_item_num+1, L <= 128, K <= 64, max_length <= {_lib.GRAM_MAX_DEC_LEN}; "
+                f"the Trie's fan-out is not limited)"
             )
         return self._ensure_workspace(need)
 
@@ -932,8 +933,8 @@ class GRAM(nn.Module):
                 toks += sorted(set(int(x) for x in l))
                 off.append(len(toks))
             fan = max((off[i + 1] - off[i] for i in range(1, len(off) - 1)), default=0)
-            if K * max(fan, 1) > 16384:
-                raise _lib.GramHipError("prefix_allowed_tokens_fn returned too many tokens for the on-chip candidate sort")
+            if fan > V:  # (a set of token ids: only ids outside the vocabulary can get here)
+                raise _lib.GramHipError("prefix_allowed_tokens_fn returned more tokens than the vocabulary holds")
             a = torch.tensor(off, **i32)
             b = torch.tensor(toks or [0], **i32)
             c = torch.full((max(len(toks), 1),), -1, **i32)

@@ -232,7 +232,10 @@ typedef struct {
   const int32_t* child_off;
   const int32_t* child_tok;
   const int32_t* child_node;
-  int32_t n_nodes, n_edges, max_fanout;
+  int32_t n_nodes, n_edges, max_fanout; /* max_fanout: the largest child count of a node, <= the vocabulary; any value is supported.
+                                           The search step holds all K * max_fanout candidates of a user on chip at once while
+                                           K * max_fanout <= 16 384 (and they fit the LDS beside the call's [K][Tmax] tables),
+                                           and streams them through a fixed-size array beyond that: the same results either way */
   int32_t min_seq_len; /* shortest candidate sequence, start token and EOS included; 0 = unknown (gram_generate then
                           never tries the live-row compaction below) */
 } gram_trie_t;
@@ -259,7 +262,9 @@ typedef struct {
   /* optional scratch (NULL / 0 = off): with B <= cand_logits_users (and <= 16) users a sparse search step computes its candidates'
    * logits with a kernel of its own over many CUs before the per-user search kernel runs -- one workgroup per user pulls up to
    * K * fan-out lm_head rows through ONE CU, most of a one-user step.  f32 [cand_logits_users][cand_logits_stride],
-   * cand_logits_stride >= the power of two >= K * max_fanout.  Same values either way. */
+   * cand_logits_stride >= the power of two >= K * max_fanout.  Same values either way.  Used by the one-shot search step only
+   * (K * max_fanout <= 16 384, gram_trie_t): a wider step streams its candidates and computes their logits itself, so the scratch
+   * never has to be larger than [16][16 384]. */
   float* cand_logits;
   int32_t cand_logits_users;
   int64_t cand_logits_stride;
@@ -555,6 +560,14 @@ int gram_debug_stream_read_variant(const void* src, size_t bytes, void* sink, in
 /* A/B hook (bench.py): 0 = decode every row in every step like the reference, 1 = live-row compaction (gram_live_rows_t),
  * -1 = what the GRAM_LIVE_ROWS environment variable says (default 1).  Results are bit-identical either way. */
 int gram_debug_set_live_rows(int on);
+/* A/B hook (tests/bench_wide_trie.py): which form of the Trie-constrained search step runs.  -1 (default) and 0 = by shape: the
+ * one-shot kernel where all K * max_fanout candidates fit on chip, the chunked kernel otherwise; 1 = always the chunked kernel.
+ * Results are bit-identical either way.  Process-wide. */
+int gram_debug_set_beam_chunked(int mode);
+/* TEST hook: the chunked search step takes at most `candidates` fresh candidates per selection round (0 = default: what its key
+ * array holds, 4 096 - P, P = the power of two >= 2K, >= 64), so that chunk boundaries are reachable with small Tries.  Results do
+ * not depend on it.  Process-wide. */
+int gram_debug_set_beam_chunk_capacity(int candidates);
 /* Sensitivity sweeps over the split modes (tests/precision_population.py --sweep): stage s of a generate() computes on the first
  * caps[s] pieces of its operands only (the upper pieces of its activation operands are zeroed before use; the caller zeroes the
  * upper pieces of that stage's weights when it expands them).  caps NULL = no caps.  n must be GRAM_STAGE_COUNT. */
