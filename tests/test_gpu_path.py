@@ -488,3 +488,51 @@ def test_generic_callback_matches_trie_fast_path(gpu):
     assert torch.equal(slow["sequences"].cpu(), fast["sequences"].cpu())
     # dense logits + row LSE vs sparse logits + fused LSE partials: same values up to fp32 summation order
     assert torch.allclose(slow["sequences_scores"].cpu(), fast["sequences_scores"].cpu(), atol=2e-5)
+
+
+def test_unfolded_norm_path_vs_oracle_and_the_folded_path(gpu, monkeypatch):
+    """GRAM_FOLD_NORM=0 at one piece per value: separate norm kernels in front of every consumer GEMM instead of the norm folded into
+    the GEMMs (generate.hip NormChain; INTEGRATION.md's A/B and debugging path).  The smoke shape, generate / forward(labels) /
+    score_sequences, against the oracle within the one-piece tolerances the folded path is held to (sequence scores 0.01 as smoke();
+    token log-probs, the loss and sequence sums as tests/test_gpu_teacher_forced.py), and against the folded path within the same."""
+    from gram_amd.utils import generation_trie as gt
+    from tests import tf_oracle as TF
+    LOGP_TOL = LOSS_TOL = 2e-2
+    B, N, L, K, C, T = 2, 3, 32, 4, 3, 4
+    oc, _ = _cfgs("tiny")
+    g = torch.Generator().manual_seed(1)
+    ids = torch.randint(2, 256, (B, N, L), generator=g)
+    mask = torch.ones(B, N, L, dtype=torch.bool)
+    mask[:, :, 20:] = False
+    ids[:, :, 20:] = 0
+    cands = [[0, a, b, c, 1] for a in (2, 3, 4) for b in (5, 6, 7) for c in (8, 9)]
+    lab = torch.randint(2, 256, (B, C, T), generator=g)
+    lab[:, 1, 3:] = -100
+    got = {}
+    for fold in ("0", "1"):
+        monkeypatch.setenv("GRAM_FOLD_NORM", fold)  # read when the model packs its weights
+        _, sd, m = _model(gpu, "tiny", 11)
+        m.set_precision("f16" if F16 else "bf16")
+        if not got:
+            ref = O.generate(sd, oc, ids, mask, 5, O.prefix_allowed_tokens_fn(O.Trie(cands)), K, K, 1.0)
+            ref_logits = TF.teacher_forced_logits(sd, oc, ids, mask, TF.shift_right(lab.view(B * C, T)))
+            _, ref_tok = TF.loss_and_token_logp(ref_logits, lab.view(B * C, T))
+            ref_loss, _ = TF.loss_and_token_logp(ref_logits.view(B, C, T, -1)[:, 0], lab[:, 0])
+        out = _gen(m, ids, mask, 5, gt.prefix_allowed_tokens_fn(gt.Trie(cands)), K)
+        _check_generate(oc, sd, out, ref, ids, mask, cands, K, tol=0.01)
+        with torch.no_grad():
+            loss = float(m(input_ids=ids.to(DEV), attention_mask=mask.to(DEV), labels=lab[:, 0].to(DEV)).loss)
+        seq, tok = m.score_sequences(ids.to(DEV), mask.to(DEV), lab.to(DEV), return_tokens=True)
+        seq, tok = seq.cpu().view(-1).double(), tok.cpu().view(B * C, T).double()
+        dt, ds = float((tok - ref_tok).abs().max()), float((seq - ref_tok.sum(-1)).abs().max())
+        rel = abs(loss - float(ref_loss)) / abs(float(ref_loss))
+        print(f"fold_norm={fold}: token logp {dt:.2e}, sequence sums {ds:.2e}, loss rel {rel:.2e}")
+        assert dt < LOGP_TOL and ds < LOGP_TOL * T and rel < LOSS_TOL
+        scores = {(i // K, tuple(s.tolist())): float(v) for i, (s, v) in enumerate(zip(out["sequences"].cpu(), out["sequences_scores"].cpu()))}
+        got[fold] = (scores, tok, seq, loss)
+    (s0, tok0, seq0, loss0), (s1, tok1, seq1, loss1) = got["0"], got["1"]
+    shared = set(s0) & set(s1)
+    d_score = max(abs(s0[k] - s1[k]) for k in shared)
+    dt, ds, rel = float((tok0 - tok1).abs().max()), float((seq0 - seq1).abs().max()), abs(loss0 - loss1) / abs(loss1)
+    print(f"unfolded vs folded: {len(shared)}/{B * K} shared sequences, scores {d_score:.2e}, token logp {dt:.2e}, sums {ds:.2e}, loss rel {rel:.2e}")
+    assert len(shared) >= B and d_score < 0.01 and dt < LOGP_TOL and ds < LOGP_TOL * T and rel < LOSS_TOL

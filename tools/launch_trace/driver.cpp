@@ -1,0 +1,133 @@
+// launch_trace <case>: prints the launch train of one call into the C ABI of generate.hip on a tiny model (vocab 256, d 128, d_ff 256,
+// 2 heads, 2 + 2 layers), recorded by stub.cpp.  launch_trace --list names the cases.  tests/test_launch_train.py compares every
+// case with tests/golden/launch_train/<case>.txt.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+
+#include "../../include/gram_hip.h"
+
+extern char* g_ws;
+extern int64_t g_ws_bytes;
+extern std::vector<int> g_live_script;
+void trace_line(const char* name, int64_t v);
+
+namespace {
+// every pointer that is not in the workspace (weights, inputs, outputs, the stream) is a fixed fake address, 16 MiB from the last
+uintptr_t g_next = 0x100000000;
+template <class T = void>
+T* fake() {
+  g_next += 0x1000000;
+  return (T*)g_next;
+}
+
+enum Entry { GENERATE, ENCODE_FUSED, ENCODE_PASSAGES, DECODE_STEP, TEACHER_FORCED };
+enum Live { OFF, NONE, SOME, ALL };  // live rows off, or on with gram_live_rows reporting no row, some rows, every row
+struct Case {
+  const char* name;
+  Entry entry;
+  int pieces, fold, B, N, L, K, T;  // K: beams, or sequences per user of the teacher-forced pass; T: max_length
+  Live live;
+  bool comp, capped, logits;  // a gram_compaction_t with cached passages; every stage capped to one piece; teacher-forced logits stored
+};
+const Case kCases[] = {
+    {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
+    {"generate_p1_unfolded", GENERATE, 1, 0, 2, 3, 32, 4, 4, SOME},
+    {"generate_p2", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME},
+    {"generate_p2_capped", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, true},
+    {"generate_greedy", GENERATE, 1, 1, 2, 3, 32, 1, 4, SOME},
+    {"generate_rows_640", GENERATE, 1, 1, 40, 1, 32, 16, 4, SOME},       // 512 < rows < 32 768: neither quarter nor pre_rs
+    {"generate_rows_32768", GENERATE, 1, 1, 1024, 1, 32, 32, 4, ALL},    // pre_rs in the encoder and in the decoder (every row live)
+    {"generate_live_off", GENERATE, 1, 1, 2, 3, 32, 4, 4, OFF},
+    {"generate_live_none", GENERATE, 1, 1, 2, 3, 32, 4, 4, NONE},
+    {"generate_live_all", GENERATE, 1, 1, 2, 3, 32, 4, 4, ALL},
+    {"generate_comp", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, true},
+    {"encode_fused", ENCODE_FUSED, 1, 1, 2, 3, 32, 4, 4},
+    {"encode_passages", ENCODE_PASSAGES, 1, 1, 6, 1, 32, 1, 2},
+    {"decode_step", DECODE_STEP, 1, 1, 2, 3, 32, 4, 4},
+    {"tf_folded", TEACHER_FORCED, 1, 1, 2, 3, 32, 3, 4},
+    {"tf_folded_logits", TEACHER_FORCED, 1, 1, 2, 3, 32, 3, 4, OFF, false, false, true},
+    {"tf_folded_comp", TEACHER_FORCED, 1, 1, 2, 3, 32, 3, 4, OFF, true},
+    {"tf_folded_comp_logits", TEACHER_FORCED, 1, 1, 2, 3, 32, 3, 4, OFF, true, false, true},
+    {"tf_unfolded", TEACHER_FORCED, 1, 0, 2, 3, 32, 3, 4},
+    {"tf_unfolded_logits", TEACHER_FORCED, 1, 0, 2, 3, 32, 3, 4, OFF, false, false, true},
+    {"tf_unfolded_comp", TEACHER_FORCED, 1, 0, 2, 3, 32, 3, 4, OFF, true},
+    {"tf_unfolded_comp_logits", TEACHER_FORCED, 1, 0, 2, 3, 32, 3, 4, OFF, true, false, true},
+    {"tf_p2", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4},
+};
+
+gram_model_t* make_model(int pieces, int fold) {
+  enum { NL = 2 };
+  static const float* ln[5][NL];
+  static const void* w[10][NL];
+  static float scales[10 * NL + 2];
+  gram_model_desc_t d{};
+  d.vocab = 256, d.d_model = 128, d.d_ff = 256, d.n_heads = 2, d.n_enc_layers = d.n_dec_layers = NL, d.max_passages = 5;
+  d.tie_word_embeddings = d.use_position_embedding = 1, d.fold_norm = fold, d.eps = 1e-6f, d.pieces = pieces;
+  d.embed_f32 = fake<float>(), d.lm_head_bf16 = fake(), d.pos_emb_f32 = fake<float>(), d.enc_bias_f32 = fake<float>();
+  d.dec_bias_f32 = fake<float>(), d.enc_final_ln = fake<float>(), d.dec_final_ln = fake<float>();
+  d.dec_wkv_x_all = fake(), d.lm_head_f32 = fake<float>();
+  for (auto& a : ln)
+    for (auto& p : a) p = fake<float>();
+  for (auto& a : w)
+    for (auto& p : a) p = fake();
+  for (int i = 0; i < 10 * NL + 2; ++i) scales[i] = (float)(1 << (i + 1));  // a different out_scale for every weight
+  d.enc_ln1 = ln[0], d.enc_ln2 = ln[1], d.dec_ln1 = ln[2], d.dec_ln2 = ln[3], d.dec_ln3 = ln[4];
+  d.enc_wqkv = w[0], d.enc_wo = w[1], d.enc_wi = w[2], d.enc_wo2 = w[3], d.dec_wqkv = w[4], d.dec_wo = w[5];
+  d.dec_wq_x = w[6], d.dec_wo_x = w[7], d.dec_wi = w[8], d.dec_wo2 = w[9];
+  d.w_scales = scales;
+  return gram_model_create(&d);
+}
+
+int run(const Case& c) {
+  gram_model_t* m = make_model(c.pieces, c.fold);
+  if (!m) return GRAM_E_ARG;
+  void* st = fake();
+  const int64_t* ids = fake<int64_t>();
+  const uint8_t* mask = fake<uint8_t>();
+  const gram_compaction_t comp{c.B * c.N - 1, fake<int32_t>(), fake<int64_t>(), fake<uint8_t>(), 2, 16, fake<float>(), fake<int32_t>()};
+  const gram_trie_t trie{fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), 40, 39, 3, /*min_seq_len=*/2};  // live rows from step 1 on
+  const int B = c.B, N = c.N, L = c.L, K = c.K, T = c.T, R = B * K;
+  if (c.capped) {
+    const int32_t caps[GRAM_STAGE_COUNT] = {1, 1, 1, 1, 1, 1, 1, 1};
+    gram_debug_set_stage_pieces(caps, GRAM_STAGE_COUNT);
+  }
+  gram_debug_set_live_rows(c.live != OFF);
+  if (c.live == SOME) g_live_script = {R - 1, B, R / 2, (B + 1) / 2};
+  if (c.live == ALL) g_live_script = {R, B, R, B};
+  trace_line("gram_workspace_bytes", gram_workspace_bytes(m, B, N, L, K, T));
+  trace_line("gram_workspace_bytes_tf", gram_workspace_bytes_tf(m, B, N, L, K, T));
+  trace_line("gram_workspace_encoder_x_offset", gram_workspace_encoder_x_offset(m, B, N, L, K, T));
+  g_ws_bytes = c.entry == TEACHER_FORCED ? gram_workspace_bytes_tf(m, B, N, L, K, T) : gram_workspace_bytes(m, B, N, L, K, T);
+  g_ws = (char*)calloc(g_ws_bytes, 1);  // zeroed, and touched only where a stub writes: a large case costs address space alone
+  int32_t width = -1;
+  void* io[5] = {fake(), fake(), fake(), fake(), fake()};  // the remaining inputs and outputs of the entry, in its argument order
+  switch (c.entry) {
+    case GENERATE:
+      return gram_generate_ex(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, g_ws, g_ws_bytes, (int64_t*)io[0],
+                              (float*)io[1], &width, st);
+    case ENCODE_FUSED:
+      return gram_encode_fused(m, ids, mask, B, N, L, g_ws, g_ws_bytes, K, T, io[0], st);
+    case ENCODE_PASSAGES:
+      return gram_encode_passages(m, ids, mask, B, L, g_ws, g_ws_bytes, (float*)io[0], st);
+    case DECODE_STEP:
+      return gram_decode_step(m, (int32_t*)io[0], (int32_t*)io[1], mask, B, N, L, K, T, /*t=*/1, g_ws, g_ws_bytes, (float*)io[2], st);
+    case TEACHER_FORCED:
+      return gram_teacher_forced(m, ids, mask, B, N, L, c.comp ? &comp : nullptr, (int32_t*)io[0], (int32_t*)io[1], K, T, g_ws, g_ws_bytes,
+                                 c.logits ? (float*)io[2] : nullptr, (float*)io[3], (float*)io[4], st);
+  }
+  return GRAM_E_ARG;
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+  for (const Case& c : kCases) {
+    if (argc == 2 && !strcmp(argv[1], "--list")) puts(c.name);
+    if (argc == 2 && !strcmp(argv[1], c.name)) {
+      trace_line("return", run(c));
+      return 0;
+    }
+  }
+  return argc == 2 && !strcmp(argv[1], "--list") ? 0 : 2;
+}
