@@ -7,23 +7,22 @@
 //     shared by all of the user's beams: algorithmic bytes = 2 * S * 64 * 2 B per (user, head)
 //     and bf16 piece of the bank.
 //
-//     Mapping: one workgroup per (user, head), NW waves (template; 2 for K <= 32, 1 above), wave w owns the valid
-//     32-key steps w, w+NW, ...  A step's K rows (32 x 128 B) and V^T rows (64 x 64 B) of every bf16 piece are brought
-//     into a wave-PRIVATE ring of R stages in LDS by LDS-DMA (global_load_lds, 16 B per lane, no staging registers);
-//     waves never synchronise inside the loop (counted s_waitcnt vmcnt only).  The DMA writes LDS linearly, so the
-//     bank-conflict swizzles are applied to the per-lane SOURCE chunk.  S^T = K Q^T puts a beam on a lane column, so
-//     the online softmax is in-register + two cross-lane steps, and exp(S^T) is directly the B operand of
-//     O^T = V^T P^T (same row-permutation trick as enc_attn.hip).  With NW > 1 the waves merge their (m, l, O)
-//     partials through LDS (aliasing the rings) at the end; with NW = 1 the accumulators are the result.
-//     (NW, R) per shape were measured, see launch_cross_v() and DESIGN.md §4.2.
+//     Mapping: one workgroup per (user, head); two waves for K <= 32, one above (measured: launch_cross()); wave w
+//     owns the valid 32-key steps w, w + NW, ...  A step's K rows (32 x 128 B) and V^T rows (64 x 64 B) of every bf16 piece are
+//     brought into the wave's PRIVATE stage in LDS by LDS-DMA (global_load_lds, 16 B per lane, no staging registers).  There is
+//     ONE stage per wave, consumed and re-filled in halves: the next step's K tiles fly during this step's S^T and softmax, its
+//     V^T tiles during O^T += V^T P^T.  Waves never synchronise inside the loop (counted s_waitcnt vmcnt only).  The DMA writes
+//     LDS linearly, so the bank-conflict swizzles are applied to the per-lane SOURCE chunk.  S^T = K Q^T puts a beam on a lane
+//     column, so the online softmax is in-register + two cross-lane steps, and exp(S^T) is directly the B operand of
+//     O^T = V^T P^T (same row-permutation trick as enc_attn.hip).  Two waves merge their (m, l, O) partials through LDS
+//     (aliasing the stages) at the end; one wave's accumulators are the result.
 //
 // (2) dec_self_attn_kernel: causal self-attention of the newest token over <= 32 cached
 //     positions with beam-parent indirection (anc table) instead of the reference's
 //     torch.cat + index_select of the whole cache (gram_t5_modeling.py:536-540,
 //     gram_t5.py:320-348); unidirectional relative bias, last query row (:586-593).
 //
-// Both kernels take their bf16 operands as 1..3 pieces (gram_split_t in gram_hip.h).
-#include <stdlib.h>
+// Both kernels take their bf16 operands as 1 or 2 pieces (GRAM_MAX_PIECES; gram_split_t in gram_hip.h).
 #include <type_traits>
 
 #include "common.h"
@@ -39,9 +38,6 @@ __device__ __forceinline__ void dma16(uint32_t lds_addr /*wave-uniform*/, uint32
 __device__ __forceinline__ void dma16_nt(uint32_t lds_addr /*wave-uniform*/, uint32_t voff, const char* base /*uniform*/) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory");
 }
-#ifndef GRAM_XA_NT
-#define GRAM_XA_NT 1  // bit 0 = K tiles, bit 1 = V^T tiles fetched with the nt hint (A/B build hook; in the bench, one box: 168.8 ms of cross-attention per step without, 163.3 with K only, 165.7 with both)
-#endif
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -73,24 +69,45 @@ __device__ __forceinline__ f32x4 xa_merge_o(f32x4 o0, f32x4 o1, float w0, float 
   return r;
 }
 
+// row of q / out that holds `beam` of user b: -1 = no such beam, or (live-row step) the beam is not live
+template <bool LIVE>
+__device__ __forceinline__ int xa_row(int b, int K, int beam, const int32_t* __restrict__ rowpos) {
+  int row = beam < K ? b * K + beam : -1;
+  if constexpr (LIVE) {
+    if (row >= 0) row = rowpos[row];
+  }
+  return row;
+}
+// four output columns from n of row `orow`, as S pieces (the plain running remainder: batch invariance depends on these bits)
+template <int S>
+__device__ __forceinline__ void xa_store(p16* __restrict__ out, int orow, int inner, int n, f32x4 v) {
+#pragma unroll
+  for (int pc = 0; pc < S; ++pc) {
+    p16x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      r[e] = (p16)v[e];
+      v[e] -= (float)r[e];
+    }
+    // (S == 2: interleaved rows [2 * inner], the O GEMM's A operand)
+    *reinterpret_cast<p16x4*>(out + (size_t)orow * inner * S + (S == 2 ? inter_off(n, pc) : n)) = r;
+  }
+}
+
 // NT = 16-beam tiles; LIVE: live-row step (gram_live_rows_t); S = bf16 pieces; NW = waves per workgroup (1: a wave owns the whole
-// (user, head) and nothing is merged); R = ring stages per wave
-template <int NT, bool LIVE, int S, int NW, int R>
+// (user, head) and nothing is merged)
+template <int NT, bool LIVE, int S, int NW>
 __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     const p16* __restrict__ q, const p16* __restrict__ kbank, const p16* __restrict__ vtbank,
     const uint8_t* __restrict__ mask, p16* __restrict__ out, int K, int H, int Sk, const int32_t* __restrict__ users,
     const int32_t* __restrict__ rowpos, long q_pstride, long bank_pstride, const uint32_t* __restrict__ key_bits) {
   using T = SplitTab<S>;
   constexpr int NB = NT * 16;                     // padded beams
-  // R == 0: "half slot" -- ONE region per wave that holds a step's K tiles, then (once their fragments are in registers) its V^T tiles,
-  // then the next step's K tiles ...: half the LDS per workgroup, twice the workgroups per CU to cover each other's prologue and merge
-  constexpr bool HALF = R == 0;
-  constexpr int PSTR = HALF ? XA_TILE : 2 * XA_TILE;  // piece stride inside a slot
-  constexpr int VOFF = HALF ? 0 : XA_TILE;           // V^T tiles: behind the K tiles, or in their place
-  constexpr int STAGE = S * PSTR;                     // per wave and ring slot: S x (K tile | V^T tile)
-  constexpr int RING = (HALF ? 1 : R) * STAGE;
+  static_assert(NW == 1 || NW == 2, "the merge is written for two waves");
+  constexpr int PSTR = 2 * XA_TILE;               // piece stride inside the stage: K tile | V^T tile
+  constexpr int STAGE = S * PSTR;                 // per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sm_m = reinterpret_cast<float*>(smem);   // [NW][NB]     (the merge buffers alias the rings)
+  float* sm_m = reinterpret_cast<float*>(smem);   // [NW][NB]     (the merge buffers alias the stages)
   float* sm_l = sm_m + NW * NB;                   // [NW][NB]
   float* sm_o = sm_l + NW * NB;                   // [NW][NB][64]
 
@@ -105,7 +122,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   const char* vt = reinterpret_cast<const char*>(vtbank + ((size_t)b * H + h) * 64 * Sk);
   const uint8_t* mk = mask + (size_t)b * Sk;
 
-  p16x8 qf[S][NT][2];  // query fragments: loaded once the ring is primed (below)
+  p16x8 qf[S][NT][2];  // query fragments
   f32x4 o[4][NT];
   float m[NT], l[NT];
 #pragma unroll
@@ -116,22 +133,17 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     for (int mt = 0; mt < 4; ++mt) o[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
 
-  if constexpr (R <= 1) {
-    // query fragments: requested first, in parallel with the key bits, and retired with them by the wait in front of the ring --
-    // the counted waits of the half-stage loop must see DMA instructions only
+  // query fragments (lane: beam 16 nt + c, dims 32 kd + 8 g ..+7 of the head; zeros for a beam that has no row): requested first, in
+  // parallel with the key bits, and retired with them by the wait in front of the loop -- the counted waits of the loop must see DMA
+  // instructions only
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int beam = 16 * nt + c;
-      int qrow = beam < K ? b * K + beam : -1;
-      if constexpr (LIVE) {
-        if (qrow >= 0) qrow = rowpos[qrow];
-      }
+  for (int nt = 0; nt < NT; ++nt) {
+    const int qrow = xa_row<LIVE>(b, K, 16 * nt + c, rowpos);
 #pragma unroll
-      for (int pc = 0; pc < S; ++pc)
+    for (int pc = 0; pc < S; ++pc)
 #pragma unroll
-        for (int kd = 0; kd < 2; ++kd)
-          qf[pc][nt][kd] = qrow >= 0 ? ld_global_b128(q + pc * q_pstride + (size_t)qrow * inner + h * 64 + 32 * kd + 8 * g) : zero_bf16x8();
-    }
+      for (int kd = 0; kd < 2; ++kd)
+        qf[pc][nt][kd] = qrow >= 0 ? ld_global_b128(q + pc * q_pstride + (size_t)qrow * inner + h * 64 + 32 * kd + 8 * g) : zero_bf16x8();
   }
   // Fully masked 32-key steps (padded passages / padded tails) are never fetched: the algorithmic
   // traffic is proportional to the VALID fused keys.  One word of key bits per step (S <= 4096 -> <= 128 steps);
@@ -190,43 +202,32 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     const int d = 16 * i + (lane >> 2);  // V^T row; position lane & 3
     voff[i] = (uint32_t)(d * 64 + (((lane & 3) ^ vsw(d)) << 4));  // (the bank's V^T is blocked by 32 keys: a step's tile is [64 d][64 B], contiguous)
   }
-  const uint32_t ring0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * RING;
-  // 4 * S DMA instructions each: this step's K tiles / V^T tiles of every piece -> ring slot
-  auto issue_k = [&](int slot, int step) {
-    const uint32_t dst = ring0 + slot * STAGE;
+  const uint32_t stage0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * STAGE;
+  // 4 * S DMA instructions each: this step's K tiles (streaming hint: measured) / V^T tiles of every piece -> the stage
+  auto issue_k = [&](int step) {
+    const uint32_t dst = stage0;  // (a copy local to the lambda, here and in read_k / read_v: hipcc orders the address arithmetic differently without)
 #pragma unroll
     for (int pc = 0; pc < S; ++pc) {
       const char* kbase = kb + (size_t)pc * bank_pstride * 2 + (size_t)step * (32 * 128);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr ((GRAM_XA_NT & 1) != 0) dma16_nt(dst + pc * PSTR + i * 1024, koff[i], kbase);
-        else dma16(dst + pc * PSTR + i * 1024, koff[i], kbase);
-      }
+      for (int i = 0; i < 4; ++i) dma16_nt(dst + pc * PSTR + i * 1024, koff[i], kbase);
     }
   };
-  auto issue_v = [&](int slot, int step) {
-    const uint32_t dst = ring0 + slot * STAGE;
+  auto issue_v = [&](int step) {
+    const uint32_t dst = stage0;  // (local copy: see issue_k)
 #pragma unroll
     for (int pc = 0; pc < S; ++pc) {
       const char* vbase = vt + (size_t)pc * bank_pstride * 2 + (size_t)step * 4096;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr ((GRAM_XA_NT & 2) != 0) dma16_nt(dst + pc * PSTR + VOFF + i * 1024, voff[i], vbase);
-        else dma16(dst + pc * PSTR + VOFF + i * 1024, voff[i], vbase);
-      }
+      for (int i = 0; i < 4; ++i) dma16(dst + pc * PSTR + XA_TILE + i * 1024, voff[i], vbase);
     }
   };
-  auto issue = [&](int slot, int step) {
-    issue_k(slot, step);
-    issue_v(slot, step);
-  };
   const int krow = 8 * (c >> 2) + (c & 3);  // + 4t: key row of S^T tile t this lane feeds
-  // A stage is consumed in two phases: read_frags pulls every K and V^T fragment of the step out of the ring slot into registers, and
-  // once those reads have returned the slot is re-filled (the next step's DMAs are in flight during the whole of `math`, which
-  // works on registers only) -- with one stage per wave and the issue after the math, a wave had nothing in flight while it computed.
+  // the step's K / V^T fragments, pulled out of the stage into registers: the arithmetic works on registers only, so a half of the
+  // stage is re-filled as soon as its reads have returned
   p16x8 kf[S][2][2], vf[S][4];
-  auto read_k = [&](int slot) {
-    const char* stg = smem + wave * RING + slot * STAGE;
+  auto read_k = [&]() {
+    const char* stg = smem + wave * STAGE;  // (local to the lambda: see issue_k)
 #pragma unroll
     for (int pc = 0; pc < S; ++pc)
 #pragma unroll
@@ -237,19 +238,15 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
           kf[pc][t][kd] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + r * 128 + (((g + 4 * kd) ^ ksw(r)) << 4));
         }
   };
-  auto read_v = [&](int slot) {
-    const char* stg = smem + wave * RING + slot * STAGE;
+  auto read_v = [&]() {
+    const char* stg = smem + wave * STAGE;  // (local to the lambda: see issue_k)
 #pragma unroll
     for (int pc = 0; pc < S; ++pc)
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
         const int d = 16 * mt + c;
-        vf[pc][mt] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + VOFF + d * 64 + ((g ^ vsw(d)) << 4));
+        vf[pc][mt] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + XA_TILE + d * 64 + ((g ^ vsw(d)) << 4));
       }
-  };
-  auto read_frags = [&](int slot) {
-    read_k(slot);
-    read_v(slot);
   };
   p16x8 pf[S][NT];  // exp(S^T - max) of the step, as pieces: the B operand of O^T += V^T P^T
   auto math_qk = [&](int step) {
@@ -308,137 +305,43 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
 #pragma unroll
         for (int pr = 0; pr < T::NP; ++pr) o[mt][nt] = mfma16(vf[T::A[pr]][mt], pf[T::B[pr]][nt], o[mt][nt]);
   };
-  auto math = [&](int step) {
-    math_qk(step);
-    math_pv();
-  };
 
-  // Everything the first DMAs depend on (the key bits) is in; ordinary loads are retired so that the counted waits below see
-  // DMA instructions only.  The query fragments are loaded AFTER the ring is primed: their latency hides behind the first stages
-  // (hipcc waits for them with vmcnt(0) at their first use, which the first stage has to reach anyway).
+  // Everything the first DMAs depend on (the key bits) is in; ordinary loads, the query fragments among them, are retired so that the
+  // counted waits below see DMA instructions only.
   wait_vm<0>();
-  if constexpr (HALF) {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
+  for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-      for (int pc = 0; pc < S; ++pc)
+    for (int pc = 0; pc < S; ++pc)
 #pragma unroll
-        for (int kd = 0; kd < 2; ++kd) asm volatile("" : "+v"(qf[pc][nt][kd]));
-    // half slot: K(s) -> fragments -> V(s) into the same region (in flight during S^T / softmax) -> fragments -> K(s+1) (in flight during
-    // O^T += V^T P^T) ...: one half-stage in flight per wave, twice the waves per CU
-    int cur = next(-1);
-    if (cur < nsteps) issue_k(0, cur);
-    while (cur < nsteps) {
-      const int nxt = next(cur);
-      wait_vm<0>();
-      read_k(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the K fragments are in registers before the region is re-filled
-      issue_v(0, cur);
-      math_qk(cur);
-      wait_vm<0>();
-      read_v(0);
+      for (int kd = 0; kd < 2; ++kd) asm volatile("" : "+v"(qf[pc][nt][kd]));  // (hipcc's own wait for the loads goes HERE)
+  // One stage per wave, consumed and re-filled in HALVES: the K tiles of step s+1 are requested as soon as the K fragments of step
+  // s are in registers (and fly during S^T, softmax), its V^T tiles as soon as the V^T fragments of step s are (and fly during
+  // O^T += V^T P^T and the next S^T): the wave always has a half-stage in flight, where waiting for the whole stage and
+  // re-filling it after the reads left nothing in flight for a few hundred cycles of every step.
+  int cur = next(-1);
+  if (cur < nsteps) {
+    issue_k(cur);
+    issue_v(cur);
+  }
+  while (cur < nsteps) {
+    const int nxt = next(cur);
+    wait_vm<4 * S>();  // all but the newest half-stage (this step's V^T tiles): its K tiles have landed
+    read_k();
+    if (nxt < nsteps) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the K fragments are in registers before their tiles are re-filled
+      issue_k(nxt);
+    }
+    math_qk(cur);
+    if (nxt < nsteps) wait_vm<4 * S>();  // (newest: the next step's K tiles)
+    else wait_vm<0>();
+    read_v();
+    if (nxt < nsteps) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (nxt < nsteps) issue_k(0, nxt);
-      math_pv();
-      cur = nxt;
+      issue_v(nxt);
     }
-  } else if constexpr (R == 1) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int pc = 0; pc < S; ++pc)
-#pragma unroll
-        for (int kd = 0; kd < 2; ++kd) asm volatile("" : "+v"(qf[pc][nt][kd]));  // (hipcc's own wait for the loads goes HERE)
-    // One stage per wave, consumed and re-filled in HALVES: the K tiles of step s+1 are requested as soon as the K fragments of step
-    // s are in registers (and fly during S^T, softmax), its V^T tiles as soon as the V^T fragments of step s are (and fly during
-    // O^T += V^T P^T and the next S^T): the wave always has a half-stage in flight, where waiting for the whole stage and
-    // re-filling it after the reads left nothing in flight for a few hundred cycles of every step.
-    int cur = next(-1);
-    if (cur < nsteps) issue(0, cur);
-    while (cur < nsteps) {
-      const int nxt = next(cur);
-      wait_vm<4 * S>();  // all but the newest half-stage (this step's V^T tiles): its K tiles have landed
-      read_k(0);
-      if (nxt < nsteps) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the K fragments are in registers before their tiles are re-filled
-        issue_k(0, nxt);
-      }
-#ifndef GRAM_XA_NOMATH
-      math_qk(cur);
-#endif
-      if (nxt < nsteps) wait_vm<4 * S>();  // (newest: the next step's K tiles)
-      else wait_vm<0>();
-      read_v(0);
-      if (nxt < nsteps) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        issue_v(0, nxt);
-      }
-#ifndef GRAM_XA_NOMATH
-      math_pv();
-#else
-      o[0][0][0] += (float)kf[0][0][0][0] + (float)vf[0][0][0];
-#endif
-      cur = nxt;
-    }
-  } else if constexpr (R >= 2) {
-    // ring of R stages: rq[i] = step held by slot i; `head` is the oldest.  All scalar state.
-    int rq[R];
-    int head = 0, inflight = 0, last = -1;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      rq[i] = nsteps;
-      if (last < nsteps) {
-        last = next(last);
-        if (last < nsteps) {
-          rq[i] = last;
-          issue(i, last);
-          ++inflight;
-        }
-      }
-    }
-    // (query loads)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int beam = 16 * nt + c;
-      int qrow = beam < K ? b * K + beam : -1;
-      if constexpr (LIVE) {
-        if (qrow >= 0) qrow = rowpos[qrow];
-      }
-  #pragma unroll
-      for (int pc = 0; pc < S; ++pc)
-  #pragma unroll
-        for (int kd = 0; kd < 2; ++kd)
-          qf[pc][nt][kd] = qrow >= 0 ? ld_global_b128(q + pc * q_pstride + (size_t)qrow * inner + h * 64 + 32 * kd + 8 * g) : zero_bf16x8();
-    }
-
-    while (inflight > 0) {
-      // all but the (inflight - 1) newer stages' DMAs have landed: the head stage is complete
-      switch (inflight - 1) {
-        case 0: wait_vm<0>(); break;
-        case 1: wait_vm<8 * S>(); break;
-        case 2: wait_vm<(R > 2 ? 16 * S : 0)>(); break;
-        default: wait_vm<(R > 3 ? 24 * S : 0)>(); break;
-      }
-      int cur = rq[0];
-#pragma unroll
-      for (int i = 1; i < R; ++i) cur = head == i ? rq[i] : cur;
-      read_frags(head);
-      --inflight;
-      if (last < nsteps) last = next(last);
-      if (last < nsteps) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this slot's fragment reads have returned before it is re-filled
-        issue(head, last);
-#pragma unroll
-        for (int i = 0; i < R; ++i) rq[i] = head == i ? last : rq[i];
-        ++inflight;
-      }
-#ifndef GRAM_XA_NOMATH
-      math(cur);
-#else
-      o[0][0][0] += (float)kf[0][0][0][0] + (float)vf[0][0][0];  // (probe build: the stream without the arithmetic)
-#endif
-      head = head + 1 == R ? 0 : head + 1;
-    }
+    math_pv();
+    cur = nxt;
   }
 
   if constexpr (NW == 1) {
@@ -449,32 +352,15 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
       lt += __shfl_xor(lt, 16, 64);
       lt += __shfl_xor(lt, 32, 64);
       const float inv = 1.f / lt;
-      const int beam = 16 * nt + c;
-      int orow = beam < K ? b * K + beam : -1;
-      if constexpr (LIVE) {
-        if (orow >= 0) orow = rowpos[orow];
-      }
+      const int orow = xa_row<LIVE>(b, K, 16 * nt + c, rowpos);
       if (orow >= 0) {
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          f32x4 v = o[mt][nt] * inv;
-#pragma unroll
-          for (int pc = 0; pc < S; ++pc) {
-            p16x4 r;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              r[e] = (p16)v[e];
-              v[e] -= (float)r[e];
-            }
-            const int n = h * 64 + 16 * mt + 4 * g;  // (S == 2: interleaved rows [2 * inner], the O GEMM's A operand)
-            *reinterpret_cast<p16x4*>(out + (size_t)orow * inner * S + (S == 2 ? inter_off(n, pc) : n)) = r;
-          }
-        }
+        for (int mt = 0; mt < 4; ++mt) xa_store<S>(out, orow, inner, h * 64 + 16 * mt + 4 * g, o[mt][nt] * inv);
       }
     }
     return;
   }
-  // merge the waves' partials (the rings are dead once every wave is past its loop)
+  // merge the two waves' partials (the stages are dead once both waves are past their loops)
   gram_sync();
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
@@ -493,169 +379,65 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   gram_sync();
   for (int idx = tid; idx < K * 16; idx += NW * 64) {
     const int beam = idx >> 4, d4 = (idx & 15) * 4;
-    if constexpr (NW == 2) {
-      float w0, w1, inv2;
-      xa_merge_w(sm_m[beam], sm_m[NB + beam], sm_l[beam], sm_l[NB + beam], w0, w1, inv2);
-      f32x4 v = xa_merge_o(*reinterpret_cast<const f32x4*>(sm_o + ((size_t)beam) * 64 + d4),
-                           *reinterpret_cast<const f32x4*>(sm_o + ((size_t)(NB + beam)) * 64 + d4), w0, w1, inv2);
-      int orow = b * K + beam;
-      if constexpr (LIVE) orow = rowpos[orow];
-      if (orow >= 0) {
-#pragma unroll
-        for (int pc = 0; pc < S; ++pc) {
-          p16x4 r;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            r[e] = (p16)v[e];
-            v[e] -= (float)r[e];
-          }
-          const int n = h * 64 + d4;
-          *reinterpret_cast<p16x4*>(out + (size_t)orow * inner * S + (S == 2 ? inter_off(n, pc) : n)) = r;
-        }
-      }
-      continue;
-    }
-    float M = GRAM_FMIN;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) M = fmaxf(M, sm_m[w * NB + beam]);
-    float Lsum = 0.f;
-    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float wgt = __expf(sm_m[w * NB + beam] - M);
-      Lsum += sm_l[w * NB + beam] * wgt;
-      acc += *reinterpret_cast<const f32x4*>(sm_o + ((size_t)(w * NB + beam)) * 64 + d4) * wgt;
-    }
-    const float inv = 1.f / Lsum;
-    f32x4 v = acc * inv;
-    int orow = b * K + beam;
+    float w0, w1, inv2;
+    xa_merge_w(sm_m[beam], sm_m[NB + beam], sm_l[beam], sm_l[NB + beam], w0, w1, inv2);
+    const f32x4 v = xa_merge_o(*reinterpret_cast<const f32x4*>(sm_o + ((size_t)beam) * 64 + d4),
+                         *reinterpret_cast<const f32x4*>(sm_o + ((size_t)(NB + beam)) * 64 + d4), w0, w1, inv2);
+    int orow = b * K + beam;  // (beam < K here; through xa_row() hipcc keeps the comparison and reschedules the merge)
     if constexpr (LIVE) orow = rowpos[orow];
-    if (orow >= 0) {
-#pragma unroll
-      for (int pc = 0; pc < S; ++pc) {
-        p16x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          r[e] = (p16)v[e];
-          v[e] -= (float)r[e];
-        }
-        const int n = h * 64 + d4;
-        *reinterpret_cast<p16x4*>(out + (size_t)orow * inner * S + (S == 2 ? inter_off(n, pc) : n)) = r;
-      }
-    }
+    if (orow >= 0) xa_store<S>(out, orow, inner, h * 64 + d4, v);
   }
 }
 
+// host side of one cross-attention launch
+struct XaLaunch {
+  const void *q, *k, *vt;
+  const uint8_t* mask;
+  void* out;
+  int B, K, H, Sk;
+  const int32_t *users, *rowpos;
+  long q_ps, bank_ps;
+  const uint32_t* key_bits;
+  hipStream_t st;
+};
 
-template <int NT, int S, int NW, int R>
-int launch_cross(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int B, int K, int H, int Sk,
-                 const int32_t* users, const int32_t* rowpos, long q_ps, long bank_ps, const uint32_t* key_bits, hipStream_t st) {
+// Two waves per (user, head) for one or two beam tiles, one wave for three or four (K > 32: the per-workgroup state is larger), ONE
+// stage per wave: many small workgroups per CU hide the per-workgroup prologue and merge better than deeper rings or more waves do.
+// Every alternative that was measured: DESIGN.md §4.2.
+template <int NT, int S>
+int launch_cross(const XaLaunch& a) {
+  constexpr int NW = NT >= 3 ? 1 : 2;
   constexpr int NB = NT * 16;
-  constexpr int ring = NW * (R == 0 ? S * XA_TILE : R * S * 2 * XA_TILE), merge = NW == 1 ? 0 : (2 * NW * NB + NW * NB * 64) * 4;
-  constexpr int smem = ring > merge ? ring : merge;
-  static_assert(smem <= 160 * 1024, "ring does not fit the LDS");
+  constexpr int stages = NW * S * 2 * XA_TILE, merge = NW == 1 ? 0 : (2 * NW * NB + NW * NB * 64) * 4;
+  constexpr int smem = stages > merge ? stages : merge;
+  static_assert(smem <= 160 * 1024, "the stages do not fit the LDS");
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_kernel<NT, false, S, NW, R>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_kernel<NT, false, S, NW>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_kernel<NT, true, S, NW, R>),
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_kernel<NT, true, S, NW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
-  if (users)
-    hipLaunchKernelGGL((cross_attn_kernel<NT, true, S, NW, R>), dim3(H, B), dim3(NW * 64), smem, st, (const p16*)q, (const p16*)k,
-                       (const p16*)vt, mask, (p16*)out, K, H, Sk, users, rowpos, q_ps, bank_ps, key_bits);
+  if (a.users)
+    hipLaunchKernelGGL((cross_attn_kernel<NT, true, S, NW>), dim3(a.H, a.B), dim3(NW * 64), smem, a.st, (const p16*)a.q, (const p16*)a.k,
+                       (const p16*)a.vt, a.mask, (p16*)a.out, a.K, a.H, a.Sk, a.users, a.rowpos, a.q_ps, a.bank_ps, a.key_bits);
   else
-    hipLaunchKernelGGL((cross_attn_kernel<NT, false, S, NW, R>), dim3(H, B), dim3(NW * 64), smem, st, (const p16*)q, (const p16*)k,
-                       (const p16*)vt, mask, (p16*)out, K, H, Sk, users, rowpos, q_ps, bank_ps, key_bits);
+    hipLaunchKernelGGL((cross_attn_kernel<NT, false, S, NW>), dim3(a.H, a.B), dim3(NW * 64), smem, a.st, (const p16*)a.q, (const p16*)a.k,
+                       (const p16*)a.vt, a.mask, (p16*)a.out, a.K, a.H, a.Sk, a.users, a.rowpos, a.q_ps, a.bank_ps, a.key_bits);
   GRAM_CHECK_LAUNCH();
   return 0;
 }
 
-// Waves per workgroup and ring depth per piece count (measured, profiles/r02_cross_attn_variants.json); GRAM_XA_VARIANT = 10*NW + R
-// selects one of the other instantiated shapes for an A/B run.
-#ifndef GRAM_XA_AB
-#define GRAM_XA_AB 0
-#endif
-template <int NT, int S>
-int launch_cross_v(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int B, int K, int H, int Sk,
-                   const int32_t* users, const int32_t* rowpos, long q_ps, long bank_ps, const uint32_t* key_bits, hipStream_t st) {
-#define XA_ARGS q, k, vt, mask, out, B, K, H, Sk, users, rowpos, q_ps, bank_ps, key_bits, st
-#if GRAM_XA_AB
-  static const int v = getenv("GRAM_XA_VARIANT") ? atoi(getenv("GRAM_XA_VARIANT")) : 0;
-  if constexpr (NT == 2 && S == 1) {
-    switch (v) {
-      case 22: return launch_cross<NT, S, 2, 2>(XA_ARGS);
-      case 23: return launch_cross<NT, S, 2, 3>(XA_ARGS);
-      case 24: return launch_cross<NT, S, 2, 4>(XA_ARGS);
-      case 43: return launch_cross<NT, S, 4, 3>(XA_ARGS);
-      case 11: return launch_cross<NT, S, 1, 1>(XA_ARGS);
-      case 12: return launch_cross<NT, S, 1, 2>(XA_ARGS);
-      case 13: return launch_cross<NT, S, 1, 3>(XA_ARGS);
-      case 14: return launch_cross<NT, S, 1, 4>(XA_ARGS);
-      case 21: return launch_cross<NT, S, 2, 1>(XA_ARGS);
-      default: break;
-    }
-  }
-  if constexpr (NT == 4 && S <= 2) {
-    switch (v) {
-      case 11: return launch_cross<NT, S, 1, 1>(XA_ARGS);
-      case 12: return launch_cross<NT, S, 1, 2>(XA_ARGS);
-      case 22: return launch_cross<NT, S, 2, 2>(XA_ARGS);
-      case 41: return launch_cross<NT, S, 4, 1>(XA_ARGS);
-      case 42: return launch_cross<NT, S, 4, 2>(XA_ARGS);
-      default: break;
-    }
-  }
-  if constexpr (NT == 2 && S == 2) {
-    switch (v) {
-      case 42: return launch_cross<NT, S, 4, 2>(XA_ARGS);
-      case 22: return launch_cross<NT, S, 2, 2>(XA_ARGS);
-      case 23: return launch_cross<NT, S, 2, 3>(XA_ARGS);
-      case 11: return launch_cross<NT, S, 1, 1>(XA_ARGS);
-      case 12: return launch_cross<NT, S, 1, 2>(XA_ARGS);
-      case 13: return launch_cross<NT, S, 1, 3>(XA_ARGS);
-      case 14: return launch_cross<NT, S, 1, 4>(XA_ARGS);
-      case 21: return launch_cross<NT, S, 2, 1>(XA_ARGS);
-      case 20: return launch_cross<NT, S, 2, 0>(XA_ARGS);
-      case 10: return launch_cross<NT, S, 1, 0>(XA_ARGS);
-      case 40: return launch_cross<NT, S, 4, 0>(XA_ARGS);
-      default: break;
-    }
-  }
-#endif
-  // two waves per (user, head), ONE stage each: many small workgroups per CU hide the per-workgroup prologue / merge better than
-  // deep rings do (in-run A/B at the bench shape, tests/bench_xattn.py: (NW, R) = (2, 1) 5.29 / 5.43 TB/s for 1 / 2 pieces against
-  // (1, 2) 5.11 / 5.21, (2, 2) 5.21 / 4.84, (4, 2) 4.49 / 3.88 on the same box)
-  // (three or four beam tiles, K > 32: the per-workgroup state is larger and one wave per (user, head) with two stages wins --
-  // K = 50, S = 2 688, H = 16: (1, 2) 4.32 / 5.28 TB/s against (2, 1) 3.93 / 4.99, (2, 2) 4.08 / 4.95, (4, 1) 3.66 / 4.75)
-  // (a ring of 3 stages per wave for grids of a handful of users was measured too: 12.42 -> 12.67 ms per one-user generate, no gain)
-  // (round 3, R = 0 "half slot": one 8-KB region per wave for a step's K tiles, then its V^T tiles -- half the LDS, twice the workgroups per
-  // CU: (2, 0) 5.80, (1, 0) 5.80, (4, 0) 5.77 TB/s against 5.75-5.94 for (2, 1) in the same run: no gain, profiles/r03_cross_attn_half_slot_ab.txt)
-  // (with the stage consumed and re-filled in halves, ONE stage wins there too: K = 50, S = 2 688, H = 16, same box: (1, 1) 4.65 / 5.75 TB/s
-  // against (1, 2) 3.97 / 5.12, (4, 1) 4.19 / 5.37, (2, 2) 3.72 / 5.02 -- profiles/r02m_cross_attn_k50_variants.txt)
-  // (round 4, both open ideas of round 3 built and measured, neither kept -- commit e681937, profiles/r04e_*, r04f_*: a PERSISTENT-WAVE
-  // kernel -- one wave per strided list of (user, head) items, the next item's first tiles requested before the current one is merged and
-  // stored, the two waves as two accumulator sets, bit-identical to this kernel on 8 shapes incl. live rows -- ran the bench's
-  // cross-attention in 164.4 ms per step against 160.8 (its 205 VGPRs leave 8 waves per CU where five two-wave workgroups fill the LDS);
-  // and the bank addressed as STEP-MAJOR 16-KB RECORDS (read side only) read 5.78 TB/s against 5.86 for the planar bank, with +-5 %
-  // between processes for either: the per-item prologue / tail and the four planar streams are not what holds the kernel at ~0.87 of the
-  // box's streaming read)
-  if constexpr (NT >= 3) return launch_cross<NT, S, 1, 1>(XA_ARGS);
-  else return launch_cross<NT, S, 2, 1>(XA_ARGS);
-#undef XA_ARGS
-}
-
 template <int S>
-int launch_cross_nt(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int B, int K, int H, int Sk,
-                    const int32_t* users, const int32_t* rowpos, long q_ps, long bank_ps, const uint32_t* key_bits, hipStream_t st) {
-  switch ((K + 15) / 16) {
-    case 1: return launch_cross_v<1, S>(q, k, vt, mask, out, B, K, H, Sk, users, rowpos, q_ps, bank_ps, key_bits, st);
-    case 2: return launch_cross_v<2, S>(q, k, vt, mask, out, B, K, H, Sk, users, rowpos, q_ps, bank_ps, key_bits, st);
-    case 3: return launch_cross_v<3, S>(q, k, vt, mask, out, B, K, H, Sk, users, rowpos, q_ps, bank_ps, key_bits, st);
-    default: return launch_cross_v<4, S>(q, k, vt, mask, out, B, K, H, Sk, users, rowpos, q_ps, bank_ps, key_bits, st);
+int launch_cross_nt(const XaLaunch& a) {
+  switch ((a.K + 15) / 16) {
+    case 1: return launch_cross<1, S>(a);
+    case 2: return launch_cross<2, S>(a);
+    case 3: return launch_cross<3, S>(a);
+    default: return launch_cross<4, S>(a);
   }
 }
 
@@ -793,8 +575,8 @@ extern "C" int gram_cross_attn_decode_split(const void* q, const void* k_layer, 
     return GRAM_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   gram_prof::Scope prof(GRAM_K_CROSS_ATTN, st, 4.0 * B * H * S * 64 * pieces);  // K + V^T, bf16, every piece
-  if (pieces == 2) return launch_cross_nt<2>(q, k_layer, vt_layer, mask, out, B, K, H, S, users, rowpos, q_pstride, bank_pstride, key_bits, st);
-  return launch_cross_nt<1>(q, k_layer, vt_layer, mask, out, B, K, H, S, users, rowpos, q_pstride, bank_pstride, key_bits, st);
+  const XaLaunch a{q, k_layer, vt_layer, mask, out, B, K, H, S, users, rowpos, (long)q_pstride, (long)bank_pstride, key_bits, st};
+  return pieces == 2 ? launch_cross_nt<2>(a) : launch_cross_nt<1>(a);
 }
 
 extern "C" int gram_cross_attn_decode(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out,

@@ -1,17 +1,17 @@
-"""GPU micro-benchmark (not a test): the cross-attention kernel at the bench shape per (waves per workgroup, ring depth)
-variant.  Needs a library built with -DGRAM_XA_AB=1; each variant runs in its own process (the selector is read once).
-    python tests/bench_xattn.py            # all variants, both piece counts
+"""GPU micro-benchmark (not a test): the cross-attention kernel alone.
+    python tests/bench_xattn.py                          # the bench shape (B 4096, H 12, S 384, K 20), one and two pieces
+    python tests/bench_xattn.py pieces B H S K [layers]  # one shape, e.g. config 5's  `2 512 16 2688 50`
+XA_HEAT=n times every launch right behind n large GEMMs, as in a decode step.
 """
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one(pieces, B=4096, H=12, S=384, K=20, reps=20, use_bits=True, layers=1):
+def one(pieces, B=4096, H=12, S=384, K=20, reps=20, layers=1):
     import torch
     from gram_amd import _lib
     DT = _lib.piece_dtype()
@@ -37,7 +37,7 @@ def one(pieces, B=4096, H=12, S=384, K=20, reps=20, use_bits=True, layers=1):
         ly = it[0] % layers
         it[0] += 1
         _lib.check(lib.gram_cross_attn_decode_split(q.data_ptr(), kbs.data_ptr() + ly * lstride, vts.data_ptr() + ly * lstride, mask.data_ptr(), out.data_ptr(), B, K, H, S,
-                                                    None, None, pieces, q[0].numel(), pstride, bits.data_ptr() if use_bits else None, st), "xattn")
+                                                    None, None, pieces, q[0].numel(), pstride, bits.data_ptr(), st), "xattn")
     for _ in range(3):
         run()
     if os.environ.get("XA_HEAT"):
@@ -70,22 +70,14 @@ def one(pieces, B=4096, H=12, S=384, K=20, reps=20, use_bits=True, layers=1):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 2:  # pieces B H S K: one shape, e.g. config 5's  `2 512 16 2688 50`
+    if len(sys.argv) not in (1, 6, 7):
+        sys.exit(__doc__)
+    if len(sys.argv) > 1:
         pieces, B, H, S, K = (int(x) for x in sys.argv[1:6])
         layers = int(sys.argv[6]) if len(sys.argv) > 6 else 1
         us, gbs = one(pieces, B=B, H=H, S=S, K=K, layers=layers, reps=max(20, 2 * layers))
         print(json.dumps({"pieces": pieces, "B": B, "H": H, "S": S, "K": K, "layers": layers, "us": round(us, 1), "GBps": round(gbs, 1)}))
-    elif len(sys.argv) > 1:
-        for ub in (True, True):
-            us, gbs = one(int(sys.argv[1]), use_bits=ub)
-            print(json.dumps({"variant": os.environ.get("GRAM_XA_VARIANT", "default"), "pieces": int(sys.argv[1]), "key_bits": ub, "us": round(us, 1), "GBps": round(gbs, 1)}))
     else:
-        for pieces, variants in ((1, ["", "21", "22", "12", "13", "41", "42"]), (2, ["", "21", "22", "11", "12", "41"])):
-            for v in variants:
-                env = dict(os.environ)
-                if v:
-                    env["GRAM_XA_VARIANT"] = v
-                else:
-                    env.pop("GRAM_XA_VARIANT", None)
-                p = subprocess.run([sys.executable, os.path.abspath(__file__), str(pieces)], env=env, capture_output=True, text=True)
-                print(p.stdout.strip() or p.stderr[-300:], flush=True)
+        for pieces in (1, 2):
+            us, gbs = one(pieces)
+            print(json.dumps({"pieces": pieces, "us": round(us, 1), "GBps": round(gbs, 1)}), flush=True)
