@@ -127,6 +127,10 @@ SIGNATURES = {
     "gram_trie_item_index": (C.c_int, [C.POINTER(Trie), vp, vp, C.c_int, C.c_int, vp, vp]),
     "gram_model_create": (vp, [C.POINTER(ModelDesc)]),
     "gram_model_destroy": (None, [vp]),
+    "gram_iota_i32": (C.c_int, [vp, C.c_int, vp]),
+    "gram_token_tables_bytes": (i64, [vp]),
+    "gram_token_tables_workspace_bytes": (i64, [vp]),
+    "gram_model_build_token_tables": (C.c_int, [vp, vp, i64, vp, i64, vp]),
     "gram_workspace_bytes": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gram_workspace_encoder_x_offset": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gram_encode_fused": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, i64, C.c_int, C.c_int, vp, vp]),
@@ -136,6 +140,7 @@ SIGNATURES = {
     "gram_debug_set_gemm_variant": (C.c_int, [C.c_int]),
     "gram_gemm_stream_max_m": (C.c_int, []),
     "gram_debug_set_live_rows": (C.c_int, [C.c_int]),
+    "gram_debug_set_token_tables": (C.c_int, [C.c_int]),
     "gram_debug_set_beam_chunked": (C.c_int, [C.c_int]),
     "gram_debug_set_beam_chunk_capacity": (C.c_int, [C.c_int]),
     "gram_debug_set_stage_pieces": (C.c_int, [C.POINTER(i32), C.c_int]),
@@ -160,8 +165,11 @@ SIGNATURES = {
     "gram_rmsnorm_bf16_split": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, f32, f32, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
     "gram_enc_self_attn_split": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp]),
     "gram_cross_attn_decode_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, i64, i64, vp, vp]),
+    "gram_enc_self_attn_rows_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp]),
     "gram_mask_key_bits": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     "gram_dec_self_attn_split": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, vp]),
+    "gram_dec_self_attn_rows_split": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64,
+                                                vp]),
     "gram_beam_step_sparse_split": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                               vp, C.c_int, vp]),
     "gram_generate": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),

@@ -464,15 +464,16 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const p16* __restric
                                                             p16* __restrict__ vcache, const int32_t* __restrict__ anc,
                                                             const float* __restrict__ bias, p16* __restrict__ out, int R,
                                                             int H, int t, const int32_t* __restrict__ rows, long qkv_ps,
-                                                            long cache_ps) {
+                                                            long cache_ps, const int32_t* __restrict__ qkv_rows) {
   // live-row step (rows != NULL): qkv/out are indexed by the compact row, the cache and the ancestor table by the
   // original row rows[compact]; R stays the row count of the cache
+  // qkv_rows != NULL: qkv is a per-token table (gram_model_build_token_tables) and compact row rc reads its row qkv_rows[rc]
   // (giving each XCD a contiguous eighth of the rows, so that a user's beams share ancestors' cache rows in ONE L2, was measured:
   // 41.9 ms per step against 41.2 for the round-robin order below)
   const int rc = blockIdx.x, i = threadIdx.x;  // i: 16 threads per head, 4 dims each
   const int r = rows ? rows[rc] : rc;
   const int inner = H * 64, h = i >> 4;
-  const p16* row = qkv + (size_t)rc * 3 * inner + 4 * i;
+  const p16* row = qkv + (size_t)(qkv_rows ? qkv_rows[rc] : rc) * 3 * inner + 4 * i;
   // values as the fp32 sum of their pieces (exact for two pieces, one rounding for three); the pieces themselves go to the cache
   float qf[4] = {0.f, 0.f, 0.f, 0.f}, kn[4] = {0.f, 0.f, 0.f, 0.f}, vn[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -594,6 +595,13 @@ extern "C" int gram_cross_attn_decode_live(const void* q, const void* k_layer, c
 extern "C" int gram_dec_self_attn_split(const void* qkv, void* kcache, void* vcache, const int32_t* anc, const float* bias, void* out,
                                         int R, int n_rows, const int32_t* rows, int H, int t, int Tmax, int pieces,
                                         int64_t qkv_pstride, int64_t cache_pstride, void* stream) {
+  return gram_dec_self_attn_rows_split(qkv, nullptr, kcache, vcache, anc, bias, out, R, n_rows, rows, H, t, Tmax, pieces, qkv_pstride,
+                                       cache_pstride, stream);
+}
+
+extern "C" int gram_dec_self_attn_rows_split(const void* qkv, const int32_t* qkv_rows, void* kcache, void* vcache, const int32_t* anc,
+                                             const float* bias, void* out, int R, int n_rows, const int32_t* rows, int H, int t,
+                                             int Tmax, int pieces, int64_t qkv_pstride, int64_t cache_pstride, void* stream) {
   if (R < 1 || n_rows < 1 || n_rows > R || H < 1 || H > 16 || t < 0 || t >= Tmax || Tmax > GRAM_MAX_DEC_LEN || pieces < 1 ||
       pieces > GRAM_MAX_PIECES)
     return GRAM_E_ARG;
@@ -603,10 +611,10 @@ extern "C" int gram_dec_self_attn_split(const void* qkv, void* kcache, void* vca
   const dim3 grid(n_rows), block(H * 16);
   if (pieces == 2)
     hipLaunchKernelGGL(dec_self_attn_kernel<2>, grid, block, 0, st, (const p16*)qkv, (p16*)kcache, (p16*)vcache, anc, bias,
-                       (p16*)out, R, H, t, rows, (long)qkv_pstride, (long)cache_pstride);
+                       (p16*)out, R, H, t, rows, (long)qkv_pstride, (long)cache_pstride, qkv_rows);
   else
     hipLaunchKernelGGL(dec_self_attn_kernel<1>, grid, block, 0, st, (const p16*)qkv, (p16*)kcache, (p16*)vcache, anc, bias,
-                       (p16*)out, R, H, t, rows, (long)qkv_pstride, (long)cache_pstride);
+                       (p16*)out, R, H, t, rows, (long)qkv_pstride, (long)cache_pstride, qkv_rows);
   GRAM_CHECK_LAUNCH();
   return 0;
 }

@@ -26,10 +26,12 @@ namespace {
 __device__ __forceinline__ int kswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 __device__ __forceinline__ int vtswz(int d, int key) { return d * 256 + ((((key >> 3) ^ (d & 15))) << 4) + (key & 7) * 2; }
 
-template <int NKS, int S>  // L = 32 * NKS; S = 16-bit pieces per value (1: plain; 2: gram_split_t -- q|k|v planar, the output interleaved)
+// L = 32 * NKS; S = 16-bit pieces per value (1: plain; 2: gram_split_t -- q|k|v planar, the output interleaved)
+// ROWS: qkv is a per-token table (gram_model_build_token_tables) and row `row` of passage p is its row ids[p * L + row]
+template <int NKS, int S, bool ROWS>
 __global__ __launch_bounds__(256) void enc_attn_kernel(const p16* __restrict__ qkv, const float* __restrict__ bias,
                                                        const uint8_t* __restrict__ mask, p16* __restrict__ out, int H,
-                                                       long qkv_pstride) {
+                                                       long qkv_pstride, const int64_t* __restrict__ ids) {
   constexpr int L = 32 * NKS;
   using T = SplitTab<S>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -45,7 +47,24 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const p16* __restrict__ q
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int inner = H * 64;
   const size_t rs = (size_t)3 * inner;  // qkv row stride (elements)
-  const p16* base = qkv + (size_t)p * L * rs + h * 64;
+  const p16* base = qkv + (ROWS ? (size_t)0 : (size_t)p * L * rs) + h * 64;
+  // ROWS: the table rows (= token ids) of this thread's NKS K/V rows and of its two query rows, requested together and ahead of
+  // everything that depends on them.  The K/V loads cannot leave before the ids are back -- one more round trip in front of them than
+  // the plain kernel has -- so this thread's bias and mask values, which the plain kernel fetches behind the K/V phase, travel with
+  // the ids: the same number of exposed round trips per workgroup.
+  long kvid[ROWS ? NKS : 1], qid[2];
+  float bias_early = 0.f;
+  uint32_t mask_early = 1;
+  if constexpr (ROWS) {
+    const int64_t* pid = ids + (size_t)p * L;
+#pragma unroll
+    for (int it = 0; it < NKS; ++it) kvid[it] = pid[(tid + it * 256) >> 3];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) qid[nt] = wave * 32 < L ? pid[wave * 32 + 16 * nt + (lane & 15)] : 0;
+    if (tid < 255) bias_early = bias[h * 255 + tid];
+    if (tid < L) mask_early = mask[(size_t)p * L + tid];
+    asm volatile("" : "+v"(bias_early), "+v"(mask_early));  // (here, not sunk to their use behind the K/V phase)
+  }
 
   // K and V rows -> LDS: all 2*NKS 16-byte loads of a thread go out first (written as load; store per iteration,
   // hipcc waits for each pair before issuing the next: NKS exposed HBM round trips per workgroup)
@@ -55,7 +74,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const p16* __restrict__ q
 #pragma unroll
     for (int it = 0; it < NKS; ++it) {
       const int i = tid + it * 256, row = i >> 3, c = i & 7;
-      const p16* src = base + pc * qkv_pstride + (size_t)row * rs + c * 8;
+      const p16* src = base + pc * qkv_pstride + (size_t)(ROWS ? kvid[it] : row) * rs + c * 8;
       if constexpr ((GRAM_ENC_ABL & 8) != 0) {
         kv[it] = zero_bf16x8();
         vv[it] = zero_bf16x8();
@@ -78,14 +97,14 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const p16* __restrict__ q
     }
   }
   if (tid < 255) {
-    const float bv = bias[h * 255 + tid];
+    const float bv = ROWS ? bias_early : bias[h * 255 + tid];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (tid >= r) bias_s[r * 256 + tid - r] = bv;
   }
   bool key_masked = false;
   if (tid < L) {
-    key_masked = mask[(size_t)p * L + tid] == 0;
+    key_masked = (ROWS ? mask_early : mask[(size_t)p * L + tid]) == 0;
     mask_s[tid] = key_masked ? 1.f : 0.f;
   }
   const bool any_masked = __syncthreads_or(key_masked) != 0;  // (an all-valid passage skips the mask pass: wave-uniform)
@@ -105,7 +124,7 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const p16* __restrict__ q
           qf[pc][nt][kd] = zero_bf16x8();
           asm volatile("" : "+v"(qf[pc][nt][kd]));
         } else {
-          qf[pc][nt][kd] = ld_stream_b128(base + pc * qkv_pstride + (size_t)(q0 + 16 * nt + c) * rs + 32 * kd + 8 * g);
+          qf[pc][nt][kd] = ld_stream_b128(base + pc * qkv_pstride + (size_t)(ROWS ? qid[nt] : q0 + 16 * nt + c) * rs + 32 * kd + 8 * g);
         }
 
   f32x4 s[NKS][2][2];
@@ -273,25 +292,25 @@ __global__ __launch_bounds__(256) void enc_attn_kernel(const p16* __restrict__ q
   }
 }
 
-template <int S>
-int launch_enc(const void* qkv, const float* bias, const uint8_t* mask, void* out, int P, int L, int H, long qkv_pstride,
-               hipStream_t st) {
+template <int S, bool ROWS>
+int launch_enc(const void* qkv, const int64_t* ids, const float* bias, const uint8_t* mask, void* out, int P, int L, int H,
+               long qkv_pstride, hipStream_t st) {
   const dim3 grid(H, P), block(256);
   constexpr int smem = S * 2 * 128 * 128 + (4 * 256 + 128) * 4;
   static bool attr_set = false;
   if (!attr_set && smem > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<1, S>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<2, S>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<3, S>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<4, S>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<1, S, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<2, S, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<3, S, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(enc_attn_kernel<4, S, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
   switch (L / 32) {
-    case 1: hipLaunchKernelGGL((enc_attn_kernel<1, S>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride); break;
-    case 2: hipLaunchKernelGGL((enc_attn_kernel<2, S>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride); break;
-    case 3: hipLaunchKernelGGL((enc_attn_kernel<3, S>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride); break;
-    default: hipLaunchKernelGGL((enc_attn_kernel<4, S>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride); break;
+    case 1: hipLaunchKernelGGL((enc_attn_kernel<1, S, ROWS>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride, ids); break;
+    case 2: hipLaunchKernelGGL((enc_attn_kernel<2, S, ROWS>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride, ids); break;
+    case 3: hipLaunchKernelGGL((enc_attn_kernel<3, S, ROWS>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride, ids); break;
+    default: hipLaunchKernelGGL((enc_attn_kernel<4, S, ROWS>), grid, block, smem, st, (const p16*)qkv, bias, mask, (p16*)out, H, qkv_pstride, ids); break;
   }
   GRAM_CHECK_LAUNCH();
   return 0;
@@ -310,6 +329,17 @@ extern "C" int gram_enc_self_attn_split(const void* qkv, const float* bias, cons
   if (pieces > 1 && qkv_pstride < (int64_t)P * L * 3 * H * 64) return GRAM_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   gram_prof::Scope prof(GRAM_K_ENC_ATTN, st, 4.0 * P * H * L * L * 64 * (pieces == 2 ? 3 : 1));
-  if (pieces == 2) return launch_enc<2>(qkv, bias, mask, out, P, L, H, qkv_pstride, st);
-  return launch_enc<1>(qkv, bias, mask, out, P, L, H, qkv_pstride, st);
+  if (pieces == 2) return launch_enc<2, false>(qkv, nullptr, bias, mask, out, P, L, H, qkv_pstride, st);
+  return launch_enc<1, false>(qkv, nullptr, bias, mask, out, P, L, H, qkv_pstride, st);
+}
+
+extern "C" int gram_enc_self_attn_rows_split(const void* qkv_table, const int64_t* ids, const float* bias, const uint8_t* mask,
+                                             void* out, int P, int L, int H, int pieces, int64_t qkv_pstride, void* stream) {
+  if (P < 1 || H < 1 || L < 32 || L > GRAM_MAX_PASSAGE_LEN || (L & 31) || pieces < 1 || pieces > GRAM_MAX_PIECES || !qkv_table || !ids)
+    return GRAM_E_ARG;
+  if (pieces > 1 && qkv_pstride < (int64_t)3 * H * 64) return GRAM_E_ARG;  // (at least one table row per piece)
+  hipStream_t st = (hipStream_t)stream;
+  gram_prof::Scope prof(GRAM_K_ENC_ATTN, st, 4.0 * P * H * L * L * 64 * (pieces == 2 ? 3 : 1));
+  if (pieces == 2) return launch_enc<2, true>(qkv_table, ids, bias, mask, out, P, L, H, qkv_pstride, st);
+  return launch_enc<1, true>(qkv_table, ids, bias, mask, out, P, L, H, qkv_pstride, st);
 }

@@ -22,6 +22,8 @@ struct gram_model {
   // 1 / (power-of-two factor a weight matrix was scaled by) = the out_scale of its GEMM (gram_model_desc_t.w_scales)
   std::vector<float> s_enc_wqkv, s_enc_wo, s_enc_wi, s_enc_wo2, s_dec_wqkv, s_dec_wo, s_dec_wq_x, s_dec_wo_x, s_dec_wi, s_dec_wo2;
   float s_wkv = 1.f, s_lm = 1.f;
+  // layer 0's q|k|v per token (gram_model_build_token_tables), [pieces][vocab][3 * inner] each; null: none, layer 0 runs its QKV GEMM
+  const p16 *enc_qkv0 = nullptr, *dec_qkv0 = nullptr;
 };
 
 namespace {
@@ -229,19 +231,23 @@ struct NormChain {
         quarter(c.fold_norm && n <= gram_gemm_stream_max_m() && d % 128 == 0 && (c.n_heads * 64) % 128 == 0 && c.d_ff % 128 == 0),
         pre_rs(n >= kPrecomputedRsRows) {}
 
-  int embed(const void* ids, int ids_are_i64) {
-    if (c.fold_norm) return gram_embed_ex_xs(c.embed_f32, ids, ids_are_i64, r.x, r.h, r.ss, r.xs[0], d / 64, n, d, w.pieces, st);
+  // want_xb false: the first consumer reads a token table, not the 16-bit copy (the copy's row factor is still published)
+  int embed(const void* ids, int ids_are_i64, bool want_xb = true) {
+    if (c.fold_norm)
+      return gram_embed_ex_xs(c.embed_f32, ids, ids_are_i64, r.x, want_xb ? r.h : nullptr, r.ss, r.xs[0], d / 64, n, d, w.pieces, st);
     return ids_are_i64 ? gram_embed_i64(c.embed_f32, (const int64_t*)ids, r.x, n, d, st)
                        : gram_embed_i32(c.embed_f32, (const int32_t*)ids, r.x, n, d, st);
   }
   // The norm in front of a consumer GEMM: launches what has to run before it (big path: 1/rms / xs and the next factor; unfolded: the
   // norm itself) and returns in *pnf what the GEMM takes, nf or null.  The first consumer after the embedding reads 64-column partials.
-  int norm(const float* gain, bool from_embed, gram_norm_fusion_t& nf, const gram_norm_fusion_t** pnf) {
+  // no_gemm (folded norm, from_embed): a token table stands in for the consumer GEMM, so what that GEMM does besides its product on
+  // the small path -- publishing the next producer's row factor -- is left to the big path's kernel (same order, same bits)
+  int norm(const float* gain, bool from_embed, gram_norm_fusion_t& nf, const gram_norm_fusion_t** pnf, bool no_gemm = false) {
     float *const xs_in = r.xs[np & 1], *const xs_out = r.xs[(np + 1) & 1];
     ++np;
     *pnf = c.fold_norm ? &nf : nullptr;
     if (!c.fold_norm) return gram_rmsnorm_bf16_split(r.x, gain, r.h, n, d, c.eps, 1.f, nullptr, 1, 1, nullptr, 1, st);
-    if (pre_rs) {
+    if (pre_rs || no_gemm) {
       nf = gram_norm_fusion_t{nullptr, nullptr, r.rs, 0, d, c.eps, 0, nullptr, nullptr};
       return gram_row_rscale_xs(r.ss, r.rs, xs_in, xs_out, n, d / 64, d, c.eps, st);
     }
@@ -271,6 +277,7 @@ struct Sublayer {
   int k_out;
   const void* w_out;
   float s_out;
+  bool mid_from_table = false;  // layer 0 of a stack whose handle has token tables: the mixer reads q|k|v rows by token, no in-GEMM
 };
 template <typename Mixer>
 int sublayer(NormChain& nc, const Sublayer& s, bool from_embed, Mixer mixer) {
@@ -280,12 +287,14 @@ int sublayer(NormChain& nc, const Sublayer& s, bool from_embed, Mixer mixer) {
   void* const st = nc.st;
   gram_norm_fusion_t nf;
   const gram_norm_fusion_t* pnf;
-  TRY(nc.norm(s.gain, from_embed, nf, &pnf));
-  TRY(cap_inter(w, r.h, n, d, s.stage, st));
-  // (the unfolded path has one piece, and has always declared its in-GEMM's C planar with stride 0)
-  TRY(linear(w, r.h, s.w_in, s.s_in, s.mid, pnf ? s.mid_kind : C_PLANAR, pnf ? s.mid_ps : 0, n, s.n_mid, d, s.epi, nullptr, pnf, st));
-  if (s.mid_kind == C_PLANAR) TRY(cap_planar(w, s.mid, s.mid_ps, s.stage, st));
-  else TRY(cap_inter(w, s.mid, n, s.n_mid, s.stage, st));
+  TRY(nc.norm(s.gain, from_embed, nf, &pnf, s.mid_from_table));
+  if (!s.mid_from_table) {  // (a table is used only where the stage has no cap: token_table())
+    TRY(cap_inter(w, r.h, n, d, s.stage, st));
+    // (the unfolded path has one piece, and has always declared its in-GEMM's C planar with stride 0)
+    TRY(linear(w, r.h, s.w_in, s.s_in, s.mid, pnf ? s.mid_kind : C_PLANAR, pnf ? s.mid_ps : 0, n, s.n_mid, d, s.epi, nullptr, pnf, st));
+    if (s.mid_kind == C_PLANAR) TRY(cap_planar(w, s.mid, s.mid_ps, s.stage, st));
+    else TRY(cap_inter(w, s.mid, n, s.n_mid, s.stage, st));
+  }
   if (s.a != s.mid) {
     TRY(mixer());
     TRY(cap_inter(w, r.attn, n, s.k_out, s.stage, st));
@@ -294,17 +303,36 @@ int sublayer(NormChain& nc, const Sublayer& s, bool from_embed, Mixer mixer) {
 }
 inline int no_mixer() { return 0; }
 
+// Layer-0 q|k|v per token (gram_hip.h, gram_model_build_token_tables).  A stack reads its table where the handle has one, the switch is
+// on and the stage runs uncapped (gram_debug_set_stage_pieces zeroes operand pieces in front of the GEMM the table replaces).
+int g_token_tables = -1;  // -1: the GRAM_TOKEN_TABLES environment variable decides (default on)
+const p16* token_table(const gram_model* m, const p16* table, int stage) {
+  if (!table || !m->d.fold_norm || g_stage_cap[stage] < 2) return nullptr;
+  if (g_token_tables >= 0) return g_token_tables ? table : nullptr;
+  const char* e = getenv("GRAM_TOKEN_TABLES");
+  return e && e[0] == '0' ? nullptr : table;
+}
+inline int64_t token_table_elems(const gram_model_desc_t& c) {  // of one table, padded to the carve's 256 B
+  const int64_t P = c.pieces > 1 ? c.pieces : 1;
+  return (P * c.vocab * 3 * c.n_heads * 64 + 127) & ~(int64_t)127;
+}
+
 // The encoder layers on P passages (ids/mask [P][L]); leaves the residual stream in w.enc.x rows [0, P*L).
 int encoder_layers(const gram_model* m, const Workspace& w, const int64_t* ids, const uint8_t* mask, int L, int P, void* st) {
   const gram_model_desc_t& c = m->d;
   const int inner = c.n_heads * 64, F = c.d_ff;
   const Rows& r = w.enc;
   NormChain nc(m, w, r, P * L, st);
-  TRY(nc.embed(ids, 1));
+  const p16* const table = token_table(m, m->enc_qkv0, GRAM_STAGE_ENC_ATTN);
+  TRY(nc.embed(ids, 1, !table));
   for (int i = 0; i < c.n_enc_layers; ++i) {
+    const p16* const tab = i == 0 ? table : nullptr;
     TRY(sublayer(nc, {GRAM_STAGE_ENC_ATTN, m->enc_ln1[i], m->enc_wqkv[i], m->s_enc_wqkv[i], r.qkv, C_PLANAR, r.ps_qkv, 3 * inner,
-                      GRAM_EPI_BF16, r.attn, inner, m->enc_wo[i], m->s_enc_wo[i]},
+                      GRAM_EPI_BF16, r.attn, inner, m->enc_wo[i], m->s_enc_wo[i], tab != nullptr},
                  i == 0, [&] {  // (unfolded: stride 0, as for the GEMM in front)
+                   if (tab)
+                     return gram_enc_self_attn_rows_split(tab, ids, c.enc_bias_f32, mask, r.attn, P, L, c.n_heads, w.pieces,
+                                                          (int64_t)c.vocab * 3 * inner, st);
                    return gram_enc_self_attn_split(r.qkv, c.enc_bias_f32, mask, r.attn, P, L, c.n_heads, w.pieces,
                                                    c.fold_norm ? r.ps_qkv : 0, st);
                  }));
@@ -368,17 +396,18 @@ struct LiveStep {  // host view of gram_live_rows_t after the counts came back
 
 // The decoder layers on n rows (tokens i32 [n]).  self_attn(i) and cross_attn(i) launch layer i's attention from w.dec.qkv / w.dec.qx
 // into w.dec.attn: one position over the cache and one row per beam (decode_step), or whole sequences (decoder_tf).
+// qkv0_from_table: self_attn(0) reads the rows `tokens` of the decoder's token table instead of w.dec.qkv.
 template <typename SelfAttn, typename CrossAttn>
-int decoder_layers(const gram_model* m, const Workspace& w, const int32_t* tokens, int n, SelfAttn self_attn, CrossAttn cross_attn,
-                   void* st) {
+int decoder_layers(const gram_model* m, const Workspace& w, const int32_t* tokens, int n, bool qkv0_from_table, SelfAttn self_attn,
+                   CrossAttn cross_attn, void* st) {
   const gram_model_desc_t& c = m->d;
   const int inner = c.n_heads * 64, F = c.d_ff;
   const Rows& r = w.dec;
   NormChain nc(m, w, r, n, st);
-  TRY(nc.embed(tokens, 0));
+  TRY(nc.embed(tokens, 0, !qkv0_from_table));
   for (int i = 0; i < c.n_dec_layers; ++i) {
     TRY(sublayer(nc, {GRAM_STAGE_DEC_SELF, m->dec_ln1[i], m->dec_wqkv[i], m->s_dec_wqkv[i], r.qkv, C_PLANAR, r.ps_qkv, 3 * inner,
-                      GRAM_EPI_BF16, r.attn, inner, m->dec_wo[i], m->s_dec_wo[i]},
+                      GRAM_EPI_BF16, r.attn, inner, m->dec_wo[i], m->s_dec_wo[i], i == 0 && qkv0_from_table},
                  i == 0, [&] { return self_attn(i); }));
     TRY(sublayer(nc, {GRAM_STAGE_DEC_CROSS, m->dec_ln2[i], m->dec_wq_x[i], m->s_dec_wq_x[i], r.qx, C_PLANAR, r.ps_qx, inner,
                       GRAM_EPI_BF16, r.attn, inner, m->dec_wo_x[i], m->s_dec_wo_x[i]},
@@ -414,9 +443,14 @@ int decode_step(const gram_model* m, const Workspace& w, const int32_t* tokens, 
   const size_t bank_layer = (size_t)B * H * S * 64;
   const size_t cache_layer = (size_t)Tmax * R_cache * inner;
   const Rows& r = w.dec;
+  const p16* const table = token_table(m, m->dec_qkv0, GRAM_STAGE_DEC_SELF);
   TRY(decoder_layers(
-      m, w, tokens, R,
+      m, w, tokens, R, table != nullptr,
       [&](int i) {
+        if (i == 0 && table)
+          return gram_dec_self_attn_rows_split(table, tokens, w.kcache, w.vcache, anc, c.dec_bias_f32, r.attn, live ? R_cache : R, R,
+                                               live ? live->rows : nullptr, H, t, Tmax, w.pieces, (int64_t)c.vocab * 3 * inner,
+                                               w.ps_cache, st);
         return gram_dec_self_attn_split(r.qkv, w.kcache + i * cache_layer, w.vcache + i * cache_layer, anc, c.dec_bias_f32, r.attn,
                                         live ? R_cache : R, R, live ? live->rows : nullptr, H, t, Tmax, w.pieces, r.ps_qkv, w.ps_cache, st);
       },
@@ -454,6 +488,10 @@ extern "C" int gram_debug_set_stage_pieces(const int32_t* caps, int n) {
 static int g_live_rows = -1;  // -1: the GRAM_LIVE_ROWS environment variable decides (default on)
 extern "C" int gram_debug_set_live_rows(int on) {
   g_live_rows = on;
+  return 0;
+}
+extern "C" int gram_debug_set_token_tables(int on) {
+  g_token_tables = on;
   return 0;
 }
 
@@ -516,6 +554,75 @@ extern "C" gram_model_t* gram_model_create(const gram_model_desc_t* d) {
 extern "C" void gram_model_destroy(gram_model_t* m) {
   if (!m) return;
   delete m;
+}
+
+// ---- token tables (gram_model_build_token_tables) ------------------------------------------------------------------------------------
+namespace {
+
+// scratch of the build: what the embedding and the norm of `vocab` rows write, and the ids 0 .. vocab-1
+struct TableScratch {
+  Rows rows;
+  int32_t* ids;
+  int64_t bytes;
+};
+TableScratch carve_tables(const gram_model_desc_t& c, void* ws) {
+  const int64_t P = c.pieces > 1 ? c.pieces : 1, V = c.vocab, d = c.d_model;
+  Carve cv(ws);
+  TableScratch t{};
+  t.rows.x = cv.take<float>(V * d);
+  t.rows.h = cv.take<p16>(P * V * d);
+  t.rows.ss = cv.take<float>(ss_floats(V, d));
+  t.rows.rs = cv.take<float>(V);
+  t.rows.xs[0] = cv.take<float>(V);
+  t.rows.xs[1] = cv.take<float>(V);
+  t.ids = cv.take<int32_t>(V);
+  t.bytes = (cv.off + 255) & ~(int64_t)255;
+  return t;
+}
+
+// one stack's table by the path's own launches: the embedding of every token, the first norm, the layer-0 QKV GEMM writing planar pieces
+int build_table(const gram_model* m, const Workspace& w, const TableScratch& t, const float* gain, const void* wqkv, float s_wqkv,
+                p16* table, void* st) {
+  const gram_model_desc_t& c = m->d;
+  const int V = c.vocab, inner = c.n_heads * 64;
+  NormChain nc(m, w, t.rows, V, st);
+  TRY(nc.embed(t.ids, 0));
+  gram_norm_fusion_t nf;
+  const gram_norm_fusion_t* pnf;
+  TRY(nc.norm(gain, true, nf, &pnf));
+  return linear(w, t.rows.h, wqkv, s_wqkv, table, C_PLANAR, (int64_t)V * 3 * inner, V, 3 * inner, c.d_model, GRAM_EPI_BF16, nullptr, pnf, st);
+}
+
+}  // namespace
+
+extern "C" int64_t gram_token_tables_bytes(const gram_model_t* m) {
+  if (!m) return GRAM_E_ARG;
+  return m->d.fold_norm ? 2 * token_table_elems(m->d) * (int64_t)sizeof(p16) : 0;
+}
+
+extern "C" int64_t gram_token_tables_workspace_bytes(const gram_model_t* m) {
+  if (!m) return GRAM_E_ARG;
+  return m->d.fold_norm ? carve_tables(m->d, nullptr).bytes : 0;
+}
+
+extern "C" int gram_model_build_token_tables(gram_model_t* m, void* tables, int64_t tables_bytes, void* workspace,
+                                             int64_t workspace_bytes, void* stream) {
+  if (!m || !m->d.fold_norm || !tables || (reinterpret_cast<uintptr_t>(tables) & 255)) return GRAM_E_ARG;
+  if (tables_bytes < gram_token_tables_bytes(m)) return GRAM_E_ARG;
+  const gram_model_desc_t& c = m->d;
+  const TableScratch t = carve_tables(c, workspace);
+  if (!workspace || workspace_bytes < t.bytes) return GRAM_E_WORKSPACE;
+  Workspace w{};
+  w.pieces = c.pieces > 1 ? c.pieces : 1;
+  m->enc_qkv0 = m->dec_qkv0 = nullptr;
+  p16* const enc = (p16*)tables;
+  p16* const dec = enc + token_table_elems(c);
+  TRY(gram_iota_i32(t.ids, c.vocab, stream));
+  TRY(build_table(m, w, t, m->enc_ln1[0], m->enc_wqkv[0], m->s_enc_wqkv[0], enc, stream));
+  TRY(build_table(m, w, t, m->dec_ln1[0], m->dec_wqkv[0], m->s_dec_wqkv[0], dec, stream));
+  m->enc_qkv0 = enc;
+  m->dec_qkv0 = dec;
+  return 0;
 }
 
 extern "C" int64_t gram_workspace_bytes(const gram_model_t* m, int B, int N, int L, int K, int max_length) {
@@ -703,7 +810,7 @@ int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, c
   const size_t bank_layer = (size_t)B * H * S * 64;
   const Rows& r = w.dec;
   TRY(decoder_layers(
-      m, w, tokens, R,
+      m, w, tokens, R, /*qkv0_from_table=*/false,
       [&](int) { return gram_dec_self_attn_tf_split(r.qkv, c.dec_bias_f32, r.attn, R / T, T, H, w.pieces, r.ps_qkv, st); },
       [&](int i) {
         return gram_cross_attn_rows_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S, w.pieces,

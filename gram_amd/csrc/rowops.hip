@@ -34,6 +34,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ ta
 // embed_tokens for the folded-norm path: x (f32), its 16-bit copy xb and the row's 64-column partial sums of squares ss[row][d/64]
 // (nblk == d / 64; fewer: the row's total in ss[row][0] and zeros, the layout of round 1 -- no row factor then).
 // xs_out != NULL: the copy is x * xs, xs the power-of-two factor of the row itself (row_xscale), written to xs_out[row]
+// xb == NULL: no copy is written (its first consumer reads a token table instead of running the layer-0 QKV GEMM on it)
 template <typename IdT>
 __global__ __launch_bounds__(256) void embed_ex_kernel(const float* __restrict__ table, const IdT* __restrict__ ids,
                                                        float* __restrict__ x, p16* __restrict__ xb, float* __restrict__ ss,
@@ -81,10 +82,12 @@ __global__ __launch_bounds__(256) void embed_ex_kernel(const float* __restrict__
     if (lane < nblk) ss[(size_t)row * nblk + lane] = lane == 0 ? total : 0.f;
   }
   const float xs = xs_out && blocks ? row_xscale(total, minblk) : 1.f;
+  if (xb) {
 #pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int i = lane + it * 64;
-    if (i < d / 4) store_pieces4(dstb, 4 * i, v[it] * xs, pieces);
+    for (int it = 0; it < 4; ++it) {
+      const int i = lane + it * 64;
+      if (i < d / 4) store_pieces4(dstb, 4 * i, v[it] * xs, pieces);
+    }
   }
   if (xs_out && lane == 0) xs_out[row] = xs;
 }
@@ -290,6 +293,12 @@ __global__ __launch_bounds__(256) void stream_read_var_kernel(const uint4* __res
   if ((a.x ^ a.y ^ a.z ^ a.w) == 0x9e3779b9u && sink) *sink = a.x;
 }
 
+// out[i] = i: every token id in order, the input of the token tables' build (gram_model_build_token_tables)
+__global__ __launch_bounds__(256) void iota_kernel(int32_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = i;
+}
+
 // passage cache -> residual stream: one 16-byte chunk per thread, consecutive threads on consecutive chunks of a row
 __global__ __launch_bounds__(256) void gather_passage_x_kernel(const float* __restrict__ cache, const int32_t* __restrict__ slot,
                                                                float* __restrict__ x, int64_t nchunks, int L, int cache_L, int d4) {
@@ -368,16 +377,23 @@ extern "C" int gram_embed_ex_split(const float* table, const void* ids, int ids_
 
 extern "C" int gram_embed_ex_xs(const float* table, const void* ids, int ids_are_i64, float* x, void* xb, float* ss, float* xs_out,
                                 int nblk, int rows, int d, int pieces, void* stream) {
-  if (rows < 1 || (d & 3) || d > 1024 || !xb || !ss || nblk < 1 || nblk > 64 || pieces < 1 || pieces > GRAM_MAX_PIECES || (pieces > 1 && (d & 31)))
+  if (rows < 1 || (d & 3) || d > 1024 || !ss || nblk < 1 || nblk > 64 || pieces < 1 || pieces > GRAM_MAX_PIECES || (pieces > 1 && (d & 31)))
     return GRAM_E_ARG;
   if (xs_out && (d % 64 != 0 || nblk != d / 64)) return GRAM_E_ARG;  // the row factor needs the true 64-column partials
-  gram_prof::Scope prof(GRAM_K_ROWOPS, (hipStream_t)stream, (8.0 + 2.0 * pieces) * rows * d);
+  gram_prof::Scope prof(GRAM_K_ROWOPS, (hipStream_t)stream, (8.0 + (xb ? 2.0 * pieces : 0.0)) * rows * d);
   if (ids_are_i64)
     hipLaunchKernelGGL(embed_ex_kernel<int64_t>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, table, (const int64_t*)ids,
                        x, (p16*)xb, ss, xs_out, nblk, rows, d, pieces);
   else
     hipLaunchKernelGGL(embed_ex_kernel<int32_t>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, table, (const int32_t*)ids,
                        x, (p16*)xb, ss, xs_out, nblk, rows, d, pieces);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int gram_iota_i32(int32_t* out, int n, void* stream) {
+  if (!out || n < 1) return GRAM_E_ARG;
+  hipLaunchKernelGGL(iota_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, n);
   GRAM_CHECK_LAUNCH();
   return 0;
 }

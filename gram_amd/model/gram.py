@@ -560,7 +560,26 @@ class GRAM(nn.Module):
         if not handle:
             raise _lib.GramHipError("gram_model_create rejected the configuration (dims must be multiples of 128, heads <= 16)")
         self._packed = (dev, self._version, handle, keep)
+        self._build_token_tables(handle, keep)
         return handle
+
+    def _build_token_tables(self, handle, keep) -> None:
+        """Layer 0's q|k|v per token (gram_hip.h, gram_model_build_token_tables): computed once per handle, on the device, by the
+        path's own kernels; the tables live as long as the handle, the build's scratch goes back to the allocator at once.
+        GRAM_TOKEN_TABLES=0 (or unfolded norms) leaves the handle without tables: layer 0 then runs its QKV GEMMs."""
+        lib = _lib.load()
+        self._token_tables = None  # (the uint8 tensor behind both tables: kept by name for the tests)
+        need = lib.gram_token_tables_bytes(handle)
+        if need <= 0 or os.environ.get("GRAM_TOKEN_TABLES", "1") == "0":
+            return
+        dev = self._device()
+        tables = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        scratch = torch.empty(int(lib.gram_token_tables_workspace_bytes(handle)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.gram_model_build_token_tables(handle, tables.data_ptr(), tables.numel(), scratch.data_ptr(), scratch.numel(),
+                                                         torch.cuda.current_stream(dev).cuda_stream), "gram_model_build_token_tables")
+        keep.append(tables)
+        self._token_tables = tables
 
     def _get_workspace(self, handle, B, N, L, K, max_length) -> torch.Tensor:
         lib = _lib.load()
@@ -585,7 +604,8 @@ class GRAM(nn.Module):
     def max_users_per_call(self, N: int, L: int, K: int, max_length: int, limit: int = 4096, headroom: float = 0.9) -> int:
         """Largest batch B <= limit whose ``generate`` workspace (gram_workspace_bytes) fits the device's free HBM: what the runners
         size their GPU batches with, whatever ``--eval_batch_size`` the loader was built with (results do not depend on the batch a
-        user is scored in).  Memory held by this model's current workspace counts as free (it is re-used or replaced)."""
+        user is scored in).  Memory held by this model's current workspace counts as free (it is re-used or replaced); the handle's
+        token tables (_build_token_tables) are allocated by the time the free memory is read, so they are already subtracted."""
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()

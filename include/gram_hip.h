@@ -158,13 +158,19 @@ int gram_gemm_bf16_lse_split(const void* A, const void* W, float* logits, float*
 int gram_embed_ex_split(const float* table, const void* ids, int ids_are_i64, float* x, void* xb, float* ss, int nblk, int rows,
                         int d, int pieces, void* stream);
 /* ... with the row factor of the 16-bit copy (gram_norm_fusion_t.xs_in of the consumer that follows): xs_out[m] = the factor of the
- * row's OWN rms, xb = pieces(x * xs_out[m]).  xs_out NULL = gram_embed_ex_split. */
+ * row's OWN rms, xb = pieces(x * xs_out[m]).  xs_out NULL = gram_embed_ex_split.  xb NULL: the 16-bit copy is
+ * not written -- x, ss and xs_out are (the first consumer reads a token table instead: gram_model_build_token_tables). */
 int gram_embed_ex_xs(const float* table, const void* ids, int ids_are_i64, float* x, void* xb, float* ss, float* xs_out, int nblk,
                      int rows, int d, int pieces, void* stream);
 int gram_rmsnorm_bf16_split(const float* x, const float* w, void* out_bf16, int rows, int d, float eps, float scale,
                             const float* pos, int N, int L, const int32_t* passage_map, int pieces, void* stream);
 int gram_enc_self_attn_split(const void* qkv, const float* bias, const uint8_t* mask, void* out, int P, int L, int H,
                              int pieces, int64_t qkv_pstride, void* stream);
+/* ... with the q|k|v rows taken from a per-token table (gram_model_build_token_tables) instead of a per-row buffer: row `row` of
+ * passage p is qkv_table + ids[p * L + row] * 3 * inner, ids i64 [P][L], every id a row of the table; qkv_pstride = elements
+ * between the table's pieces.  Same bits as gram_enc_self_attn_split on the gathered rows. */
+int gram_enc_self_attn_rows_split(const void* qkv_table, const int64_t* ids, const float* bias, const uint8_t* mask, void* out,
+                                  int P, int L, int H, int pieces, int64_t qkv_pstride, void* stream);
 /* users/rowpos NULL: all B users, rows b*K + beam; else the live-row form (gram_cross_attn_decode_live, B = n_users).
  * key_bits: gram_mask_key_bits(mask) computed once per generate (the mask is the same for every head, layer and step), or
  * NULL: every workgroup packs its user's bits from the mask bytes itself. */
@@ -177,6 +183,11 @@ int gram_mask_key_bits(const uint8_t* mask, uint32_t* key_bits, int B, int S, vo
 int gram_dec_self_attn_split(const void* qkv, void* kcache, void* vcache, const int32_t* anc, const float* bias, void* out,
                              int R, int n_rows, const int32_t* rows, int H, int t, int Tmax, int pieces, int64_t qkv_pstride,
                              int64_t cache_pstride, void* stream);
+/* ... with the new token's q|k|v taken from a per-token table: compact row r reads qkv_table + qkv_rows[r] * 3 * inner (qkv_rows
+ * i32 [n_rows]: the step's token array, every entry a row of the table).  Cache writes, ancestor reads and `rows` are unchanged. */
+int gram_dec_self_attn_rows_split(const void* qkv_table, const int32_t* qkv_rows, void* kcache, void* vcache, const int32_t* anc,
+                                  const float* bias, void* out, int R, int n_rows, const int32_t* rows, int H, int t, int Tmax,
+                                  int pieces, int64_t qkv_pstride, int64_t cache_pstride, void* stream);
 /* lm_head with the log-softmax normaliser fused: logits as GRAM_EPI_F32, plus for every row and every
  * 64-column block the pair (max, sum exp(x - max)) in lse_part f32 [M][N/64][2]; gram_lse_combine folds
  * them into lse[M] = log sum_v exp(logits[m][v]) without re-reading the logits (gram_row_lse does).
@@ -400,6 +411,22 @@ typedef struct gram_model gram_model_t;
 gram_model_t* gram_model_create(const gram_model_desc_t* desc_host);
 void gram_model_destroy(gram_model_t* m);
 
+/* Layer-0 q|k|v per TOKEN.  T5 has no absolute positions: the first sublayer of each stack norms the raw embedding row of a token
+ * (row-local) and multiplies it by layer 0's W_qkv, so its q|k|v row depends on the token id and the weights only.  The two tables
+ * (encoder, decoder: shared embedding, own W_qkv), each [pieces][vocab][3 * inner] 16-bit planar pieces, are computed once per
+ * handle by the path's own launches (embedding of ids 0 .. vocab-1, the folded norm, the layer-0 QKV GEMM: the same bits a row
+ * holding that token gets today); generate / encode / decode-step calls on a handle that has them read layer 0's q|k|v from the
+ * tables and launch no layer-0 QKV GEMM.  The teacher-forced pass keeps its GEMM.  A handle without tables behaves as before.
+ * gram_token_tables_bytes: bytes of both tables (0: no tables for this model -- unfolded norms);
+ * gram_token_tables_workspace_bytes: scratch of the build (free again once the build's launches have run);
+ * gram_model_build_token_tables: launches the build on `stream` into caller-owned memory (256-B aligned) that must outlive the
+ * handle's use, and records the tables in the handle. */
+int gram_iota_i32(int32_t* out, int n, void* stream); /* out[i] = i, i < n: the build's token ids */
+int64_t gram_token_tables_bytes(const gram_model_t* m);
+int64_t gram_token_tables_workspace_bytes(const gram_model_t* m);
+int gram_model_build_token_tables(gram_model_t* m, void* tables, int64_t tables_bytes, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
 /* Bytes of scratch gram_generate needs for this problem size (256-B aligned carve). */
 int64_t gram_workspace_bytes(const gram_model_t* m, int B, int N, int L, int K, int max_length);
 
@@ -560,6 +587,9 @@ int gram_debug_stream_read_variant(const void* src, size_t bytes, void* sink, in
 /* A/B hook (bench.py): 0 = decode every row in every step like the reference, 1 = live-row compaction (gram_live_rows_t),
  * -1 = what the GRAM_LIVE_ROWS environment variable says (default 1).  Results are bit-identical either way. */
 int gram_debug_set_live_rows(int on);
+/* A/B hook: 0 = layer 0's QKV GEMMs run as on a handle without token tables, 1 = the tables are read where the handle has them,
+ * -1 = what the GRAM_TOKEN_TABLES environment variable says (default 1).  Results are bit-identical either way.  Process-wide. */
+int gram_debug_set_token_tables(int on);
 /* A/B hook (tests/bench_wide_trie.py): which form of the Trie-constrained search step runs.  -1 (default) and 0 = by shape: the
  * one-shot kernel where all K * max_fanout candidates fit on chip, the chunked kernel otherwise; 1 = always the chunked kernel.
  * Results are bit-identical either way.  Process-wide. */

@@ -30,6 +30,7 @@ struct Case {
   int pieces, fold, B, N, L, K, T;  // K: beams, or sequences per user of the teacher-forced pass; T: max_length
   Live live;
   bool comp, capped, logits;  // a gram_compaction_t with cached passages; every stage capped to one piece; teacher-forced logits stored
+  bool tables;                // the handle has token tables: the trace starts with their build (workspace offsets: the build's scratch)
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -55,6 +56,16 @@ const Case kCases[] = {
     {"tf_unfolded_comp", TEACHER_FORCED, 1, 0, 2, 3, 32, 3, 4, OFF, true},
     {"tf_unfolded_comp_logits", TEACHER_FORCED, 1, 0, 2, 3, 32, 3, 4, OFF, true, false, true},
     {"tf_p2", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4},
+    // handles with token tables: layer 0 of the encoder and of a decode step reads them; a capped stage and the teacher-forced pass keep the GEMM
+    {"generate_p1_tables", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, true},
+    {"generate_p2_tables", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, true},
+    {"generate_p2_capped_tables", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, true, false, true},
+    {"generate_greedy_tables", GENERATE, 1, 1, 2, 3, 32, 1, 4, SOME, false, false, false, true},
+    {"generate_rows_32768_tables", GENERATE, 1, 1, 1024, 1, 32, 32, 4, ALL, false, false, false, true},
+    {"generate_comp_tables", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, true, false, false, true},
+    {"encode_passages_tables", ENCODE_PASSAGES, 1, 1, 6, 1, 32, 1, 2, OFF, false, false, false, true},
+    {"decode_step_tables", DECODE_STEP, 1, 1, 2, 3, 32, 4, 4, OFF, false, false, false, true},
+    {"tf_p2_tables", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4, OFF, false, false, false, true},
 };
 
 gram_model_t* make_model(int pieces, int fold) {
@@ -92,6 +103,13 @@ int run(const Case& c) {
   if (c.capped) {
     const int32_t caps[GRAM_STAGE_COUNT] = {1, 1, 1, 1, 1, 1, 1, 1};
     gram_debug_set_stage_pieces(caps, GRAM_STAGE_COUNT);
+  }
+  if (c.tables) {
+    trace_line("gram_token_tables_bytes", gram_token_tables_bytes(m));
+    g_ws_bytes = gram_token_tables_workspace_bytes(m);
+    trace_line("gram_token_tables_workspace_bytes", g_ws_bytes);
+    g_ws = (char*)calloc(g_ws_bytes, 1);
+    trace_line("gram_model_build_token_tables", gram_model_build_token_tables(m, fake(), gram_token_tables_bytes(m), g_ws, g_ws_bytes, st));
   }
   gram_debug_set_live_rows(c.live != OFF);
   if (c.live == SOME) g_live_script = {R - 1, B, R / 2, (B + 1) / 2};

@@ -89,6 +89,11 @@ int gram_enc_self_attn_split(const void* qkv, const float* bias, const uint8_t* 
                              void* st) {
   REC(qkv, bias, mask, out, P, L, H, pieces, ps, st);
 }
+int gram_enc_self_attn_rows_split(const void* table, const int64_t* ids, const float* bias, const uint8_t* mask, void* out, int P, int L, int H,
+                                  int pieces, int64_t ps, void* st) {
+  REC(table, ids, bias, mask, out, P, L, H, pieces, ps, st);
+}
+int gram_iota_i32(int32_t* out, int n, void* st) { REC(out, n, st); }
 int gram_gather_passage_x(const float* cache_x, const int32_t* slot, float* x, int n, int L, int cache_L, int d, void* st) {
   REC(cache_x, slot, x, n, L, cache_L, d, st);
 }
@@ -96,6 +101,11 @@ int gram_mask_key_bits(const uint8_t* mask, uint32_t* key_bits, int B, int S, vo
 int gram_dec_self_attn_split(const void* qkv, void* kcache, void* vcache, const int32_t* anc, const float* bias, void* out, int R, int n_rows,
                              const int32_t* rows, int H, int t, int Tmax, int pieces, int64_t qkv_ps, int64_t cache_ps, void* st) {
   REC(qkv, kcache, vcache, anc, bias, out, R, n_rows, rows, H, t, Tmax, pieces, qkv_ps, cache_ps, st);
+}
+int gram_dec_self_attn_rows_split(const void* table, const int32_t* qkv_rows, void* kcache, void* vcache, const int32_t* anc, const float* bias,
+                                  void* out, int R, int n_rows, const int32_t* rows, int H, int t, int Tmax, int pieces, int64_t qkv_ps,
+                                  int64_t cache_ps, void* st) {
+  REC(table, qkv_rows, kcache, vcache, anc, bias, out, R, n_rows, rows, H, t, Tmax, pieces, qkv_ps, cache_ps, st);
 }
 int gram_cross_attn_decode_split(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int B, int K, int H, int S,
                                  const int32_t* users, const int32_t* rowpos, int pieces, int64_t q_ps, int64_t bank_ps,
