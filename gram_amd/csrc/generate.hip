@@ -496,7 +496,9 @@ extern "C" int gram_debug_set_token_tables(int on) {
 }
 
 extern "C" gram_model_t* gram_model_create(const gram_model_desc_t* d) {
-  if (!d || d->vocab % 128 || d->d_model % 128 || d->d_ff % 128 || d->n_heads < 1 || d->n_heads > 16 ||
+  // (x % 128 alone lets 0 and negative multiples through)
+  if (!d || d->vocab < 128 || d->d_model < 128 || d->d_ff < 128 || d->vocab % 128 || d->d_model % 128 || d->d_ff % 128 ||
+      d->n_heads < 1 || d->n_heads > 16 ||
       (d->n_heads * 64) % 128 || d->d_model > 1024 || d->n_enc_layers < 1 || d->n_dec_layers < 1)
     return nullptr;
   if (d->pieces < 0 || d->pieces > GRAM_MAX_PIECES || (d->pieces > 1 && (!d->lm_head_f32 || !d->fold_norm))) return nullptr;

@@ -407,7 +407,10 @@ typedef struct {
 typedef struct gram_model gram_model_t;
 
 /* Copies the descriptor (not the weights).  Mirrors create_model("gram", config) +
- * load_state_dict (src/model/__init__.py:9-24, gram.py:162-165). */
+ * load_state_dict (src/model/__init__.py:9-24, gram.py:162-165).
+ * NULL for a shape the kernels do not cover: vocab, d_model and d_ff are positive multiples of 128, d_model <= 1024, n_heads even
+ * and <= 16 (inner = 64 n_heads, independent of d_model), at least one layer per stack, pieces 0..2; two pieces need lm_head_f32
+ * and fold_norm (tests/test_model_shapes_host.py). */
 gram_model_t* gram_model_create(const gram_model_desc_t* desc_host);
 void gram_model_destroy(gram_model_t* m);
 

@@ -39,7 +39,10 @@ def gpu():
 
 
 def _cfgs(name):
-    if name == "tiny":
+    """(OracleConfig, T5Config) of a named backbone, or of an OracleConfig as given"""
+    if isinstance(name, O.OracleConfig):
+        oc = name
+    elif name == "tiny":
         oc = O.OracleConfig(vocab_size=256, d_model=128, d_kv=64, d_ff=256, num_layers=2, num_decoder_layers=2, num_heads=2,
                             max_item_num=5)
     elif name == "small":
@@ -48,13 +51,16 @@ def _cfgs(name):
         oc = O.OracleConfig.named(name)
     from gram_amd import T5Config
     gc = T5Config(vocab_size=oc.vocab_size, d_model=oc.d_model, d_ff=oc.d_ff, num_layers=oc.num_layers,
-                  num_decoder_layers=oc.num_decoder_layers, num_heads=oc.num_heads, max_item_num=oc.max_item_num)
+                  num_decoder_layers=oc.num_decoder_layers, num_heads=oc.num_heads, max_item_num=oc.max_item_num,
+                  tie_word_embeddings=oc.tie_word_embeddings)
     return oc, gc
 
 
-def _model(gpu, name, seed):
+def _model(gpu, name, seed, sd=None):
+    """name: a backbone name or an OracleConfig; sd: the weights to load instead of init_state_dict(oc, seed)"""
     oc, gc = _cfgs(name)
-    sd = O.init_state_dict(oc, seed)
+    if sd is None:
+        sd = O.init_state_dict(oc, seed)
     m = gpu.create_model("gram", gc)
     m.load_state_dict(sd)
     return oc, sd, m.to(DEV).eval()
@@ -94,20 +100,27 @@ def _encode_device(m, ids, mask, K=2, max_length=6):
     return _L.deinterleave(enc).double().sum(0).float().cpu().view(B, N * L, d), ws, mk, handle
 
 
-@pytest.mark.parametrize("name,B,N,L", [("tiny", 2, 3, 32), ("tiny", 3, 2, 64), ("small", 2, 2, 128), ("t5-base", 1, 3, 32)])
-def test_encoder_fused_vs_oracle(gpu, name, B, N, L):
-    oc, sd, m = _model(gpu, name, 11)
-    g = torch.Generator().manual_seed(3)
-    ids, mask = _inputs(g, B, N, L, min(oc.vocab_size, 32100))
-    ref = O.encode_fused(sd, oc, ids, mask)
+def _check_encoder(m, ids, mask, ref, tag):
+    """gram_encode_fused (two-piece mode) against the oracle's fused encoder states `ref`, over the valid positions;
+    returns (relative, max abs) deviation"""
+    B = ids.shape[0]
     enc, *_ = _encode_device(m, ids, mask)
     valid = mask.reshape(B, -1)
     err = (enc - ref)[valid]
     rel = err.norm() / ref[valid].norm()
     # hidden states are O(1) after the final RMSNorm
-    print(f"[encoder {name}] rel {float(rel):.2e} max abs {float(err.abs().max()):.2e}")
+    print(f"[encoder {tag}] rel {float(rel):.2e} max abs {float(err.abs().max()):.2e}")
     assert rel < ENC_REL_TOL, float(rel)
     assert err.abs().max() < ENC_ABS_TOL, float(err.abs().max())
+    return float(rel), float(err.abs().max())
+
+
+@pytest.mark.parametrize("name,B,N,L", [("tiny", 2, 3, 32), ("tiny", 3, 2, 64), ("small", 2, 2, 128), ("t5-base", 1, 3, 32)])
+def test_encoder_fused_vs_oracle(gpu, name, B, N, L):
+    oc, sd, m = _model(gpu, name, 11)
+    g = torch.Generator().manual_seed(3)
+    ids, mask = _inputs(g, B, N, L, min(oc.vocab_size, 32100))
+    _check_encoder(m, ids, mask, O.encode_fused(sd, oc, ids, mask), name)
 
 
 def test_encoder_matches_reference_golden(gpu, golden_dir):
@@ -127,11 +140,16 @@ def test_encoder_matches_reference_golden(gpu, golden_dir):
 def test_decode_steps_vs_oracle(gpu, name):
     """gram_decode_step logits for a fixed token stream with beam reorders, vs the oracle's cached
     decoder (= the reference's tuple cache + _reorder_cache, pinned by tests/golden)."""
-    from gram_amd import _lib
     oc, sd, m = _model(gpu, name, 11)
-    g = torch.Generator().manual_seed(8)
-    B, N, L, K, T = 2, 2, 32, 3, 5
+    _check_decode_steps(oc, sd, m, torch.Generator().manual_seed(8), 2, 2, 32, 3, 5)
+
+
+def _check_decode_steps(oc, sd, m, g, B, N, L, K, T):
+    """T steps of gram_decode_step on random tokens, the beams reordered after each, against O.decoder_step; returns the largest
+    deviation of the logits and of the log-probs"""
+    from gram_amd import _lib
     V = oc.vocab_size
+    worst = 0.0
     ids, mask = _inputs(g, B, N, L, min(V, 32100))
     _, ws, mk, handle = _encode_device(m, ids, mask, K=K, max_length=T + 1)
     enc_ref = O.encode_fused(sd, oc, ids, mask)
@@ -155,6 +173,7 @@ def test_decode_steps_vs_oracle(gpu, name):
         print(f"[decode step {t}] max |logit err| {float((got - ref).abs().max()):.2e}  max |log-prob err| {float(lp_err):.2e}")
         assert (got - ref).abs().max() < LOGIT_TOL, (t, float((got - ref).abs().max()))
         assert lp_err < LOGIT_TOL, (t, float(lp_err))
+        worst = max(worst, float((got - ref).abs().max()), float(lp_err))
         parent = torch.cat([torch.randperm(K, generator=g) + b * K for b in range(B)])
         st.reorder(parent)
         a = anc.cpu()
@@ -162,6 +181,7 @@ def test_decode_steps_vs_oracle(gpu, name):
         new[:t, :] = a[:t, parent]
         new[t, :] = parent.int()
         anc.copy_(new)
+    return worst
 
 
 def _random_items(g, n_items, depth_lo, depth_hi, tok_hi):

@@ -87,6 +87,21 @@ def _same_rows(a, b):
     return torch.equal(pad(a), pad(b))
 
 
+def _rescored(m, ids, mask, seqs, K):
+    """The (B * K, width) rows a generate() returned, scored again by the teacher-forced decoder in one score_sequences call: the
+    f64 sums of their token log-probs over the hypothesis length (length_penalty 1), what their sequences_scores must equal."""
+    B = ids.shape[0]
+    lab = seqs[:, 1:].clone()
+    T = lab.shape[1]
+    eos = lab == 1
+    has_eos = eos.any(1)
+    n = torch.where(has_eos, eos.int().argmax(1) + 1, torch.full((B * K,), T))  # labels up to and including EOS
+    hyp_len = torch.where(has_eos, n, torch.full((B * K,), T + 1))  # (as test_sequences_scores_equal_scored_sequences)
+    lab[torch.arange(T)[None, :] >= n[:, None]] = -100
+    seq = m.score_sequences(ids.to(DEV), mask.to(DEV), lab.view(B, K, T).to(DEV)).cpu().view(-1)
+    return seq.double() / hyp_len.double()  # length_penalty 1
+
+
 # ---------------------------------------------------------------------------------------------------------- 1. bench.py's workload
 @pytest.mark.parametrize("mode", [TWO, ONE])  # (the larger, two-piece workspace first)
 def test_generate_at_the_bench_workload(gpu, bench_model, mode):
@@ -117,16 +132,8 @@ def test_generate_at_the_bench_workload(gpu, bench_model, mode):
             assert _same_rows(o["sequences"][j * K:(j + 1) * K], seqs[u * K:(u + 1) * K]), (sub, u)
             assert torch.equal(o["sequences_scores"][j * K:(j + 1) * K].cpu(), scores[u * K:(u + 1) * K]), (sub, u)
     # beam audit: generate and the teacher-forced pass are two independent decoders
-    lab = seqs[:, 1:].clone()
-    T = lab.shape[1]
-    eos = lab == 1
-    has_eos = eos.any(1)
-    n = torch.where(has_eos, eos.int().argmax(1) + 1, torch.full((B * K,), T))  # labels up to and including EOS
-    hyp_len = torch.where(has_eos, n, torch.full((B * K,), T + 1))  # (as test_sequences_scores_equal_scored_sequences)
-    lab[torch.arange(T)[None, :] >= n[:, None]] = -100
-    assert B * K * T >= THRESHOLD
-    seq = m.score_sequences(ids.to(DEV), mask.to(DEV), lab.view(B, K, T).to(DEV)).cpu().view(-1)
-    norm = seq.double() / hyp_len.double()  # length_penalty 1
+    assert B * K * (seqs.shape[1] - 1) >= THRESHOLD
+    norm = _rescored(m, ids, mask, seqs, K)
     audit = float((norm - scores.double()).abs().max())
     print(f"\n[bench workload {mode}] beam audit over {B * K} sequences: max |score diff| {audit:.2e}, "
           f"bit-equal {int((norm.float() == scores).sum())}/{B * K}")
