@@ -82,6 +82,11 @@ class Compaction(C.Structure):
                 ("n_cached", i32), ("cache_L", i32), ("cache_x", vp), ("cache_slot", vp)]
 
 
+class XattnOut(C.Structure):
+    """gram_xattn_out_t: the attention outputs of gram_teacher_forced_ex (device pointers, None = not wanted)"""
+    _fields_ = [("probs", vp), ("layer_probs", vp), ("token_scores", vp), ("passage_scores", vp)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("vocab", i32), ("d_model", i32), ("d_ff", i32), ("n_heads", i32), ("n_enc_layers", i32),
@@ -181,6 +186,12 @@ SIGNATURES = {
     "gram_dec_self_attn_tf_split": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp]),
     "gram_cross_attn_rows_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, vp, vp, vp]),
     "gram_label_logprob_split": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    # cross-attention probabilities and per-passage scores
+    "gram_cross_attn_probs_split": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, vp, vp]),
+    "gram_xattn_head_sum": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "gram_xattn_passage_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
+    "gram_teacher_forced_ex": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Compaction), vp, vp, C.c_int, C.c_int, vp, i64,
+                                         vp, vp, vp, C.POINTER(XattnOut), vp]),
 }
 
 # the `_f16` aliases (gram_hip.h): same signatures as the `_bf16` names

@@ -804,9 +804,11 @@ Workspace carve_tf(const gram_model* m, void* ws, int B, int N, int L, int C, in
 
 // The decoder layers over R = B * Q rows (Q = C * T per user): decode_step's, with the stepped self-attention replaced by the
 // whole-sequence one and the cross-attention taking all Q rows of a user; then the lm_head with its LSE partials (logits stored when
-// given) and their combination.
+// given) and their combination.  attn != NULL (gram_teacher_forced_ex): every layer's cross-attention is followed by its probabilities
+// (xattn_probs.hip, on the same r.qx and K bank) and their head sum; the passage scores follow the last layer.  These launches only read
+// what the pass computes.
 int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, const uint8_t* mask, int B, int N, int L, int Q, int T,
-               float* logits, void* st) {
+               float* logits, const gram_xattn_out_t* attn, void* st) {
   const gram_model_desc_t& c = m->d;
   const int H = c.n_heads, R = B * Q, S = N * L;
   const size_t bank_layer = (size_t)B * H * S * 64;
@@ -815,10 +817,16 @@ int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, c
       m, w, tokens, R, /*qkv0_from_table=*/false,
       [&](int) { return gram_dec_self_attn_tf_split(r.qkv, c.dec_bias_f32, r.attn, R / T, T, H, w.pieces, r.ps_qkv, st); },
       [&](int i) {
-        return gram_cross_attn_rows_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S, w.pieces,
-                                          r.ps_qx, w.ps_bank, w.key_bits, w.rowmap, st);
+        TRY(gram_cross_attn_rows_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S, w.pieces,
+                                       r.ps_qx, w.ps_bank, w.key_bits, w.rowmap, st));
+        if (!attn) return 0;
+        float* p = attn->probs ? attn->probs + (size_t)i * B * H * Q * S : attn->layer_probs;
+        TRY(gram_cross_attn_probs_split(r.qx, w.bank_k + i * bank_layer, mask, p, B, Q, H, S, w.pieces, r.ps_qx, w.ps_bank, w.key_bits, st));
+        return attn->token_scores ? gram_xattn_head_sum(p, attn->token_scores, B, Q, H, S, /*first=*/i == 0, st) : 0;
       },
       st));
+  if (attn && attn->passage_scores)
+    TRY(gram_xattn_passage_scores(attn->token_scores, mask, attn->passage_scores, B, Q, N, L, (float)(c.n_dec_layers * H), st));
   TRY(lm_head(m, w, R, logits, w.lse_part, st));
   return gram_lse_combine(w.lse_part, w.lse, R, c.vocab / 64, st);
 }
@@ -834,14 +842,25 @@ extern "C" int gram_teacher_forced(const gram_model_t* m, const int64_t* input_i
                                    const gram_compaction_t* comp, const int32_t* dec_ids, const int32_t* labels, int C, int T,
                                    void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
                                    void* stream) {
+  return gram_teacher_forced_ex(m, input_ids, mask, B, N, L, comp, dec_ids, labels, C, T, workspace, workspace_bytes, logits, token_logp,
+                                seq_logp, nullptr, stream);
+}
+
+extern "C" int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                                      const gram_compaction_t* comp, const int32_t* dec_ids, const int32_t* labels, int C, int T,
+                                      void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
+                                      const gram_xattn_out_t* attn, void* stream) {
   TRY(check_shapes_tf(m, B, N, L, C, T));
   if (!mask || !dec_ids || !labels || !token_logp || !seq_logp || (!comp && !input_ids)) return GRAM_E_ARG;
+  // the attention outputs are the caller's memory: one layer of probabilities at least, and the passage scores are a reduction of the
+  // token scores
+  if (attn && ((!attn->probs && !attn->layer_probs) || (attn->passage_scores && !attn->token_scores))) return GRAM_E_ARG;
   TRY(check_compaction(comp, B, N));  // (as gram_generate_ex)
   Workspace w = carve_tf(m, workspace, B, N, L, C, T);
   if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
   const gram_model_desc_t& c = m->d;
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
-  TRY(decoder_tf(m, w, dec_ids, mask, B, N, L, C * T, T, logits, stream));
+  TRY(decoder_tf(m, w, dec_ids, mask, B, N, L, C * T, T, logits, attn, stream));
   return gram_label_logprob_split(w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, labels, B * C, T, c.vocab, w.pieces,
                                   token_logp, seq_logp, stream);
 }

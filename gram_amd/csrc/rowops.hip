@@ -455,3 +455,71 @@ extern "C" int gram_gather_passage_x(const float* cache_x, const int32_t* slot, 
   GRAM_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- reducers of the cross-attention probabilities (xattn_probs.hip): the per-passage scores of GRAM.get_crossattention_scores ------
+namespace {
+
+// acc[b][i][s] = (first ? 0 : acc[b][i][s]) + probs[b][0][i][s] + probs[b][1][i][s] + ...: heads in order, four keys per thread
+__global__ __launch_bounds__(256) void xattn_head_sum_kernel(const float* __restrict__ probs, float* __restrict__ acc, int64_t nchunks,
+                                                            int64_t row_chunks /* Q * S / 4 */, int H, int first) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= nchunks) return;
+  const int64_t b = idx / row_chunks, r = idx - b * row_chunks;
+  const f32x4* p = reinterpret_cast<const f32x4*>(probs) + b * H * row_chunks + r;
+  f32x4 t = first ? (f32x4){0.f, 0.f, 0.f, 0.f} : reinterpret_cast<const f32x4*>(acc)[idx];
+  for (int h = 0; h < H; ++h) t += p[(int64_t)h * row_chunks];
+  reinterpret_cast<f32x4*>(acc)[idx] = t;
+}
+
+// One wave per (user, row, passage): lane sums of the valid keys l = lane, lane + 64, ... in order, then wave_sum's fixed butterfly.
+__global__ __launch_bounds__(256) void xattn_passage_scores_kernel(const float* __restrict__ acc, const uint8_t* __restrict__ mask,
+                                                                  float* __restrict__ scores, int64_t items, int Q, int N, int L,
+                                                                  float denom) {
+  const int64_t it = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (it >= items) return;  // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  const int64_t row = it / N;  // b * Q + i
+  const int n = (int)(it - row * N);
+  const int64_t b = row / Q;
+  const float* a = acc + (row * N + n) * L;
+  const uint8_t* mk = mask + (b * N + n) * L;
+  float s = 0.f;
+  int cnt = 0;
+  for (int l = lane; l < L; l += 64)
+    if (mk[l]) {
+      s += a[l];
+      ++cnt;
+    }
+  s = wave_sum(s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  // a passage without a valid key: the reference's 0 / 0, written as the NaN it is (not left to a division the compiler may fold)
+  if (lane == 0) scores[it] = cnt ? s / ((float)cnt * denom) : __uint_as_float(0x7fc00000u);
+}
+
+}  // namespace
+
+extern "C" int gram_xattn_head_sum(const float* probs, float* acc, int B, int Q, int H, int S, int first, void* stream) {
+  if (!probs || !acc || B < 1 || Q < 1 || H < 1 || S < 4 || (S & 3) || (reinterpret_cast<uintptr_t>(probs) & 15) ||
+      (reinterpret_cast<uintptr_t>(acc) & 15))
+    return GRAM_E_ARG;
+  const int64_t row_chunks = (int64_t)Q * (S / 4), nchunks = (int64_t)B * row_chunks;
+  if ((nchunks + 255) / 256 > 0x7fffffffLL) return GRAM_E_ARG;
+  gram_prof::Scope prof(GRAM_K_ROWOPS, (hipStream_t)stream, 16.0 * nchunks * (H + 1 + (first ? 0 : 1)));
+  hipLaunchKernelGGL(xattn_head_sum_kernel, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, probs, acc,
+                     nchunks, row_chunks, H, first);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int gram_xattn_passage_scores(const float* acc, const uint8_t* mask, float* scores, int B, int Q, int N, int L, float denom,
+                                         void* stream) {
+  if (!acc || !mask || !scores || B < 1 || Q < 1 || N < 1 || L < 1 || !(denom > 0.f)) return GRAM_E_ARG;
+  const int64_t items = (int64_t)B * Q * N;
+  if ((items + 3) / 4 > 0x7fffffffLL) return GRAM_E_ARG;
+  gram_prof::Scope prof(GRAM_K_ROWOPS, (hipStream_t)stream, 5.0 * items * L);
+  hipLaunchKernelGGL(xattn_passage_scores_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream, acc, mask,
+                     scores, items, Q, N, L, denom);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}

@@ -349,9 +349,10 @@ class GRAM(nn.Module):
         return labels
 
     def max_users_per_call_tf(self, N: int, L: int, C_: int, T: int, want_logits: bool = False, limit: int = 1 << 20,
-                              headroom: float = 0.9) -> int:
+                              headroom: float = 0.9, extra_per_user: int = 0) -> int:
         """Largest B <= limit whose teacher-forced workspace (gram_workspace_bytes_tf) and outputs fit the free HBM, net of what a
-        reserved passage cache will still allocate (``reserve_passage_cache``)."""
+        reserved passage cache will still allocate (``reserve_passage_cache``).  ``extra_per_user``: further output bytes per user
+        (the attention buffers of ``cross_attentions`` / ``passage_attention``)."""
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()
@@ -362,7 +363,7 @@ class GRAM(nn.Module):
         pc_have = 0 if self._pcache is None else int(self._pcache["x"].shape[0])
         pc_more = max(0, int(getattr(self, "_pcache_reserve", 0)) - pc_have)
         budget = int(free * headroom) - pc_more * self._CACHE_L * (self.config.d_model * 4 + 4)
-        per_user_out = C_ * T * 4 * (2 + (self.config.vocab_size if want_logits else 0))
+        per_user_out = C_ * T * 4 * (2 + (self.config.vocab_size if want_logits else 0)) + int(extra_per_user)
 
         def need(b):
             w = lib.gram_workspace_bytes_tf(handle, b, N, Lp, C_, T)
@@ -379,8 +380,11 @@ class GRAM(nn.Module):
                 hi = mid - 1
         return lo
 
-    def _teacher_forced(self, input_ids, attention_mask, dec, lab, want_logits: bool, users_per_call: Optional[int] = None):
-        """(logits (B,C,T,V) or empty, token log-probs (B,C,T), sequence sums (B,C)) over user chunks of torch.ops.gram.teacher_forced."""
+    def _tf_chunks(self, input_ids, attention_mask, dec, lab, call, want_logits: bool = False, extra_bytes=None,
+                   users_per_call: Optional[int] = None):
+        """The teacher-forced pass over user chunks whose workspace and outputs fit the free HBM: ``call(ids, mask, handle, workspace,
+        dec, lab, compaction fields)`` per chunk -> (the list of its results, the padded passage length).  ``extra_bytes(Lp)``: further
+        output bytes per user."""
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()
@@ -396,7 +400,8 @@ class GRAM(nn.Module):
             mask = torch.nn.functional.pad(mask, (0, Lp - L))
         dec = dec.to(dev, torch.int32).contiguous()
         lab = lab.to(dev, torch.int32).contiguous()
-        step = int(users_per_call) if users_per_call else self.max_users_per_call_tf(N, Lp, Cn, T, want_logits, limit=B)
+        step = int(users_per_call) if users_per_call else self.max_users_per_call_tf(N, Lp, Cn, T, want_logits, limit=B,
+                                                                                     extra_per_user=extra_bytes(Lp) if extra_bytes else 0)
         from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
         outs = []
         for b0 in range(0, B, max(1, step)):
@@ -410,12 +415,108 @@ class GRAM(nn.Module):
                                         f"N*L <= 4096, T <= {_lib.GRAM_MAX_DEC_LEN})")
             ws = self._ensure_workspace(need)
             ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
-            outs.append(torch.ops.gram.teacher_forced(
-                cid, cmask, int(handle), ws, dec[b0:b1], lab[b0:b1], int(self.config.vocab_size), bool(want_logits), ct["comp_map"],
-                ct["comp_ids"], ct["comp_mask"], ct["cache_slot"], ct["cache_x"], int(ct["n_cached"]), int(ct["cache_L"])))
+            # (a chunk's slice of dec / lab starts wherever the rows before it end: a copy is 16-byte aligned, as the ops require)
+            cdec, clab = (dec[b0:b1], lab[b0:b1]) if dec[b0:b1].data_ptr() % 16 == 0 else (dec[b0:b1].clone(), lab[b0:b1].clone())
+            outs.append(call(cid, cmask, int(handle), ws, cdec, clab, ct["comp_map"], ct["comp_ids"], ct["comp_mask"], ct["cache_slot"],
+                             ct["cache_x"], int(ct["n_cached"]), int(ct["cache_L"])))
+        return outs, Lp
+
+    def _teacher_forced(self, input_ids, attention_mask, dec, lab, want_logits: bool, users_per_call: Optional[int] = None):
+        """(logits (B,C,T,V) or empty, token log-probs (B,C,T), sequence sums (B,C)) over user chunks of torch.ops.gram.teacher_forced."""
+        V = int(self.config.vocab_size)
+        outs, _Lp = self._tf_chunks(input_ids, attention_mask, dec, lab,
+                                    lambda cid, cmask, handle, ws, cdec, clab, *comp: torch.ops.gram.teacher_forced(
+                                        cid, cmask, handle, ws, cdec, clab, V, bool(want_logits), *comp),
+                                    want_logits=want_logits, users_per_call=users_per_call)
         if len(outs) == 1:
             return outs[0]
         return tuple(torch.cat([o[i] for o in outs]) if (i or want_logits) else outs[0][0] for i in range(3))
+
+    # ------------------------------------------------------------------ cross-attention probabilities, per-passage scores
+    def _teacher_forced_attn(self, input_ids, attention_mask, dec, lab, want_probs: bool, want_scores: bool,
+                             users_per_call: Optional[int] = None):
+        """(probs (nl,B,H,C*T,N*Lp) or None, token_scores (B,C*T,N*Lp) or None, passage_scores (B,C*T,N) or None, Lp) over user chunks
+        of torch.ops.gram.teacher_forced_attn, with the attention buffers counted in the chunk budget."""
+        if attention_mask.shape != input_ids.shape:
+            raise ValueError("attention_mask must have input_ids' shape (B, N, L)")
+        V, H, nl = int(self.config.vocab_size), int(self.config.num_heads), int(self.config.num_decoder_layers)
+        N, Q = input_ids.shape[1], dec.shape[1] * dec.shape[2]
+
+        def attn_bytes(Lp):  # per user: every layer's probabilities or one layer of scratch, the token and passage scores
+            return 4 * Q * ((nl if want_probs else 1) * H * N * Lp + ((N * Lp + N) if want_scores else 0))
+
+        outs, Lp = self._tf_chunks(input_ids, attention_mask, dec, lab,
+                                   lambda cid, cmask, handle, ws, cdec, clab, *comp: torch.ops.gram.teacher_forced_attn(
+                                       cid, cmask, handle, ws, cdec, clab, V, nl, H, bool(want_probs), bool(want_scores), *comp),
+                                   extra_bytes=attn_bytes, users_per_call=users_per_call)
+        probs = (outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs], 1)) if want_probs else None
+        tsc, psc = ((outs[0][i] if len(outs) == 1 else torch.cat([o[i] for o in outs])) if want_scores else None for i in (1, 2))
+        return probs, tsc, psc, Lp
+
+    @torch.no_grad()
+    def cross_attentions(self, input_ids, attention_mask, labels=None, decoder_input_ids=None, users_per_call: Optional[int] = None):
+        """HF's ``cross_attentions`` of the teacher-forced pass: a tuple of ``num_decoder_layers`` fp32 tensors (B, H, T, N*L), the
+        softmax weights of every decoder position over the user's fused keys (masked keys exactly 0; a user without a valid key:
+        uniform).  labels (B, T) in label form (decoder inputs = ``shift_right(labels)``) or decoder_input_ids (B, T) as given;
+        ``decoder_input_ids = zeros(B, 1)`` is the first generated token's cross-attention -- every beam's at step 0 -- which
+        ``get_crossattention_scores`` consumes.  Computed on the device by a kernel of its own next to the pass's cross-attention
+        (the same operands and product order); a user's result does not depend on the chunk (``users_per_call``)."""
+        if self._device().type != "cuda":
+            raise NotImplementedError("gram_amd.GRAM.cross_attentions runs on a ROCm device (model.to('cuda')); there is no CPU path")
+        if labels is None and decoder_input_ids is None:
+            raise ValueError("cross_attentions needs labels or decoder_input_ids")
+        if input_ids is None or input_ids.dim() != 3:
+            raise ValueError("input_ids must be (B, N, L)")
+        dev = self._device()
+        lab = None if labels is None else self._check_labels(labels.to(dev))
+        dec = shift_right(lab) if decoder_input_ids is None else decoder_input_ids.to(dev)
+        if dec.dim() != 2 or dec.shape[0] != input_ids.shape[0] or (lab is not None and lab.shape != dec.shape):
+            raise ValueError("decoder_input_ids / labels must be (B, T) with B = input_ids.shape[0]")
+        lab_k = lab if lab is not None else torch.full_like(dec, -100)
+        probs, _t, _p, Lp = self._teacher_forced_attn(input_ids, attention_mask, dec[:, None, :], lab_k[:, None, :], True, False, users_per_call)
+        nl, B, H, T, _ = probs.shape
+        N, L = input_ids.shape[1:]
+        probs = probs.view(nl, B, H, T, N, Lp)[..., :L].reshape(nl, B, H, T, N * L)  # (a view when L % 32 == 0)
+        return tuple(probs[i] for i in range(nl))
+
+    @torch.no_grad()
+    def passage_attention(self, input_ids, attention_mask, labels, users_per_call: Optional[int] = None):
+        """Which passages the decoder read, at every position of given sequences: labels (B, C, T) as for ``score_sequences`` (a
+        generated sequence as labels gives the attribution of that hypothesis).  Returns ``(token_scores (B, C, T, N, L),
+        passage_scores (B, C, T, N))``: the cross-attention weights summed over decoder layers and heads, and per passage their sum
+        over its valid keys / (valid keys * layers * heads) -- ``get_crossattention_scores``'s two results at every position; NaN for a
+        passage without a valid key.  Reduced on the device, one layer of probabilities held at a time; a user's result does not
+        depend on the chunk."""
+        if self._device().type != "cuda":
+            raise NotImplementedError("gram_amd.GRAM.passage_attention runs on a ROCm device (model.to('cuda')); there is no CPU path")
+        if input_ids.dim() != 3 or labels.dim() != 3 or labels.shape[0] != input_ids.shape[0]:
+            raise ValueError("input_ids must be (B, N, L) and labels (B, C, T)")
+        lab = self._check_labels(labels.to(self._device()))
+        _pr, tsc, psc, Lp = self._teacher_forced_attn(input_ids, attention_mask, shift_right(lab), lab, False, True, users_per_call)
+        B, N, L = input_ids.shape
+        _, Cn, T = lab.shape
+        return tsc.view(B, Cn, T, N, Lp)[..., :L], psc.view(B, Cn, T, N)
+
+    @staticmethod
+    def get_crossattention_scores(cross_attentions, attention_mask, b_idx: int = 0):
+        """The reference's ``GRAM.get_crossattention_scores`` (src/model/gram.py:109-138): how much the FIRST generated token attends
+        to every key and to every passage of user ``b_idx``.  cross_attentions: ``[token][layer]`` of (B, H, 1, N*L) tensors --
+        ``[model.cross_attentions(ids, mask, decoder_input_ids=zeros(B, 1))]`` --, attention_mask (1, N, L): that user's.  Returns
+        ``(token_scores, scores)``: the weights summed over layers and heads as a nested list [N][L] (masked keys 0), and a (1, N)
+        tensor of per-passage means, sum over the passage's valid keys / (valid keys * layers * heads) (NaN for a passage without
+        one).  Plain torch: works on CPU tensors."""
+        valid = torch.as_tensor(attention_mask).ne(0)
+        if valid.dim() != 3 or valid.shape[0] != 1:
+            raise ValueError("attention_mask must be (1, N, L): the mask of user b_idx")
+        w = torch.stack([layer[b_idx] for layer in cross_attentions[0]])  # (layers, H, 1, N*L): the first token
+        if w.dim() != 4 or w.shape[2] != 1:
+            raise ValueError("cross_attentions must hold (B, H, 1, N*L) tensors: one decoder position")
+        n_layers, H = w.shape[:2]
+        _, N, L = valid.shape
+        w = w.reshape(1, n_layers, H, N, L).masked_fill(~valid.to(w.device)[:, None, None], 0.0)
+        per_key = w.sum(dim=(1, 2))  # (1, N, L)
+        scores = w.sum(dim=(1, 2, 4)) / (valid.to(w.device).sum(dim=2) * (n_layers * H))
+        return per_key[0].tolist(), scores
 
     # ------------------------------------------------------------------ device packing
     def _device(self) -> torch.device:

@@ -8,6 +8,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
     torch.ops.gram.generate          GRAM.generate's whole path (gram_generate_ex) -- what ``GRAM.generate`` calls
     torch.ops.gram.teacher_forced    the teacher-forced decoder pass (gram_teacher_forced) -- ``GRAM.forward(labels=...)`` and
                                      ``GRAM.score_sequences``
+    torch.ops.gram.teacher_forced_attn  the same pass with its cross-attention probabilities (gram_teacher_forced_ex) --
+                                     ``GRAM.cross_attentions`` and ``GRAM.passage_attention``
     torch.ops.gram.linear            nn.Linear without bias: A @ W^T on the 16-bit MFMA (gram_gemm_bf16, 16-bit epilogue)
     torch.ops.gram.enc_self_attn     T5Attention self branch on (P*L, 3*inner) q|k|v rows (gram_enc_self_attn)
     torch.ops.gram.cross_attn_decode the fusion read of one decoder layer and step over the beam-shared bank
@@ -140,6 +142,68 @@ def _(input_ids, attention_mask, handle, workspace, decoder_input_ids, labels, v
     f = dict(dtype=torch.float32)
     return (decoder_input_ids.new_empty((B, Cn, T, vocab_size) if want_logits else (0,), **f),
             decoder_input_ids.new_empty(B, Cn, T, **f), decoder_input_ids.new_empty(B, Cn, **f))
+
+
+@torch.library.custom_op("gram::teacher_forced_attn", mutates_args=("workspace",), device_types="cuda")
+def teacher_forced_attn(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, decoder_input_ids: Tensor,
+                        labels: Tensor, vocab_size: int, n_dec_layers: int, n_heads: int, want_probs: bool, want_scores: bool,
+                        comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor],
+                        cache_x: Optional[Tensor], n_cached: int, cache_L: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """The teacher-forced pass of ``teacher_forced`` (same inputs, validated the same way) with its cross-attention probabilities
+    (gram_teacher_forced_ex).  ``n_dec_layers`` / ``n_heads`` are the model's (they size the outputs).  Returns
+    (probs f32 (n_dec_layers, B, H, C*T, N*L) -- empty unless want_probs: then one layer at a time lives in a scratch tensor --,
+    token_scores f32 (B, C*T, N*L) = their sum over layers and heads, passage_scores f32 (B, C*T, N) = per passage the sum over its
+    valid keys / (valid keys * n_dec_layers * n_heads), NaN for a passage without one -- both empty unless want_scores)."""
+    lib = _lib.load()
+    dev = input_ids.device
+    if input_ids.dim() != 3 or decoder_input_ids.dim() != 3:
+        raise ValueError("teacher_forced_attn: input_ids must be (B, N, L) and decoder_input_ids (B, C, T)")
+    if not (want_probs or want_scores):
+        raise ValueError("teacher_forced_attn: nothing requested (want_probs / want_scores)")
+    B, N, L = input_ids.shape
+    Bd, Cn, T = decoder_input_ids.shape
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    _check("decoder_input_ids", decoder_input_ids, torch.int32, (B, None, None), dev)
+    _check("labels", labels, torch.int32, (B, Cn, T), dev)
+    if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN or Cn < 1 or n_dec_layers < 1 or n_heads < 1:
+        raise ValueError(f"teacher_forced_attn: need 1 <= T <= {_lib.GRAM_MAX_DEC_LEN}, C >= 1, n_dec_layers >= 1, n_heads >= 1")
+    lo_d, hi_d, hi_l = torch.stack([decoder_input_ids.min(), decoder_input_ids.max(), labels.max()]).tolist()
+    if lo_d < 0 or hi_d >= vocab_size or hi_l >= vocab_size:
+        raise ValueError(f"teacher_forced_attn: decoder_input_ids must lie in [0, {vocab_size}) and labels below {vocab_size}")
+    comp = None
+    if comp_map is not None:
+        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
+                               _p(cache_slot))
+    Q, S = Cn * T, N * L
+    f = dict(dtype=torch.float32, device=dev)
+    probs = torch.empty((n_dec_layers, B, n_heads, Q, S) if want_probs else (0,), **f)
+    layer = None if want_probs else torch.empty(B, n_heads, Q, S, **f)
+    tsc = torch.empty((B, Q, S) if want_scores else (0,), **f)
+    psc = torch.empty((B, Q, N) if want_scores else (0,), **f)
+    tok = torch.empty(B, Cn, T, **f)
+    seq = torch.empty(B, Cn, **f)
+    attn = _lib.XattnOut(probs.data_ptr() if want_probs else None, _p(layer), tsc.data_ptr() if want_scores else None,
+                         psc.data_ptr() if want_scores else None)
+    with torch.cuda.device(dev):
+        rc = lib.gram_teacher_forced_ex(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
+                                        C.byref(comp) if comp is not None else None, decoder_input_ids.data_ptr(), labels.data_ptr(),
+                                        Cn, T, workspace.data_ptr(), workspace.numel(), None, tok.data_ptr(), seq.data_ptr(),
+                                        C.byref(attn), _stream(input_ids))
+    _lib.check(rc, "gram_teacher_forced_ex")
+    return probs, tsc, psc
+
+
+@teacher_forced_attn.register_fake
+def _(input_ids, attention_mask, handle, workspace, decoder_input_ids, labels, vocab_size, n_dec_layers, n_heads, want_probs, want_scores,
+      comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L):
+    B, N, L = input_ids.shape
+    _, Cn, T = decoder_input_ids.shape
+    Q, S = Cn * T, N * L
+    f = dict(dtype=torch.float32)
+    return (decoder_input_ids.new_empty((n_dec_layers, B, n_heads, Q, S) if want_probs else (0,), **f),
+            decoder_input_ids.new_empty((B, Q, S) if want_scores else (0,), **f),
+            decoder_input_ids.new_empty((B, Q, N) if want_scores else (0,), **f))
 
 
 # ---------------------------------------------------------------------------------------------- linear
@@ -275,4 +339,4 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
-__all__ = ["generate", "teacher_forced", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]
+__all__ = ["generate", "teacher_forced", "teacher_forced_attn", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]

@@ -545,6 +545,44 @@ int gram_label_logprob_split(const void* hidden, const void* lm_head_bf16, const
                              const int32_t* labels, int n_seq, int T, int V, int pieces, float* token_logp, float* seq_logp,
                              void* stream);
 
+/* ---- cross-attention probabilities and per-passage scores (GRAM.get_crossattention_scores) ---------------------------------
+ * HF's `cross_attentions` (T5Attention.forward's attn_weights, gram_t5_modeling.py:600-603,629) and the reference's reduction of
+ * them to one score per passage (src/model/gram.py:109-138), for the teacher-forced pass. */
+
+/* probs f32 [B][H][Q][S]: probs[b][h][i][s] = softmax over s of (q[b*Q + i] . k[b][h][s] + (mask[b][s] ? 0 : finfo(float32).min)),
+ * scores unscaled.  q, k_layer, mask, pieces, the strides and key_bits as gram_cross_attn_rows_split takes them (the same operand
+ * pieces and product order as the cross-attention kernel), any Q >= 1, B <= 65535.  Masked keys of a user with a valid key are
+ * exactly 0.0; a user without one gets 1 / S everywhere.  A row's bits depend on that row, its user's K and mask only.
+ * S % 32 == 0, S <= 4096, pieces 1 or 2, pointers 16-byte aligned: otherwise GRAM_E_ARG before any launch. */
+int gram_cross_attn_probs_split(const void* q, const void* k_layer, const uint8_t* mask, float* probs, int B, int Q, int H, int S,
+                                int pieces, int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits, void* stream);
+
+/* acc[b][i][s] = (first ? 0 : acc[b][i][s]) + the sum over h, in head order, of probs[b][h][i][s]; acc f32 [B][Q][S], S % 4 == 0. */
+int gram_xattn_head_sum(const float* probs, float* acc, int B, int Q, int H, int S, int first, void* stream);
+
+/* scores[b][i][n] = (sum over l with mask[b][n][l] != 0 of acc[b][i][n*L + l]) / (count(b, n) * denom), count = the passage's valid
+ * keys; NaN when count == 0 (the reference's 0 / 0).  mask u8 [B][N][L], scores f32 [B][Q][N]; fixed summation order. */
+int gram_xattn_passage_scores(const float* acc, const uint8_t* mask, float* scores, int B, int Q, int N, int L, float denom,
+                              void* stream);
+
+/* Attention outputs of gram_teacher_forced_ex, all caller-owned device memory (Q = C * T rows per user, S = N * L keys). */
+typedef struct {
+  float* probs;          /* [n_dec_layers][B][H][Q][S]: every layer's probabilities, or NULL                            */
+  float* layer_probs;    /* [B][H][Q][S]: scratch for one layer; required when probs == NULL                             */
+  float* token_scores;   /* [B][Q][S]: the sum over layers and heads, or NULL                                            */
+  float* passage_scores; /* [B][Q][N]: gram_xattn_passage_scores of token_scores, denom = n_dec_layers * H; or NULL      */
+} gram_xattn_out_t;
+
+/* gram_teacher_forced with the cross-attention probabilities of the pass.  attn_host == NULL: gram_teacher_forced itself (which is
+ * this call).  Otherwise every decoder layer's cross-attention is followed by gram_cross_attn_probs_split on the same queries and
+ * K bank and, with token_scores, gram_xattn_head_sum; gram_xattn_passage_scores follows the last layer.  The workspace and every
+ * other output are those of gram_teacher_forced.  probs and layer_probs both NULL, or passage_scores without token_scores:
+ * GRAM_E_ARG before any launch. */
+int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                           const gram_compaction_t* compaction_host, const int32_t* dec_ids, const int32_t* labels, int C, int T,
+                           void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
+                           const gram_xattn_out_t* attn_host, void* stream);
+
 /* ---- live per-kernel timing (bench.py) ------------------------------------------------ */
 enum gram_kernel_kind {
   GRAM_K_GEMM = 0,          /* work = 2*M*N*K flops per launch                              */

@@ -31,6 +31,7 @@ struct Case {
   Live live;
   bool comp, capped, logits;  // a gram_compaction_t with cached passages; every stage capped to one piece; teacher-forced logits stored
   bool tables;                // the handle has token tables: the trace starts with their build (workspace offsets: the build's scratch)
+  int attn;                   // gram_teacher_forced_ex: 1 = every layer's probabilities, 2 = one layer of scratch + token and passage scores
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -66,6 +67,9 @@ const Case kCases[] = {
     {"encode_passages_tables", ENCODE_PASSAGES, 1, 1, 6, 1, 32, 1, 2, OFF, false, false, false, true},
     {"decode_step_tables", DECODE_STEP, 1, 1, 2, 3, 32, 4, 4, OFF, false, false, false, true},
     {"tf_p2_tables", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4, OFF, false, false, false, true},
+    // gram_teacher_forced_ex with attention outputs: the train of tf_folded / tf_p2 plus, per layer, the probabilities and their head sum
+    {"tf_attn_probs", TEACHER_FORCED, 1, 1, 2, 3, 32, 3, 4, OFF, false, false, false, false, 1},
+    {"tf_p2_attn_scores", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4, OFF, false, false, false, false, 2},
 };
 
 gram_model_t* make_model(int pieces, int fold) {
@@ -132,6 +136,12 @@ int run(const Case& c) {
     case DECODE_STEP:
       return gram_decode_step(m, (int32_t*)io[0], (int32_t*)io[1], mask, B, N, L, K, T, /*t=*/1, g_ws, g_ws_bytes, (float*)io[2], st);
     case TEACHER_FORCED:
+      if (c.attn) {
+        const gram_xattn_out_t attn = c.attn == 1 ? gram_xattn_out_t{fake<float>(), nullptr, nullptr, nullptr}
+                                                  : gram_xattn_out_t{nullptr, fake<float>(), fake<float>(), fake<float>()};
+        return gram_teacher_forced_ex(m, ids, mask, B, N, L, nullptr, (int32_t*)io[0], (int32_t*)io[1], K, T, g_ws, g_ws_bytes, nullptr,
+                                      (float*)io[3], (float*)io[4], &attn, st);
+      }
       return gram_teacher_forced(m, ids, mask, B, N, L, c.comp ? &comp : nullptr, (int32_t*)io[0], (int32_t*)io[1], K, T, g_ws, g_ws_bytes,
                                  c.logits ? (float*)io[2] : nullptr, (float*)io[3], (float*)io[4], st);
   }

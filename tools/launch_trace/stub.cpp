@@ -123,6 +123,16 @@ int gram_label_logprob_split(const void* hidden, const void* lm16, const float* 
                              int T, int V, int pieces, float* token_logp, float* seq_logp, void* st) {
   REC(hidden, lm16, lm32, d, lse, labels, n_seq, T, V, pieces, token_logp, seq_logp, st);
 }
+int gram_cross_attn_probs_split(const void* q, const void* k, const uint8_t* mask, float* probs, int B, int Q, int H, int S, int pieces,
+                                int64_t q_ps, int64_t bank_ps, const uint32_t* key_bits, void* st) {
+  REC(q, k, mask, probs, B, Q, H, S, pieces, q_ps, bank_ps, key_bits, st);
+}
+int gram_xattn_head_sum(const float* probs, float* acc, int B, int Q, int H, int S, int first, void* st) {
+  REC(probs, acc, B, Q, H, S, first, st);
+}
+int gram_xattn_passage_scores(const float* acc, const uint8_t* mask, float* scores, int B, int Q, int N, int L, float denom, void* st) {
+  REC(acc, mask, scores, B, Q, N, L, denom, st);
+}
 int gram_lse_combine(const float* lse_part, float* lse, int M, int nblk, void* st) { REC(lse_part, lse, M, nblk, st); }
 int gram_beam_init(const gram_beam_state_t* s, const gram_trie_t* trie, int start, void* st) { REC(s, trie, start, st); }
 int gram_beam_step_sparse(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, int d, const float* lse,
