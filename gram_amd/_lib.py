@@ -19,6 +19,8 @@ EPI_BF16, EPI_BF16_RELU, EPI_F32_ADD, EPI_F32, EPI_KV_BANK = range(5)
 K_GEMM, K_ENC_ATTN, K_CROSS_ATTN, K_DEC_SELF_ATTN, K_ROWOPS, K_LSE, K_BEAM = range(7)
 E_ARG, E_WORKSPACE, E_BEAM, E_NONFINITE = -1, -2, -3, -4
 ABI_VERSION = 7
+GRAM_MAX_USER_ITEMS = 4096   # entries of one user's item list (gram_user_items_t)
+ITEMS_EXCLUDE, ITEMS_ALLOW = 0, 1
 # two-piece mode (gram_hip.h, gram_split_t): 16-bit pieces per value -> MFMA products per product
 MAX_PIECES = 2
 SPLIT_NPROD = (0, 1, 3)
@@ -80,6 +82,11 @@ class NormFusion(C.Structure):
 class Compaction(C.Structure):
     _fields_ = [("n_active", i32), ("passage_map", vp), ("ids", vp), ("mask", vp),
                 ("n_cached", i32), ("cache_L", i32), ("cache_x", vp), ("cache_slot", vp)]
+
+
+class UserItems(C.Structure):
+    """gram_user_items_t: per-user item filters of a search (device pointers)"""
+    _fields_ = [("leaf_lo", vp), ("leaf_hi", vp), ("ranks", vp), ("count", vp), ("stride", i32), ("mode", i32)]
 
 
 class XattnOut(C.Structure):
@@ -157,6 +164,15 @@ SIGNATURES = {
     "gram_rmsnorm_bf16_map": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, f32, f32, vp, C.c_int, C.c_int, vp, vp]),
     "gram_generate_ex": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
                                    C.POINTER(Compaction), vp, i64, vp, vp, C.POINTER(i32), vp]),
+    # per-user item filters
+    "gram_user_items_prepare": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "gram_beam_step_sparse_items": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+                                              C.POINTER(UserItems), vp]),
+    "gram_beam_step_sparse_split_items": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                                    vp, C.c_int, C.POINTER(UserItems), vp]),
+    "gram_greedy_step_items": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, C.c_int, C.c_int, C.POINTER(UserItems), vp]),
+    "gram_generate_items": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
+                                      C.POINTER(Compaction), C.POINTER(UserItems), vp, i64, vp, vp, C.POINTER(i32), vp]),
     "gram_encode_passages": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, i64, vp, vp]),
     "gram_gather_passage_x": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "gram_live_rows": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), C.POINTER(LiveRows), vp]),

@@ -132,7 +132,38 @@ struct StepArgs {
   const float* __restrict__ emb32;
   const float* __restrict__ pre;
   int pre_stride;
+  const gram_user_items_t* ui;  // per-user item filter (the FILT instantiations only; nullptr otherwise)
 };
+
+// ---- per-user item filters (gram_user_items_t).  FILT is a compile-time property of the step kernels: the unfiltered instantiations
+// carry none of this.  The alive test below is the ONE definition that the key builders (dense_window, sparse_window, shared0_keys),
+// flag_nonfinite_keys (through the zero key), step_finish (the ranked walk and the filler loop) and the greedy step all share.
+
+// first index in r[0, n) whose value is >= v
+__device__ __forceinline__ int rank_lower_bound(const int32_t* __restrict__ r, int n, int v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (r[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// does user b keep an item below `node`?  c = the user's ranks inside the node's leaf range [lo, hi): allow mode keeps the node
+// iff c > 0, exclude mode iff some leaf of the range is not listed (the ranks are distinct: c <= hi - lo)
+__device__ __forceinline__ bool node_alive(const gram_user_items_t& ui, int b, int node) {
+  const int lo = ui.leaf_lo[node], hi = ui.leaf_hi[node];
+  const int32_t* __restrict__ r = ui.ranks + (size_t)b * ui.stride;
+  int n = ui.count[b];
+  n = n < 0 ? 0 : (n > ui.stride ? ui.stride : n);  // (a wrong count must not reach past the user's row)
+  const int c = rank_lower_bound(r, n, hi) - rank_lower_bound(r, n, lo);
+  return ui.mode == GRAM_ITEMS_ALLOW ? c > 0 : c < hi - lo;
+}
+template <bool FILT>
+__device__ __forceinline__ bool child_alive(const StepArgs& a, int b, int edge) {
+  if constexpr (FILT) return node_alive(*a.ui, b, a.tr.child_node[edge]);
+  else return true;
+}
 
 // the step's small per-user tables (static LDS, ~3 KB)
 struct StepShared {
@@ -190,7 +221,9 @@ __device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, in
 // at B = 2048) is never written.  Candidates [c0, c0 + n) of the user's list go to kw[0, n) as keys; shared0 (step 0: all K beams sit
 // on the same node and the same row): children [c0, c0 + n) of that node, their logits go to s_log[0, n) and shared0_keys makes the
 // K keys of each.  The caller puts a barrier behind it.
-template <int NTHR>
+// FILT: a candidate whose child node is not alive for the user gets the zero key ("nothing", below every real key) and no dot product;
+// the shared step-0 row computes every child's logit and leaves the test to shared0_keys.
+template <int NTHR, bool FILT = false>
 __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, float* s_log, int b, int tid,
                                               int c0, int n, bool shared0) {
   const gram_beam_state_t& st = a.st;
@@ -206,6 +239,8 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
       while (sh.pre[k + 1] <= ci) ++k;
     const int tok = tr.child_tok[sh.off[k] + (ci - sh.pre[k])];
     kw[i] = ((unsigned long long)(uint32_t)k << 32) | (unsigned long long)(uint32_t)tok;
+    if constexpr (FILT)
+      if (!shared0 && !child_alive<true>(a, b, sh.off[k] + (ci - sh.pre[k]))) kw[i] |= 1ull << 63;  // (k <= 64: the bit is free)
   }
   gram_sync();
   auto dot = [&](bool act, int lr, int tok, int ci) -> float {
@@ -216,19 +251,24 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
   constexpr int NG = NTHR / 8;
   for (int base = 0; base < n; base += 2 * NG) {
     int i2[2], k2[2], tok2[2], lr2[2];
-    bool act2[2];
+    bool act2[2], dead2[2];
 #pragma unroll
     for (int w = 0; w < 2; ++w) {
       i2[w] = base + NG * w + grp;
       act2[w] = i2[w] < n;
-      const unsigned long long kt = act2[w] ? kw[i2[w]] : 0ull;
+      unsigned long long kt = act2[w] ? kw[i2[w]] : 0ull;
+      dead2[w] = false;
+      if constexpr (FILT) {
+        dead2[w] = (kt >> 63) != 0;
+        kt &= ~(1ull << 63);
+      }
       k2[w] = (int)(kt >> 32);
       tok2[w] = (int)(kt & 0xffffffffull);
       lr2[w] = shared0 ? b : sh.lr[k2[w]];
     }
     float acc2[2];
 #pragma unroll
-    for (int w = 0; w < 2; ++w) acc2[w] = dot(act2[w], lr2[w], tok2[w], c0 + i2[w]);
+    for (int w = 0; w < 2; ++w) acc2[w] = dot(act2[w] && !dead2[w], lr2[w], tok2[w], c0 + i2[w]);
 #pragma unroll
     for (int w = 0; w < 2; ++w) {
       if (act2[w] && sub == 0) {
@@ -236,7 +276,7 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
           s_log[i2[w]] = acc2[w];
         } else {
           const float sc = (acc2[w] - a.lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
-          kw[i2[w]] = cand_key(sc, k2[w], V, tok2[w]);
+          kw[i2[w]] = dead2[w] ? 0ull : cand_key(sc, k2[w], V, tok2[w]);
         }
       }
     }
@@ -246,7 +286,7 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
 // step 0's shared row: the keys of beams [k0, k0 + kg) x children [j0, j0 + nj) of the shared node, from the nj logits that
 // sparse_window left in s_log: kw[(k - k0) * nj + (j - j0)].  (k0 = j0 = 0, kg = K, nj = the node's fan-out: the user's whole list
 // in its flat-index order)
-template <int NTHR>
+template <int NTHR, bool FILT = false>
 __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared& sh, unsigned long long* kw, const float* s_log, int b,
                                              int tid, int j0, int nj, int k0, int kg) {
   const gram_beam_state_t& st = a.st;
@@ -259,12 +299,12 @@ __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared
     const int k = k0 + kk;
     const int tok = tr.child_tok[off0 + j0 + jj];
     const float sc = (s_log[jj] - a.lse[b]) + st.beam_scores[row0 + k];
-    kw[i] = cand_key(sc, k, a.V, tok);
+    kw[i] = child_alive<FILT>(a, b, off0 + j0 + jj) ? cand_key(sc, k, a.V, tok) : 0ull;
   }
 }
 
 // DENSE mode, gather: log_softmax at the allowed tokens + running beam score.  Candidates [c0, c0 + n) -> kw[0, n); kw[n, npad) = 0
-template <int NTHR>
+template <int NTHR, bool FILT = false>
 __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, int b, int tid, int c0, int n,
                                              int npad) {
   const gram_beam_state_t& st = a.st;
@@ -282,7 +322,7 @@ __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared
       // rows_per_user == 1: the K beams of a user share one logits row (step 0: identical beams)
       const int lr = a.rows_per_user == 1 ? b : r;
       const float sc = (a.logits[(size_t)lr * V + tok] - a.lse[lr]) + st.beam_scores[r];
-      key = cand_key(sc, k, V, tok);
+      key = child_alive<FILT>(a, b, e) ? cand_key(sc, k, V, tok) : 0ull;
     }
     kw[i] = key;
   }
@@ -292,10 +332,12 @@ __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared
 // +inf (positive NaN) or below -inf (negative NaN) and would be picked first or never, a row whose normaliser is +inf / NaN turns
 // all its candidates into -inf / NaN -- either way the search would go on and return an ordinary-looking ranking without them.
 // -inf candidates are legitimate (HF's -inf refills of finished beams).  Every candidate's key passes through here before the
-// selection can drop it.
-template <int NTHR>
+// selection can drop it.  FILT: the zero key of a dead candidate is no score (a real key's low word is never 0) and is passed over.
+template <int NTHR, bool FILT = false>
 __device__ __forceinline__ void flag_nonfinite_keys(const StepArgs& a, const unsigned long long* kw, int n, int tid) {
   for (int i = tid; i < n; i += NTHR) {
+    if constexpr (FILT)
+      if (kw[i] == 0ull) continue;
     const uint32_t o = (uint32_t)(kw[i] >> 32);
     if (o >= 0xff800000u || o < 0x007fffffu) a.st.error[0] = 4;  // f2ord(+inf) = 0xff800000, f2ord(-inf) = 0x007fffff
   }
@@ -360,8 +402,9 @@ __device__ __forceinline__ void top_p_select(unsigned long long* keys, int NC, i
 
 // Everything behind the selection: keys[0, min(C, 2K)) hold the user's best candidates in descending order (C = sh.C of them in
 // all).  BeamSearchScorer.process on one thread, then the sequences / ancestor table / per-row state are advanced through
-// new_seq [K][Tmax] / new_anc [Tmax][K] (LDS).
-template <int NTHR>
+// new_seq [K][Tmax] / new_anc [Tmax][K] (LDS).  FILT: the zero keys of dead candidates sort last, so the ranking ends at the first
+// one, and a filler token is any token that is not an ALIVE child of beam 0's node.
+template <int NTHR, bool FILT = false>
 __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int* new_seq, int* new_anc,
                                             int b, int tid) {
   const gram_beam_state_t& st = a.st;
@@ -377,7 +420,7 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
   if (!isdone) {
     for (int rank = tid; rank < 2 * K; rank += NTHR) {
       int e = -1;
-      if (rank < C) {
+      if (rank < C && (!FILT || keys[rank] != 0ull)) {
         const unsigned long long key = keys[rank];
         const uint32_t flat = 0xffffffffu - (uint32_t)(key & 0xffffffffull);
         const int k = (int)(flat / (uint32_t)V), tok = (int)(flat % (uint32_t)V);
@@ -405,14 +448,22 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
       for (int rank = 0; rank < 2 * K && j < K; ++rank) {
         float sc;
         int k, tok;
-        if (rank < C) {
+        const bool real = rank < C && (!FILT || keys[rank] != 0ull);
+        if (real) {
           const unsigned long long key = keys[rank];
           sc = ord2f((uint32_t)(key >> 32));
           const uint32_t flat = 0xffffffffu - (uint32_t)(key & 0xffffffffull);
           k = (int)(flat / (uint32_t)V);
           tok = (int)(flat % (uint32_t)V);
         } else {
-          while (ftok < V && find_child(tr, node0, ftok) >= 0) ++ftok;
+          if constexpr (FILT) {
+            for (; ftok < V; ++ftok) {
+              const int fe = find_child(tr, node0, ftok);
+              if (fe < 0 || !child_alive<true>(a, b, fe)) break;
+            }
+          } else {
+            while (ftok < V && find_child(tr, node0, ftok) >= 0) ++ftok;
+          }
           sc = -INFINITY;
           k = 0;
           tok = ftok++;
@@ -422,7 +473,7 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
           if (rank >= K) continue;
           hyp_add(st, b, st.seq + (size_t)(row0 + k) * T, cur_len, sc);
         } else {
-          const int e = (rank < C) ? sh.edge[rank] : -1;
+          const int e = real ? sh.edge[rank] : -1;
           sh.sel_score[j] = sc;
           sh.sel_tok[j] = tok;
           sh.sel_par[j] = k;
@@ -521,6 +572,53 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
   }
   step_finish<NTHR>(a, sh, keys, new_seq, new_anc, b, tid);
 }
+// ... with per-user item filters (gram_user_items_t).  beam_step_kernel's text with the filtered (FILT = true) forms of the pieces; the
+// unfiltered kernel above keeps its own text, and with it its code object, instruction for instruction.
+template <int NTHR>
+__global__ __launch_bounds__(NTHR) void beam_step_items_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
+                                                              const float* __restrict__ lse, int V, int cur_len, int nc_max,
+                                                              int rows_per_user, const p16* __restrict__ hd, const p16* __restrict__ emb,
+                                                              int d, const int32_t* __restrict__ rowpos, int pieces,
+                                                              const float* __restrict__ emb32, const float* __restrict__ pre,
+                                                              gram_user_items_t ui) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nc_max]
+  float* s_log = reinterpret_cast<float*>(keys + nc_max);                   // [max_fanout, rounded up to 4] shared step-0 logits
+  // [K][Tmax] + [Tmax][K]: the advanced sequences / ancestor table on their way back to HBM (sized by the call, not by the maxima)
+  int* new_seq = reinterpret_cast<int*>(smem + (size_t)nc_max * 8 + ((size_t)tr.max_fanout * 4 + 15) / 16 * 16);
+  int* new_anc = new_seq + st.K * st.Tmax;
+  __shared__ StepShared sh;
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max, &ui};
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int K = st.K;
+  step_setup(a, sh, b, tid, nc_max);
+  const int C = sh.C, NC = sh.NC;
+  const bool isdone = sh.isdone != 0;
+
+  if (!isdone && logits == nullptr) {
+    for (int ci = C + tid; ci < NC; ci += NTHR) keys[ci] = 0ull;
+    const bool shared0 = rows_per_user == 1;
+    sparse_window<NTHR, true>(a, sh, keys, s_log, b, tid, 0, shared0 ? sh.pre[1] : C, shared0);
+    if (shared0) {
+      gram_sync();
+      shared0_keys<NTHR, true>(a, sh, keys, s_log, b, tid, 0, sh.pre[1], 0, K);
+    }
+    gram_sync();
+  }
+  if (!isdone && logits != nullptr) {
+    dense_window<NTHR, true>(a, sh, keys, b, tid, 0, C, NC);
+    gram_sync();
+  }
+  if (!isdone) {
+    flag_nonfinite_keys<NTHR, true>(a, keys, C, tid);
+    flag_nonfinite_lse(a, sh, b, tid);
+    int P = 64;
+    while (P < 2 * K) P <<= 1;
+    top_p_select<NTHR, kOneShotMaxKeys>(keys, NC, P, tid);
+  }
+  step_finish<NTHR, true>(a, sh, keys, new_seq, new_anc, b, tid);
+}
 
 // CHUNKED form: any fan-out.  The candidates stream through a fixed key array: keys[0, P) carry the best P keys so far (descending;
 // zero keys -- below every real key, whose low word is never 0 -- while fewer have been seen), keys[P, P + n) take the next n <= cap
@@ -608,6 +706,75 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
     }
   }
   step_finish<NTHR>(a, sh, keys, new_seq, new_anc, b, tid);
+}
+// ... with per-user item filters: beam_step_chunked_kernel's text with the filtered forms of the pieces (see beam_step_items_kernel)
+template <int NTHR>
+__global__ __launch_bounds__(NTHR) void beam_step_chunked_items_kernel(gram_beam_state_t st, gram_trie_t tr,
+                                                                      const float* __restrict__ logits, const float* __restrict__ lse,
+                                                                      int V, int cur_len, int cap, int rows_per_user,
+                                                                      const p16* __restrict__ hd, const p16* __restrict__ emb, int d,
+                                                                      const int32_t* __restrict__ rowpos, int pieces,
+                                                                      const float* __restrict__ emb32, gram_user_items_t ui) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [kChunkKeys]
+  float* s_log = reinterpret_cast<float*>(keys + kChunkKeys);              // [kChunkLog]
+  int* new_seq = reinterpret_cast<int*>(s_log + kChunkLog);                // [K][Tmax] + [Tmax][K], as in the one-shot kernel
+  int* new_anc = new_seq + st.K * st.Tmax;
+  __shared__ StepShared sh;
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0, &ui};
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int K = st.K;
+  step_setup(a, sh, b, tid, 0);
+  const int C = sh.C;
+  const bool isdone = sh.isdone != 0;
+
+  if (!isdone) {
+    flag_nonfinite_lse(a, sh, b, tid);
+    int P = 64;
+    while (P < 2 * K) P <<= 1;
+    if (cap > kChunkKeys - P) cap = kChunkKeys - P;  // (the launcher's job; a wrong value must not reach past the array)
+    if (cap < 1) cap = 1;
+    unsigned long long* kw = keys + P;
+    for (int i = tid; i < P; i += NTHR) keys[i] = 0ull;  // nothing carried yet
+    // kw[0, n) hold fresh keys (all threads behind a barrier or not: one follows the padding)
+    auto merge = [&](int n) {
+      int na = 2 * P;  // the power of two >= P + n
+      while (na < P + n) na <<= 1;
+      for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
+      gram_sync();
+      flag_nonfinite_keys<NTHR, true>(a, kw, n, tid);
+      top_p_select<NTHR, kChunkKeys>(keys, na, P, tid);
+    };
+    if (logits != nullptr) {
+      for (int c0 = 0; c0 < C; c0 += cap) {
+        const int n = C - c0 < cap ? C - c0 : cap;
+        dense_window<NTHR, true>(a, sh, kw, b, tid, c0, n, n);
+        merge(n);
+      }
+    } else if (rows_per_user != 1) {
+      for (int c0 = 0; c0 < C; c0 += cap) {
+        const int n = C - c0 < cap ? C - c0 : cap;
+        sparse_window<NTHR, true>(a, sh, kw, s_log, b, tid, c0, n, false);
+        merge(n);
+      }
+    } else {
+      const int cnt0 = sh.pre[1];
+      const int njmax = cap < kChunkLog ? cap : kChunkLog;
+      for (int j0 = 0; j0 < cnt0; j0 += njmax) {
+        const int nj = cnt0 - j0 < njmax ? cnt0 - j0 : njmax;
+        sparse_window<NTHR, true>(a, sh, kw, s_log, b, tid, j0, nj, true);
+        gram_sync();
+        const int kgmax = cap / nj;  // >= 1
+        for (int k0 = 0; k0 < K; k0 += kgmax) {
+          const int kg = K - k0 < kgmax ? K - k0 : kgmax;
+          shared0_keys<NTHR, true>(a, sh, kw, s_log, b, tid, j0, nj, k0, kg);
+          merge(kg * nj);
+        }
+      }
+    }
+  }
+  step_finish<NTHR, true>(a, sh, keys, new_seq, new_anc, b, tid);
 }
 
 // The sparse logits of a search step, computed by MANY workgroups (a handful of users: beam_step_kernel's one workgroup per user pulls
@@ -800,6 +967,105 @@ __global__ void greedy_step_kernel(gram_beam_state_t st, gram_trie_t tr, const f
   st.tokens[b] = tok;
   st.node[b] = next_node;
 }
+// greedy_step_kernel with per-user item filters: the argmax runs over the children that are alive for the user (node_alive)
+__global__ void greedy_step_items_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits, int V, int cur_len,
+                                         gram_user_items_t ui) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= st.B) return;
+  const int T = st.Tmax;
+  int tok = st.pad, next_node = -1;
+  if (!st.done[b]) {
+    const int nd = st.node[b];
+    tok = 0;  // argmax of an all -inf row
+    if (nd >= 0) {
+      const int lo = tr.child_off[nd], hi = tr.child_off[nd + 1];
+      float best = -INFINITY;
+      bool any = false;
+      for (int e = lo; e < hi; ++e) {
+        if (!node_alive(ui, b, tr.child_node[e])) continue;
+        const int c = tr.child_tok[e];
+        const float v = logits[(size_t)b * V + c];
+        // children are sorted by token: strict > keeps the first maximum; a -inf logit at a lower index than
+        // an allowed -inf one cannot happen for finite model outputs, NaN is never selected over a number
+        if (!any || v > best) {
+          best = v;
+          tok = c;
+          next_node = tr.child_node[e];
+          any = true;
+        }
+      }
+    }
+    if (tok == st.eos) {
+      st.done[b] = 1;
+      st.n_hyps[b] = cur_len + 1;
+    }
+  }
+  st.seq[(size_t)b * T + cur_len] = tok;
+  st.tokens[b] = tok;
+  st.node[b] = next_node;
+}
+
+// A call's per-user item lists -> sorted distinct leaf ranks (gram_user_items_prepare).  One workgroup per user: the list's entries
+// become leaf ranks (padding and out-of-range indices become INT32_MAX, above every rank), a bitonic sort in LDS puts them in
+// ascending order, and every thread compacts its slice of the sorted array behind an exclusive scan of the slices' distinct counts.
+// npad: the power of two >= max(M, 256); dynamic LDS npad * 4 B (16 KB at GRAM_MAX_USER_ITEMS).
+__global__ __launch_bounds__(256) void user_items_prepare_kernel(const int32_t* __restrict__ item_rank, int n_items,
+                                                                 const int32_t* __restrict__ items, int M, int npad,
+                                                                 int32_t* __restrict__ ranks, int32_t* __restrict__ count, int stride) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int32_t* s = reinterpret_cast<int32_t*>(smem);  // [npad]
+  __shared__ int s_cnt[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < npad; i += 256) {
+    int32_t v = INT32_MAX;
+    if (i < M) {
+      const int32_t it = items[(size_t)b * M + i];
+      if (it >= 0 && it < n_items) {
+        const int32_t r = item_rank[it];
+        if (r >= 0) v = r;
+      }
+    }
+    s[i] = v;
+  }
+  gram_sync();
+  for (int kk = 2; kk <= npad; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < npad; i += 256) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const int32_t x = s[i], y = s[ixj];
+          if (((i & kk) == 0) ? (x > y) : (x < y)) {
+            s[i] = y;
+            s[ixj] = x;
+          }
+        }
+      }
+      gram_sync();
+    }
+  // thread tid owns sorted entries [tid * per, (tid + 1) * per): an entry is kept if it is a rank and differs from its predecessor
+  const int per = npad / 256;
+  auto keep = [&](int i) { return s[i] != INT32_MAX && (i == 0 || s[i] != s[i - 1]); };
+  int c = 0;
+  for (int i = tid * per; i < (tid + 1) * per; ++i) c += keep(i) ? 1 : 0;
+  s_cnt[tid] = c;
+  gram_sync();
+  if (tid == 0) {
+    int acc = 0;
+    for (int t = 0; t < 256; ++t) {
+      const int n = s_cnt[t];
+      s_cnt[t] = acc;
+      acc += n;
+    }
+    count[b] = acc < stride ? acc : stride;  // (acc <= M <= stride: the launcher checks)
+  }
+  gram_sync();
+  int pos = s_cnt[tid];
+  for (int i = tid * per; i < (tid + 1) * per; ++i)
+    if (keep(i)) {
+      if (pos < stride) ranks[(size_t)b * stride + pos] = s[i];
+      ++pos;
+    }
+}
 
 __global__ void greedy_finalize_kernel(gram_beam_state_t st, int max_length, int64_t* __restrict__ sequences,
                                        int32_t* __restrict__ out_width) {
@@ -867,9 +1133,18 @@ extern "C" int gram_debug_set_beam_chunk_capacity(int candidates) {
   return 0;
 }
 
+// the per-user lists of the *_items entry points (gram_user_items_t): every array present, stride and mode in range
+static int check_items(const gram_user_items_t* it) {
+  if (!it || !it->leaf_lo || !it->leaf_hi || !it->ranks || !it->count || it->stride < 1 || it->stride > GRAM_MAX_USER_ITEMS ||
+      (it->mode != GRAM_ITEMS_EXCLUDE && it->mode != GRAM_ITEMS_ALLOW))
+    return GRAM_E_ARG;
+  return 0;
+}
+
+// items != nullptr: the step's form with per-user item filters (the *_items kernels); nullptr: exactly the launches of before
 static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                             int cur_len, int rows_per_user, const void* hd, const void* emb, int d, const int32_t* rowpos,
-                            void* stream, int pieces = 1, const float* emb32 = nullptr) {
+                            void* stream, int pieces = 1, const float* emb32 = nullptr, const gram_user_items_t* items = nullptr) {
   if (int e = check_state(st)) return e;
   if (!tr || !lse || cur_len < 1 || cur_len >= st->Tmax || V < 2 || (rows_per_user != 1 && rows_per_user != st->K)) return GRAM_E_ARG;
   if (!logits && (!hd || (!emb && !emb32) || d < 64 || (d & 63))) return GRAM_E_ARG;
@@ -905,6 +1180,26 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
       if (e != hipSuccess) return (int)e;
       attr_bytes = smem;
     }
+    if (items) {
+      static size_t items_attr_bytes = 0;
+      if (smem > items_attr_bytes) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_items_kernel<256>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e == hipSuccess)
+          e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_items_kernel<1024>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return (int)e;
+        items_attr_bytes = smem;
+      }
+      if (st->B <= wide_max_b)
+        hipLaunchKernelGGL(beam_step_chunked_items_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse,
+                           V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, *items);
+      else
+        hipLaunchKernelGGL(beam_step_chunked_items_kernel<256>, dim3(st->B), dim3(256), smem, (hipStream_t)stream, *st, *tr, logits, lse,
+                           V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, *items);
+      GRAM_CHECK_LAUNCH();
+      return 0;
+    }
     if (st->B <= wide_max_b)
       hipLaunchKernelGGL(beam_step_chunked_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse, V,
                          cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32);
@@ -936,6 +1231,26 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
     pre = st->cand_logits;
   }
   const int nc_arg = nc;
+  if (items) {
+    static size_t items_attr_bytes = 0;
+    if (smem > items_attr_bytes) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_items_kernel<256>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_items_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)smem);
+      if (e != hipSuccess) return (int)e;
+      items_attr_bytes = smem;
+    }
+    if (st->B <= wide_max_b)
+      hipLaunchKernelGGL(beam_step_items_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len,
+                         nc_arg, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, pre, *items);
+    else
+      hipLaunchKernelGGL(beam_step_items_kernel<256>, dim3(st->B), dim3(256), smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len,
+                         nc_arg, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, pre, *items);
+    GRAM_CHECK_LAUNCH();
+    return 0;
+  }
   if (st->B <= wide_max_b)
     hipLaunchKernelGGL(beam_step_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nc_arg,
                        rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, pre);
@@ -972,6 +1287,36 @@ extern "C" int gram_beam_step_sparse_split(const gram_beam_state_t* st, const gr
   return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, nullptr, d, rowpos, stream, pieces, lm_head_f32);
 }
 
+extern "C" int gram_beam_step_sparse_items(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
+                                           const void* lm_head_bf16, int d, const float* lse, int V, int cur_len, int rows_per_user,
+                                           const int32_t* rowpos, const gram_user_items_t* items, void* stream) {
+  if (int e = check_items(items)) return e;
+  if (!st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
+  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, lm_head_bf16, d, rowpos, stream, 1, nullptr, items);
+}
+
+extern "C" int gram_beam_step_sparse_split_items(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
+                                                 const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                                                 int rows_per_user, const int32_t* rowpos, int pieces, const gram_user_items_t* items,
+                                                 void* stream) {
+  if (int e = check_items(items)) return e;
+  if (!lm_head_f32) return GRAM_E_ARG;
+  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, nullptr, d, rowpos, stream, pieces, lm_head_f32,
+                          items);
+}
+
+extern "C" int gram_user_items_prepare(const int32_t* item_rank, int n_items, const int32_t* items, int B, int M, int32_t* ranks,
+                                       int32_t* count, int stride, void* stream) {
+  if (!item_rank || !items || !ranks || !count || n_items < 1 || B < 1 || M < 1 || stride < M || stride > GRAM_MAX_USER_ITEMS)
+    return GRAM_E_ARG;
+  int npad = 256;
+  while (npad < M) npad <<= 1;
+  hipLaunchKernelGGL(user_items_prepare_kernel, dim3(B), dim3(256), (size_t)npad * 4, (hipStream_t)stream, item_rank, n_items, items, M,
+                     npad, ranks, count, stride);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int gram_live_rows(const gram_beam_state_t* st, const gram_trie_t* tr, const gram_live_rows_t* out, void* stream) {
   if (int e = check_state(st)) return e;
   if (!tr || !out || !out->rows || !out->rowpos || !out->users || !out->tokens || !out->counts) return GRAM_E_ARG;
@@ -987,6 +1332,18 @@ extern "C" int gram_greedy_step(const gram_beam_state_t* st, const gram_trie_t* 
   if (!tr || st->K != 1 || cur_len < 1 || cur_len >= st->Tmax || V < 2) return GRAM_E_ARG;
   gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
   hipLaunchKernelGGL(greedy_step_kernel, dim3((st->B + 127) / 128), dim3(128), 0, (hipStream_t)stream, *st, *tr, logits, V, cur_len);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int gram_greedy_step_items(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, int V, int cur_len,
+                                      const gram_user_items_t* items, void* stream) {
+  if (int e = check_items(items)) return e;
+  if (int e = check_state(st)) return e;
+  if (!tr || st->K != 1 || cur_len < 1 || cur_len >= st->Tmax || V < 2) return GRAM_E_ARG;
+  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
+  hipLaunchKernelGGL(greedy_step_items_kernel, dim3((st->B + 127) / 128), dim3(128), 0, (hipStream_t)stream, *st, *tr, logits, V, cur_len,
+                     *items);
   GRAM_CHECK_LAUNCH();
   return 0;
 }

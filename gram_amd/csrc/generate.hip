@@ -463,10 +463,18 @@ int decode_step(const gram_model* m, const Workspace& w, const int32_t* tokens, 
   return lm_head(m, w, R, logits, lse_part, st);
 }
 
-// the search step on the hidden states decode_step left in w.dec.h (rowpos: live-row step, else NULL)
+// the search step on the hidden states decode_step left in w.dec.h (rowpos: live-row step, else NULL; items: per-user item filters of
+// gram_generate_items, else NULL)
 int search_step(const gram_model* m, const Workspace& w, const gram_trie_t* trie, int cur_len, int rows_per_user, const int32_t* rowpos,
-                void* st) {
+                const gram_user_items_t* items, void* st) {
   const gram_model_desc_t& c = m->d;
+  if (items) {
+    if (w.pieces > 1)
+      return gram_beam_step_sparse_split_items(&w.beam, trie, w.dec.h, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len, rows_per_user,
+                                               rowpos, w.pieces, items, st);
+    return gram_beam_step_sparse_items(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.d_model, w.lse, c.vocab, cur_len, rows_per_user, rowpos,
+                                       items, st);
+  }
   if (w.pieces > 1)
     return gram_beam_step_sparse_split(&w.beam, trie, w.dec.h, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len, rows_per_user, rowpos,
                                        w.pieces, st);
@@ -688,14 +696,15 @@ namespace {
 // 14.1 vs 12.8 ms, 11.5 vs 10.65 ms eager: the chain is bound by the GPU-side dependency between ~950 tiny kernels, not by the host's
 // launch cost, and a captured train cannot take the live-row step, whose row counts travel through the host -- and removed in round 4.)
 int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
-                  int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, int64_t* sequences, float* scores,
-                  void* stream) {
+                  int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
+                  int64_t* sequences, float* scores, void* stream) {
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
   TRY(gram_beam_init(&w.beam, trie, /*decoder_start_token_id=*/0, stream));
   if (K == 1) {  // HF: num_beams == 1 -> greedy_search (raw logits, no hypotheses, no scores)
     for (int t = 0; t + 1 < max_length; ++t) {
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, 1, B, max_length, t, w.logits, nullptr, nullptr, stream));
-      TRY(gram_greedy_step(&w.beam, trie, w.logits, m->d.vocab, t + 1, stream));
+      if (items) TRY(gram_greedy_step_items(&w.beam, trie, w.logits, m->d.vocab, t + 1, items, stream));
+      else TRY(gram_greedy_step(&w.beam, trie, w.logits, m->d.vocab, t + 1, stream));
     }
     TRY(gram_greedy_finalize(&w.beam, max_length, sequences, w.width, stream));
   } else {
@@ -728,7 +737,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
                             stream));
             TRY(gram_lse_combine(w.lse_part, w.lse, counts[0], m->d.vocab / 64, stream));
           }  // else: no beam can be extended; the search step below reads no decoder row
-          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, stream));
+          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream));
           continue;
         }
       }
@@ -736,7 +745,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, Kt, B * K, max_length, t, nullptr, w.lse_part, nullptr,
                       stream));
       TRY(gram_lse_combine(w.lse_part, w.lse, B * Kt, m->d.vocab / 64, stream));
-      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, stream));
+      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream));
     }
     TRY(gram_beam_finalize(&w.beam, nret, max_length, sequences, scores, w.width, stream));
   }
@@ -745,17 +754,18 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
 
 }  // namespace
 
-extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
-                                int nret, int max_length, float length_penalty, const gram_trie_t* trie,
-                                const gram_compaction_t* comp, void* workspace, int64_t workspace_bytes, int64_t* sequences,
-                                float* scores, int32_t* width_host, void* stream) {
+// gram_generate_ex and gram_generate_items (items: the per-user item filters, NULL for gram_generate_ex)
+static int generate_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
+                         int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp,
+                         const gram_user_items_t* items, void* workspace, int64_t workspace_bytes, int64_t* sequences, float* scores,
+                         int32_t* width_host, void* stream) {
   TRY(check_shapes(m, B, N, L, K, max_length));
   TRY(check_compaction(comp, B, N));
   if (!trie || nret < 1 || nret > K || !sequences || (!scores && K != 1)) return GRAM_E_ARG;
   Workspace w = carve(m, workspace, B, N, L, K, max_length);
   if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
   w.beam.length_penalty = length_penalty;
-  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, sequences, scores, stream));
+  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, sequences, scores, stream));
   if (width_host) {
     int32_t host[2] = {0, 0};
     hipError_t e = hipMemcpyAsync(&host[0], w.width, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -767,6 +777,25 @@ extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids,
     if (host[1] != 0) return GRAM_E_BEAM;
   }
   return 0;
+}
+
+extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
+                                int nret, int max_length, float length_penalty, const gram_trie_t* trie,
+                                const gram_compaction_t* comp, void* workspace, int64_t workspace_bytes, int64_t* sequences,
+                                float* scores, int32_t* width_host, void* stream) {
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, workspace, workspace_bytes,
+                       sequences, scores, width_host, stream);
+}
+
+extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
+                                   int nret, int max_length, float length_penalty, const gram_trie_t* trie,
+                                   const gram_compaction_t* comp, const gram_user_items_t* items, void* workspace,
+                                   int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
+  if (!items || !items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
+      items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW))
+    return GRAM_E_ARG;
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, workspace, workspace_bytes,
+                       sequences, scores, width_host, stream);
 }
 
 // ---- teacher-forced decoder pass (gram_teacher_forced) -----------------------------------------------------------------------------

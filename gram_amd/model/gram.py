@@ -945,12 +945,20 @@ class GRAM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask, max_length, prefix_allowed_tokens_fn=None, num_beams=1,
                  num_return_sequences=None, output_scores=True, return_dict_in_generate=True, length_penalty=1.0,
-                 **unused):
+                 exclude_items=None, allowed_items=None, candidates=None, **unused):
         """GRAM.generate (gram.py:74-107) with the kwargs single_runner_gram.py:641-651 passes.
 
         input_ids (B,N,L) int64, attention_mask (B,N,L) bool on the model's device.  Returns a
         mapping with ``sequences`` (B*num_return_sequences, T) int64 -- user-major, best first,
-        0-padded, starting with the decoder start token -- and ``sequences_scores`` (fp32)."""
+        0-padded, starting with the decoder start token -- and ``sequences_scores`` (fp32).
+
+        Per-user item filters: ``exclude_items`` (what a user must not get, e.g. its history) or ``allowed_items`` (the only items
+        a user may get, e.g. a retrieval stage's output) -- one of the two, a (B, M) integer tensor padded with -1 or B Python
+        lists of indices into ``candidates``, the token sequences the closure's Trie was built from (the list ``sequence_items``
+        takes; required with either).  User b then gets exactly what this call returns for that user alone with
+        ``prefix_allowed_tokens_fn(Trie(A_b))``, A_b its remaining candidates, bit for bit -- the search walks a per-user view of
+        the one shared device Trie.  Two candidates that spell the same sequence share a Trie leaf: naming
+        either names the sequence.  At most 4096 entries per user; a user left without any item is a ``ValueError``."""
         if prefix_allowed_tokens_fn is None:
             raise NotImplementedError("unconstrained generation is not on GRAM's scoring path (a Trie is always passed)")
         # HF kwargs that would change the search: refuse the ones this path does not implement instead of ignoring them
@@ -980,24 +988,40 @@ class GRAM(nn.Module):
             ids = torch.nn.functional.pad(ids, (0, Lp - L))
             mask = torch.nn.functional.pad(mask, (0, Lp - L))
         ids, mask = ids.contiguous(), mask.contiguous()
+        filtered = exclude_items is not None or allowed_items is not None
+        if exclude_items is not None and allowed_items is not None:
+            raise ValueError("generate: exclude_items and allowed_items are mutually exclusive")
+        if filtered and candidates is None:
+            raise ValueError("generate: exclude_items / allowed_items index `candidates` (the sequences the Trie was built from): pass it")
+        if filtered and self._closure_trie(prefix_allowed_tokens_fn) is None:
+            raise ValueError("generate: exclude_items / allowed_items need the Trie closure form of prefix_allowed_tokens_fn "
+                             "(an arbitrary callback receives batch_id and can filter per user itself)")
         if self._closure_trie(prefix_allowed_tokens_fn) is None:
             if K == 1:
                 raise NotImplementedError("greedy search needs the Trie closure form of prefix_allowed_tokens_fn")
             return self._generate_with_callback(ids, mask, B, N, Lp, K, nret, int(max_length), float(length_penalty),
                                                 prefix_allowed_tokens_fn, return_dict_in_generate)
-        comp, harvest_plan = self._plan(ids, mask, B, N, Lp)
         flat = self._flat_trie(prefix_allowed_tokens_fn)
+        if filtered:  # (validated before anything below touches the passage cache or the workspace)
+            allow = allowed_items is not None
+            items = self._user_item_lists(allowed_items if allow else exclude_items, allow, B, flat, candidates, dev)
+        comp, harvest_plan = self._plan(ids, mask, B, N, Lp)
         _ctrie, (t_off, t_tok, t_node) = flat.to_device(dev)
         ws = self._get_workspace(handle, B, N, Lp, K, int(max_length))
         if K == 1 and nret != 1:
             raise ValueError("num_return_sequences must be 1 for greedy search (num_beams == 1), as in HF generate")
         ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
-        # the whole path is ONE PyTorch-ROCm custom op over the C ABI (gram_amd/ops.py -> gram_generate_ex)
+        # the whole path is ONE PyTorch-ROCm custom op over the C ABI (gram_amd/ops.py -> gram_generate_ex / gram_generate_items)
         from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
-        seqs, scores, width = torch.ops.gram.generate(
-            ids, mask, int(handle), ws, t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len), K, nret, int(max_length),
-            float(length_penalty), ct["comp_map"], ct["comp_ids"], ct["comp_mask"], ct["cache_slot"], ct["cache_x"],
-            int(ct["n_cached"]), int(ct["cache_L"]))
+        args = (ids, mask, int(handle), ws, t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len), K, nret, int(max_length),
+                float(length_penalty), ct["comp_map"], ct["comp_ids"], ct["comp_mask"], ct["cache_slot"], ct["cache_x"],
+                int(ct["n_cached"]), int(ct["cache_L"]))
+        if filtered:
+            leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
+            seqs, scores, width = torch.ops.gram.generate_items(*args, leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items,
+                                                                allow)
+        else:
+            seqs, scores, width = torch.ops.gram.generate(*args)
         if harvest_plan is not None:
             self._harvest_from_workspace(harvest_plan, ws, handle, B, N, Lp, K, int(max_length))
         seqs = seqs[:, : int(width[0])]
@@ -1005,6 +1029,54 @@ class GRAM(nn.Module):
         if not return_dict_in_generate:
             return seqs
         return GenerateOutput(sequences=seqs, sequences_scores=scores)
+
+    @staticmethod
+    def _user_item_lists(lists, allow: bool, B: int, flat: FlatTrie, candidates, device="cpu") -> torch.Tensor:
+        """The per-user lists of ``generate`` as the int32 (B, M) tensor torch.ops.gram.generate_items takes, on ``device``: every
+        row's entries first (in their order), -1 behind them, M = the longest row (at least 1).  Everything a list can get wrong is
+        a ``ValueError`` here, before the search is launched.  The checks are tensor operations on ``device`` (a call's lists can
+        be B x 4096 indices) with one read-back of their four results."""
+        what = "allowed_items" if allow else "exclude_items"
+        limit = _lib.GRAM_MAX_USER_ITEMS
+        if isinstance(lists, torch.Tensor):
+            if lists.dim() != 2 or lists.shape[0] != B or lists.dtype.is_floating_point or lists.dtype == torch.bool:
+                raise ValueError(f"generate: {what} must be a (B, M) integer tensor padded with -1, or B lists")
+            t = lists.detach().to(device, torch.int64)
+        else:
+            rows = [list(map(int, r)) for r in lists]
+            if len(rows) != B:
+                raise ValueError(f"generate: {what} needs one list per user ({B}), got {len(rows)}")
+            t = torch.full((B, max(1, max(map(len, rows)))), -1, dtype=torch.int64)
+            for b, r in enumerate(rows):
+                t[b, : len(r)] = torch.tensor(r, dtype=torch.int64)
+            t = t.to(device)
+        if t.shape[1] == 0:
+            t = torch.full((B, 1), -1, dtype=torch.int64, device=device)
+        n = len(candidates)
+        if n < 1:
+            raise ValueError(f"generate: {what} indexes an empty `candidates`")
+        valid = t != -1
+        outside = (t < -1) | (t >= n)
+        per_user = valid.sum(dim=1)
+        # entries first, padding behind them
+        t = torch.gather(t, 1, torch.sort((~valid).to(torch.uint8), dim=1, stable=True).indices)
+        # a user must keep at least one item: count the DISTINCT leaves its list names (duplicate sequences share one)
+        if torch.device(device).type == "cpu":
+            rank = torch.from_numpy(flat.item_ranks(candidates))
+        else:
+            rank = flat.item_ranks_on(device, candidates)[1]
+        r = torch.where((t >= 0) & (t < n), rank.to(torch.int64)[t.clamp(0, n - 1)], torch.full_like(t, -1)).sort(dim=1).values
+        distinct = (r[:, :1] >= 0).sum(dim=1) + ((r[:, 1:] != r[:, :-1]) & (r[:, 1:] >= 0)).sum(dim=1)
+        empty = distinct == 0 if allow else distinct >= int(flat.leaf_ranges()[1][0])
+        any_outside, longest, any_empty, first_empty = torch.stack(
+            [outside.any().long(), per_user.max(), empty.any().long(), empty.long().argmax()]).tolist()
+        if any_outside:
+            raise ValueError(f"generate: {what} holds an index outside [0, {n}) (-1 is the padding value)")
+        if longest > limit:
+            raise ValueError(f"generate: {what} has {longest} entries for one user, at most {limit} are supported")
+        if any_empty:
+            raise ValueError(f"generate: {what} leaves user {first_empty} without any item")
+        return t[:, : max(1, longest)].to(torch.int32).contiguous()
 
     @torch.no_grad()
     def sequence_items(self, sequences, prefix_allowed_tokens_fn, candidates):

@@ -6,6 +6,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
 (there is no CPU path in gram_amd; the CPU restatement lives in oracle/ and is test infrastructure).
 
     torch.ops.gram.generate          GRAM.generate's whole path (gram_generate_ex) -- what ``GRAM.generate`` calls
+    torch.ops.gram.generate_items    the same path with per-user item filters (gram_user_items_prepare + gram_generate_items) --
+                                     ``GRAM.generate(exclude_items= / allowed_items=)``
     torch.ops.gram.teacher_forced    the teacher-forced decoder pass (gram_teacher_forced) -- ``GRAM.forward(labels=...)`` and
                                      ``GRAM.score_sequences``
     torch.ops.gram.teacher_forced_attn  the same pass with its cross-attention probabilities (gram_teacher_forced_ex) --
@@ -87,6 +89,72 @@ def generate(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: 
 def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
       cache_x, n_cached, cache_L):
+    B = input_ids.shape[0]
+    return (input_ids.new_empty(B * num_return_sequences, max_length),
+            input_ids.new_empty(B * num_return_sequences if num_beams > 1 else 0, dtype=torch.float32),
+            torch.empty(1, dtype=torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------- generate with per-user item filters
+@torch.library.custom_op("gram::generate_items", mutates_args=("workspace",), device_types="cuda")
+def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                   trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
+                   num_return_sequences: int, max_length: int, length_penalty: float, comp_map: Optional[Tensor],
+                   comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor],
+                   n_cached: int, cache_L: int, leaf_lo: Tensor, leaf_hi: Tensor, item_rank: Tensor, items: Tensor,
+                   allow: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``generate`` (same inputs, same outputs) with every user searching its own view of the Trie (gram_user_items_t): leaf_lo /
+    leaf_hi i32 (n_nodes,) the leaf-rank range below every node, item_rank i32 (n_items,) the leaf rank of every candidate, items
+    i32 (B, M) each user's candidate indices padded with -1, M <= 4096; ``allow``: the lists are what a user may get (else what it
+    may not).  The lists become sorted distinct ranks on the device (gram_user_items_prepare), then gram_generate_items runs."""
+    lib = _lib.load()
+    if input_ids.dim() != 3 or items.dim() != 2:
+        raise ValueError("generate_items: input_ids must be (B, N, L) and items (B, M)")
+    B, N, L = input_ids.shape
+    dev = input_ids.device
+    K, nret = num_beams, num_return_sequences
+    M = items.shape[1]
+    n_nodes = trie_child_off.numel() - 1
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),)), ("leaf_lo", leaf_lo, (n_nodes,)),
+                           ("leaf_hi", leaf_hi, (n_nodes,)), ("item_rank", item_rank, (None,)), ("items", items, (B, None))):
+        _check(name, t, torch.int32, shape, dev)
+    if n_nodes < 1 or item_rank.numel() < 1 or not 1 <= M <= _lib.GRAM_MAX_USER_ITEMS:
+        raise ValueError(f"generate_items: need a Trie, at least one candidate and 1 <= M <= {_lib.GRAM_MAX_USER_ITEMS} (got M={M})")
+    # candidate indices index item_rank on the device: out-of-range ones are refused here, not read there
+    lo_i, hi_i = torch.stack([items.min(), items.max()]).tolist()
+    if lo_i < -1 or hi_i >= item_rank.numel():
+        raise ValueError(f"generate_items: items must lie in [0, {item_rank.numel()}) or be the padding value -1")
+    trie = _lib.Trie(trie_child_off.data_ptr(), trie_child_tok.data_ptr(), trie_child_node.data_ptr(), n_nodes,
+                     trie_child_tok.numel(), trie_max_fanout, trie_min_seq_len)
+    comp = None
+    if comp_map is not None:
+        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
+                               _p(cache_slot))
+    ranks = torch.empty(B, M, dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    ui = _lib.UserItems(leaf_lo.data_ptr(), leaf_hi.data_ptr(), ranks.data_ptr(), count.data_ptr(), M,
+                        _lib.ITEMS_ALLOW if allow else _lib.ITEMS_EXCLUDE)
+    seqs = torch.empty(B * nret, max_length, dtype=torch.int64, device=dev)
+    scores = torch.empty(B * nret if K > 1 else 0, dtype=torch.float32, device=dev)
+    width = C.c_int32(0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gram_user_items_prepare(item_rank.data_ptr(), item_rank.numel(), items.data_ptr(), B, M, ranks.data_ptr(),
+                                               count.data_ptr(), M, _stream(input_ids)), "gram_user_items_prepare")
+        rc = lib.gram_generate_items(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length,
+                                     float(length_penalty), C.byref(trie), C.byref(comp) if comp is not None else None, C.byref(ui),
+                                     workspace.data_ptr(), workspace.numel(), seqs.data_ptr(), scores.data_ptr() if K > 1 else None,
+                                     C.byref(width), _stream(input_ids))
+    _lib.check(rc, "gram_generate_items")
+    return seqs, scores, torch.tensor([width.value], dtype=torch.int32)
+
+
+@generate_items.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
+      trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
+      cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
     B = input_ids.shape[0]
     return (input_ids.new_empty(B * num_return_sequences, max_length),
             input_ids.new_empty(B * num_return_sequences if num_beams > 1 else 0, dtype=torch.float32),
@@ -339,4 +407,4 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
-__all__ = ["generate", "teacher_forced", "teacher_forced_attn", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]
+__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]

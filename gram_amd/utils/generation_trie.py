@@ -135,6 +135,7 @@ class FlatTrie:
             raise ValueError("FlatTrie: append_trie is not supported (never set by the GRAM runners)")
         self._device = {}
         self._node_item = None
+        self._leaf_ranges = None
         seqs = trie.sequences() if isinstance(trie, Trie) else None
         if seqs:
             self._from_sequences(seqs)
@@ -263,6 +264,73 @@ class FlatTrie:
         out[node[idx[::-1]]] = idx[::-1].astype(np.int32)
         return out
 
+    def leaf_ranges(self):
+        """(lo, hi): two int32 [n_nodes] arrays.  The Trie's leaves are numbered in lexicographic order of their sequences (the
+        leaf RANK: a depth-first walk that takes children in token order); the leaves below node n -- n itself when it is a leaf --
+        are then the contiguous ranks [lo[n], hi[n]), and hi[0] is the number of leaves.  What the search step's per-user item
+        filters test a node against (include/gram_hip.h ``gram_user_items_t``).  Built once per Trie from the CSR arrays alone, so
+        both constructors are covered: leaf counts bottom-up, then first ranks top-down, one vectorised pass per level."""
+        if self._leaf_ranges is not None:
+            return self._leaf_ranges
+        n = self.n_nodes
+        fan = np.diff(self.child_off).astype(np.int64)
+        child = self.child_node.astype(np.int64)
+        edge_parent = np.repeat(np.arange(n, dtype=np.int64), fan)
+        parent = np.zeros(n, dtype=np.int64)
+        parent[child] = edge_parent
+        levels, frontier = [], np.zeros(1, dtype=np.int64)
+        while frontier.size:
+            levels.append(frontier)
+            counts = fan[frontier]
+            first = self.child_off[frontier].astype(np.int64)
+            edges = np.repeat(first - (np.cumsum(counts) - counts), counts) + np.arange(int(counts.sum()), dtype=np.int64)
+            frontier = child[edges]
+        cnt = (fan == 0).astype(np.int64)
+        cnt[0] = 0  # (the root of an empty Trie is no candidate)
+        for lv in reversed(levels[1:]):
+            np.add.at(cnt, parent[lv], cnt[lv])
+        # leaves under the earlier siblings of every edge's child: an exclusive prefix sum over the parent-major, token-ordered edges
+        w = cnt[child]
+        before = np.cumsum(w) - w
+        sib = np.zeros(n, dtype=np.int64)
+        if child.size:
+            sib[child] = before - before[self.child_off[edge_parent].astype(np.int64)]
+        lo = np.zeros(n, dtype=np.int64)
+        for lv in levels[1:]:
+            lo[lv] = lo[parent[lv]] + sib[lv]
+        self._leaf_ranges = (lo.astype(np.int32), (lo + cnt).astype(np.int32))
+        return self._leaf_ranges
+
+    def item_ranks(self, candidates: Sequence[Sequence[int]]) -> np.ndarray:
+        """int32 [len(candidates)]: the leaf rank (:meth:`leaf_ranges`) of every candidate -- the token sequences the Trie was
+        built from, in the caller's order, the list ``GRAM.sequence_items`` takes.  Two candidates that spell the same sequence
+        share a leaf and get the same rank.  ``ValueError`` for a candidate that is not in the Trie or does not end on a leaf."""
+        n = len(candidates)
+        if n == 0:
+            return np.zeros(0, dtype=np.int32)
+        lens = np.fromiter((len(c) for c in candidates), dtype=np.int64, count=n)
+        width = int(lens.max())
+        toks = np.full((n, max(width, 1)), -1, dtype=np.int64)
+        for i, c in enumerate(candidates):
+            toks[i, : len(c)] = c
+        node = np.zeros(n, dtype=np.int64)
+        fan = np.diff(self.child_off)
+        edge_key = np.repeat(np.arange(self.n_nodes, dtype=np.int64), fan) * (1 << 32) + self.child_tok.astype(np.int64)
+        for p in range(width):
+            live = (lens > p) & (node >= 0)
+            if not live.any() or not len(edge_key):
+                node[live] = -1
+                continue
+            key = node[live] * (1 << 32) + toks[live, p]
+            e = np.minimum(np.searchsorted(edge_key, key), len(edge_key) - 1)
+            node[live] = np.where(edge_key[e] == key, self.child_node[e], -1)
+        if (node < 0).any():
+            raise ValueError(f"item_ranks: candidate {int(np.nonzero(node < 0)[0][0])} is not in the Trie")
+        bad = (fan[node] != 0) | (node == 0)
+        if bad.any():
+            raise ValueError(f"item_ranks: candidate {int(np.nonzero(bad)[0][0])} does not end on a leaf of the Trie")
+        return self.leaf_ranges()[0][node].astype(np.int32)
+
     # host-side walk with the same arrays the device uses (for tests)
     def get(self, prefix: Sequence[int]) -> List[int]:
         node = 0
@@ -300,3 +368,26 @@ class FlatTrie:
             self._device = {k: v for k, v in self._device.items() if not (isinstance(k, tuple) and k[0] == "items")}
             self._device[key] = hit
         return hit[1]
+
+    def leaf_ranges_on(self, device):
+        """Device copies of :meth:`leaf_ranges`, uploaded once per device."""
+        import torch
+
+        key = ("leaf", str(device))
+        if key not in self._device:
+            lo, hi = self.leaf_ranges()
+            self._device[key] = (torch.from_numpy(lo).to(device), torch.from_numpy(hi).to(device))
+        return self._device[key]
+
+    def item_ranks_on(self, device, candidates: Sequence[Sequence[int]]):
+        """(host array, device copy) of :meth:`item_ranks` for this candidate list, built once per (list object, device)."""
+        import torch
+
+        key = ("ranks", str(device), id(candidates), len(candidates))
+        hit = self._device.get(key)
+        if hit is None or hit[0] is not candidates:
+            ranks = self.item_ranks(candidates)
+            hit = (candidates, ranks, torch.from_numpy(ranks).to(device))
+            self._device = {k: v for k, v in self._device.items() if not (isinstance(k, tuple) and k[0] == "ranks")}
+            self._device[key] = hit
+        return hit[1], hit[2]

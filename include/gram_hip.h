@@ -338,6 +338,48 @@ int gram_beam_step_sparse_split(const gram_beam_state_t* st_host, const gram_tri
                                 const float* lm_head_f32, int d, const float* lse, int V, int cur_len, int rows_per_user,
                                 const int32_t* rowpos, int pieces, void* stream);
 
+/* ---- per-user item filters: every user searches its own view of the shared Trie ------------------------------------------------
+ * User b has an item set A_b, a subset of the candidate list the Trie was built from: A_b = its list (GRAM_ITEMS_ALLOW) or every
+ * candidate but its list (GRAM_ITEMS_EXCLUDE).  The search step then offers a child token iff some item of A_b lies below it --
+ * exactly what HF's PrefixConstrainedLogitsProcessor does with prefix_allowed_tokens_fn(Trie(A_b)) for that user alone; everything
+ * else is -inf, and the -inf fillers are still the lowest token ids of beam 0 that are not offered.
+ * Mechanism: the Trie's leaves are numbered in lexicographic order of their sequences (the leaf RANK), so the leaves below node n
+ * are the contiguous ranks [leaf_lo[n], leaf_hi[n]).  A user's list travels as its distinct leaf ranks in ascending order; node n
+ * is alive for the user iff the number c of its ranks inside [leaf_lo[n], leaf_hi[n]) -- two binary searches -- is > 0 (allow) or
+ * < leaf_hi[n] - leaf_lo[n] (exclude).  Two candidates that spell the same sequence share a leaf: listing either lists the sequence.
+ * All arrays are caller-allocated; gram_workspace_bytes does not change. */
+#define GRAM_MAX_USER_ITEMS 4096 /* entries of one user's list (the preparation kernel sorts them in 16 KB of LDS) */
+#define GRAM_ITEMS_EXCLUDE 0
+#define GRAM_ITEMS_ALLOW 1
+typedef struct {
+  const int32_t* leaf_lo; /* [n_nodes]   first leaf rank below (or at) each node                            */
+  const int32_t* leaf_hi; /* [n_nodes]   one past the last                                                  */
+  const int32_t* ranks;   /* [B][stride] each user's leaf ranks, ascending and distinct                     */
+  const int32_t* count;   /* [B]         how many of them                                                   */
+  int32_t stride;         /* 1 .. GRAM_MAX_USER_ITEMS                                                       */
+  int32_t mode;           /* GRAM_ITEMS_EXCLUDE or GRAM_ITEMS_ALLOW                                         */
+} gram_user_items_t;
+
+/* A call's lists -> gram_user_items_t.ranks / .count.  items i32 [B][M]: indices into the candidate list, -1 = padding (dropped);
+ * item_rank i32 [n_items]: leaf rank of every candidate (an index outside [0, n_items) is dropped like padding: the caller
+ * validates).  One workgroup per user maps, sorts and de-duplicates in LDS.  1 <= M <= stride <= GRAM_MAX_USER_ITEMS. */
+int gram_user_items_prepare(const int32_t* item_rank, int n_items, const int32_t* items, int B, int M, int32_t* ranks,
+                            int32_t* count, int stride, void* stream);
+
+/* gram_beam_step_sparse / gram_beam_step_sparse_live (rowpos != NULL: the live-row form, rows_per_user must be K) with the lists. */
+int gram_beam_step_sparse_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
+                                const void* lm_head_bf16, int d, const float* lse, int V, int cur_len, int rows_per_user,
+                                const int32_t* rowpos, const gram_user_items_t* items_host, void* stream);
+/* gram_beam_step_sparse_split with the lists. */
+int gram_beam_step_sparse_split_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
+                                      const float* lm_head_f32, int d, const float* lse, int V, int cur_len, int rows_per_user,
+                                      const int32_t* rowpos, int pieces, const gram_user_items_t* items_host, void* stream);
+/* gram_greedy_step with the lists: the argmax runs over the alive children. */
+int gram_greedy_step_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const float* logits, int V, int cur_len,
+                           const gram_user_items_t* items_host, void* stream);
+/* Every entry point that takes the lists returns GRAM_E_ARG before any launch for items_host == NULL, a NULL array, a stride
+ * outside 1 .. GRAM_MAX_USER_ITEMS or an unknown mode. */
+
 /* HF 4.26 greedy_search (generate with num_beams == 1; BASELINE configs[0]) on the same state with K = 1:
  * argmax of the RAW logits over the Trie children (first maximum), finished users emit pad; finalize copies
  * the sequences (i64 [B][max_length]) and reports the width HF would return (it stops once all rows hit EOS). */
@@ -486,6 +528,14 @@ int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids, const uint
                      int K, int nret, int max_length, float length_penalty, const gram_trie_t* trie_host,
                      const gram_compaction_t* compaction_host, void* workspace, int64_t workspace_bytes,
                      int64_t* sequences, float* scores, int32_t* width_host, void* stream);
+
+/* gram_generate_ex with per-user item filters (gram_user_items_t, prepared by gram_user_items_prepare on the same stream): every
+ * search step and the greedy step take the lists; everything else -- the encoder, the decoder, the workspace, the live-row
+ * compaction -- is gram_generate_ex's.  The caller guarantees every user at least one item.  GRAM_E_ARG for bad lists as above. */
+int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
+                        int max_length, float length_penalty, const gram_trie_t* trie_host, const gram_compaction_t* compaction_host,
+                        const gram_user_items_t* items_host, void* workspace, int64_t workspace_bytes, int64_t* sequences,
+                        float* scores, int32_t* width_host, void* stream);
 
 /* The encoder layers alone on P independent passages (T5Stack encoder role, gram_t5_modeling.py:1037-1296, up to
  * but excluding final_layer_norm): x_out f32 [P][L][d_model] is the residual stream the final norm, the position

@@ -32,6 +32,7 @@ struct Case {
   bool comp, capped, logits;  // a gram_compaction_t with cached passages; every stage capped to one piece; teacher-forced logits stored
   bool tables;                // the handle has token tables: the trace starts with their build (workspace offsets: the build's scratch)
   int attn;                   // gram_teacher_forced_ex: 1 = every layer's probabilities, 2 = one layer of scratch + token and passage scores
+  bool items;                 // gram_generate_items: per-user item filters (gram_user_items_t)
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -70,6 +71,8 @@ const Case kCases[] = {
     // gram_teacher_forced_ex with attention outputs: the train of tf_folded / tf_p2 plus, per layer, the probabilities and their head sum
     {"tf_attn_probs", TEACHER_FORCED, 1, 1, 2, 3, 32, 3, 4, OFF, false, false, false, false, 1},
     {"tf_p2_attn_scores", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4, OFF, false, false, false, false, 2},
+    // gram_generate_items: the train of generate_p2 with every search step in its per-user-filter form
+    {"generate_p2_items", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, true},
 };
 
 gram_model_t* make_model(int pieces, int fold) {
@@ -127,6 +130,11 @@ int run(const Case& c) {
   void* io[5] = {fake(), fake(), fake(), fake(), fake()};  // the remaining inputs and outputs of the entry, in its argument order
   switch (c.entry) {
     case GENERATE:
+      if (c.items) {
+        const gram_user_items_t items{fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), 64, GRAM_ITEMS_EXCLUDE};
+        return gram_generate_items(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, &items, g_ws, g_ws_bytes,
+                                   (int64_t*)io[0], (float*)io[1], &width, st);
+      }
       return gram_generate_ex(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, g_ws, g_ws_bytes, (int64_t*)io[0],
                               (float*)io[1], &width, st);
     case ENCODE_FUSED:

@@ -49,6 +49,7 @@ void put(const gram_beam_state_t* s) {
          s->hyp_score, s->worst, s->hyp_len, s->hyp_tok, s->error, s->cand_logits, s->cand_logits_users, s->cand_logits_stride);
 }
 void put(const gram_trie_t* t) { fields(t->child_off, t->child_tok, t->child_node, t->n_nodes, t->n_edges, t->max_fanout, t->min_seq_len); }
+void put(const gram_user_items_t* u) { fields(u->leaf_lo, u->leaf_hi, u->ranks, u->count, u->stride, u->mode); }
 void put(const gram_live_rows_t* l) { fields(l->rows, l->rowpos, l->users, l->tokens, l->counts); }
 template <class... A>
 int rec(const char* name, A... a) {
@@ -146,6 +147,20 @@ int gram_beam_step_sparse_live(const gram_beam_state_t* s, const gram_trie_t* tr
 int gram_beam_step_sparse_split(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const float* lm32, int d,
                                 const float* lse, int V, int cur_len, int rows_per_user, const int32_t* rowpos, int pieces, void* st) {
   REC(s, trie, hidden, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, st);
+}
+int gram_beam_step_sparse_items(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, int d,
+                                const float* lse, int V, int cur_len, int rows_per_user, const int32_t* rowpos, const gram_user_items_t* items,
+                                void* st) {
+  REC(s, trie, hidden, lm16, d, lse, V, cur_len, rows_per_user, rowpos, items, st);
+}
+int gram_beam_step_sparse_split_items(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const float* lm32, int d,
+                                      const float* lse, int V, int cur_len, int rows_per_user, const int32_t* rowpos, int pieces,
+                                      const gram_user_items_t* items, void* st) {
+  REC(s, trie, hidden, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, items, st);
+}
+int gram_greedy_step_items(const gram_beam_state_t* s, const gram_trie_t* trie, const float* logits, int V, int cur_len,
+                           const gram_user_items_t* items, void* st) {
+  REC(s, trie, logits, V, cur_len, items, st);
 }
 int gram_greedy_step(const gram_beam_state_t* s, const gram_trie_t* trie, const float* logits, int V, int cur_len, void* st) {
   REC(s, trie, logits, V, cur_len, st);
