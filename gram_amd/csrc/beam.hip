@@ -1300,7 +1300,7 @@ extern "C" int gram_beam_step_sparse_split_items(const gram_beam_state_t* st, co
                                                  int rows_per_user, const int32_t* rowpos, int pieces, const gram_user_items_t* items,
                                                  void* stream) {
   if (int e = check_items(items)) return e;
-  if (!lm_head_f32) return GRAM_E_ARG;
+  if (!lm_head_f32 || !st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
   return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, nullptr, d, rowpos, stream, pieces, lm_head_f32,
                           items);
 }

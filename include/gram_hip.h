@@ -370,7 +370,7 @@ int gram_user_items_prepare(const int32_t* item_rank, int n_items, const int32_t
 int gram_beam_step_sparse_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
                                 const void* lm_head_bf16, int d, const float* lse, int V, int cur_len, int rows_per_user,
                                 const int32_t* rowpos, const gram_user_items_t* items_host, void* stream);
-/* gram_beam_step_sparse_split with the lists. */
+/* gram_beam_step_sparse_split with the lists (rowpos != NULL: rows_per_user must be K, as above). */
 int gram_beam_step_sparse_split_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
                                       const float* lm_head_f32, int d, const float* lse, int V, int cur_len, int rows_per_user,
                                       const int32_t* rowpos, int pieces, const gram_user_items_t* items_host, void* stream);

@@ -118,6 +118,23 @@ def device_live_rows(st, ctrie):
     return o["rows"][:n_rows], o["rowpos"], o["users"][:n_users]
 
 
+def user_items(flat, cands, lists, mode):
+    """B lists of candidate indices (-1 = padding) -> (gram_user_items_t, keep-alive tensors).  The lists go through
+    gram_user_items_prepare on the current stream; ranks and count are prefilled with -7, stride = M = the longest list."""
+    B, M = len(lists), max(1, max(map(len, lists)))
+    items = np.full((B, M), -1, dtype=np.int32)
+    for b, r in enumerate(lists):
+        items[b, : len(r)] = np.asarray(r, dtype=np.int32)
+    dev = torch.device(DEV)
+    lo, hi = flat.leaf_ranges_on(dev)
+    rank = flat.item_ranks_on(dev, cands)[1]
+    t = dict(lo=lo, hi=hi, rank=rank, items=torch.from_numpy(items).to(dev),
+             ranks=torch.full((B, M), -7, dtype=torch.int32, device=dev), count=torch.full((B,), -7, dtype=torch.int32, device=dev))
+    _lib.check(lib().gram_user_items_prepare(p(rank), rank.numel(), p(t["items"]), B, M, p(t["ranks"]), p(t["count"]), M, stream()),
+               "gram_user_items_prepare")
+    return _lib.UserItems(p(lo), p(hi), p(t["ranks"]), p(t["count"]), M, mode), t
+
+
 def vt_blocked(vt):
     """[..., 64, S] (V transposed) -> the bank's layout [..., S/32, 64, 32]: V^T blocked by 32 keys, so that the 64 x 32 tile of a
     32-key step is 4 KiB contiguous (include/gram_hip.h, gram_kv_bank_t)."""
