@@ -94,6 +94,12 @@ class XattnOut(C.Structure):
     _fields_ = [("probs", vp), ("layer_probs", vp), ("token_scores", vp), ("passage_scores", vp)]
 
 
+class TrieRows(C.Structure):
+    """gram_trie_rows_t: the row tables of a Trie for gram_score_trie (device pointers; FlatTrie.decoder_rows)"""
+    _fields_ = [("tokens", vp), ("pos", vp), ("anc", vp), ("row_node", vp), ("node_row", vp), ("node_tok", vp), ("node_leaf", vp),
+                ("Q", i32), ("Tq", i32), ("n_nodes", i32), ("n_leaves", i32)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("vocab", i32), ("d_model", i32), ("d_ff", i32), ("n_heads", i32), ("n_enc_layers", i32),
@@ -208,6 +214,13 @@ SIGNATURES = {
     "gram_xattn_passage_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
     "gram_teacher_forced_ex": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Compaction), vp, vp, C.c_int, C.c_int, vp, i64,
                                          vp, vp, vp, C.POINTER(XattnOut), vp]),
+    # every catalogue item in one decoder pass over the Trie
+    "gram_dec_self_attn_tree_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp]),
+    "gram_trie_repeat_tokens": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "gram_trie_leaf_logprob_split": (C.c_int, [vp, vp, vp, C.c_int, vp, C.POINTER(TrieRows), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "gram_workspace_bytes_trie": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gram_score_trie": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Compaction), C.POINTER(Trie), C.POINTER(TrieRows), vp,
+                                  i64, vp, vp, vp]),
 }
 
 # the `_f16` aliases (gram_hip.h): same signatures as the `_bf16` names

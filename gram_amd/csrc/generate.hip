@@ -835,16 +835,22 @@ Workspace carve_tf(const gram_model* m, void* ws, int B, int N, int L, int C, in
 // whole-sequence one and the cross-attention taking all Q rows of a user; then the lm_head with its LSE partials (logits stored when
 // given) and their combination.  attn != NULL (gram_teacher_forced_ex): every layer's cross-attention is followed by its probabilities
 // (xattn_probs.hip, on the same r.qx and K bank) and their head sum; the passage scores follow the last layer.  These launches only read
-// what the pass computes.
+// what the pass computes.  tree != NULL (gram_score_trie): the Q rows of a user are the rows of a Trie, each attending to its ancestors
+// (T is not used).
 int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, const uint8_t* mask, int B, int N, int L, int Q, int T,
-               float* logits, const gram_xattn_out_t* attn, void* st) {
+               float* logits, const gram_xattn_out_t* attn, const gram_trie_rows_t* tree, void* st) {
   const gram_model_desc_t& c = m->d;
   const int H = c.n_heads, R = B * Q, S = N * L;
   const size_t bank_layer = (size_t)B * H * S * 64;
   const Rows& r = w.dec;
   TRY(decoder_layers(
       m, w, tokens, R, /*qkv0_from_table=*/false,
-      [&](int) { return gram_dec_self_attn_tf_split(r.qkv, c.dec_bias_f32, r.attn, R / T, T, H, w.pieces, r.ps_qkv, st); },
+      [&](int) {
+        if (tree)
+          return gram_dec_self_attn_tree_split(r.qkv, tree->pos, tree->anc, c.dec_bias_f32, r.attn, B, Q, tree->Tq, H, w.pieces, r.ps_qkv,
+                                               st);
+        return gram_dec_self_attn_tf_split(r.qkv, c.dec_bias_f32, r.attn, R / T, T, H, w.pieces, r.ps_qkv, st);
+      },
       [&](int i) {
         TRY(gram_cross_attn_rows_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S, w.pieces,
                                        r.ps_qx, w.ps_bank, w.key_bits, w.rowmap, st));
@@ -889,7 +895,57 @@ extern "C" int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* inpu
   if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
   const gram_model_desc_t& c = m->d;
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
-  TRY(decoder_tf(m, w, dec_ids, mask, B, N, L, C * T, T, logits, attn, stream));
+  TRY(decoder_tf(m, w, dec_ids, mask, B, N, L, C * T, T, logits, attn, nullptr, stream));
   return gram_label_logprob_split(w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, labels, B * C, T, c.vocab, w.pieces,
                                   token_logp, seq_logp, stream);
+}
+
+// ---- every catalogue item in one decoder pass over the Trie (gram_score_trie) ------------------------------------------------------
+namespace {
+
+struct TrieScratch {
+  int32_t* tokens;  // [B * Q]  the row table's tokens repeated per user
+  float* edge;      // [B * Q]  gram_trie_leaf_logprob_split's row_edge
+};
+
+// carve_tf's layout with R = B * Q rows, then the two row tables of the pass
+Workspace carve_trie(const gram_model* m, void* ws, int B, int N, int L, int Q, TrieScratch& ts) {
+  Workspace w = carve_tf(m, ws, B, N, L, Q, 1);
+  Carve cv(ws);
+  cv.off = w.bytes;
+  ts.tokens = cv.take<int32_t>((int64_t)B * Q);
+  ts.edge = cv.take<float>((int64_t)B * Q);
+  w.bytes = (cv.off + 255) & ~(int64_t)255;
+  return w;
+}
+
+}  // namespace
+
+extern "C" int64_t gram_workspace_bytes_trie(const gram_model_t* m, int B, int N, int L, int Q) {
+  if (check_shapes_tf(m, B, N, L, Q, 1)) return GRAM_E_ARG;
+  TrieScratch ts;
+  return carve_trie(m, nullptr, B, N, L, Q, ts).bytes;
+}
+
+extern "C" int gram_score_trie(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                               const gram_compaction_t* comp, const gram_trie_t* trie, const gram_trie_rows_t* rows, void* workspace,
+                               int64_t workspace_bytes, float* leaf_logp, float* node_logp, void* stream) {
+  if (!rows || !trie || rows->Q < 1) return GRAM_E_ARG;
+  const int Q = rows->Q;
+  TRY(check_shapes_tf(m, B, N, L, Q, 1));
+  if (!mask || !leaf_logp || (!comp && !input_ids)) return GRAM_E_ARG;
+  if (!rows->tokens || !rows->pos || !rows->anc || !rows->row_node || !rows->node_row || !rows->node_tok || !rows->node_leaf ||
+      rows->Tq < 1 || rows->Tq > GRAM_MAX_DEC_LEN || rows->n_nodes != trie->n_nodes || rows->n_nodes < 3 || rows->n_leaves < 1 ||
+      rows->n_leaves >= rows->n_nodes || (int64_t)B * rows->n_nodes > INT32_MAX / 4)
+    return GRAM_E_ARG;
+  TRY(check_compaction(comp, B, N));  // (as gram_generate_ex)
+  TrieScratch ts;
+  Workspace w = carve_trie(m, workspace, B, N, L, Q, ts);
+  if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
+  const gram_model_desc_t& c = m->d;
+  TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
+  TRY(gram_trie_repeat_tokens(rows->tokens, ts.tokens, B, Q, stream));
+  TRY(decoder_tf(m, w, ts.tokens, mask, B, N, L, Q, 1, nullptr, nullptr, rows, stream));
+  return gram_trie_leaf_logprob_split(w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, rows, B, c.vocab, w.pieces, ts.edge,
+                                      leaf_logp, node_logp, stream);
 }

@@ -342,6 +342,45 @@ class GRAM(nn.Module):
                                                  users_per_call=users_per_call)
         return (seq, tok) if return_tokens else seq
 
+    @torch.no_grad()
+    def score_all_items(self, input_ids, attention_mask, prefix_allowed_tokens_fn, candidates, length_penalty: Optional[float] = None,
+                        users_per_call: Optional[int] = None):
+        """log p(item | user) of EVERY candidate in one decoder pass: the exact rank of a held-out item, full-ranking metrics at any
+        cut-off (``gram_amd.utils.evaluate.full_ranking``), an exact check on what beam search missed.  input_ids / attention_mask
+        (B, N, L); ``prefix_allowed_tokens_fn`` the Trie closure ``generate`` takes; ``candidates`` the token sequences the Trie was
+        built from (the list ``sequence_items`` takes).  Returns (B, len(candidates)) fp32: column i is the value ``score_sequences``
+        returns for ``candidates[i]`` -- the decoder runs on one row per internal Trie node instead of one per (candidate, position),
+        and computes the same expressions.  Two candidates that spell one sequence get one score, in
+        two columns: give ``full_ranking`` the identities ``sequence_ids=FlatTrie(trie).item_ranks(candidates)`` so that such a
+        sequence is ranked once.  With ``length_penalty`` the sums are divided by ``len ** length_penalty`` (len = the label count, EOS included; the power in
+        float64), as BeamHypotheses.add does: the columns are then comparable with ``sequences_scores``.  Users are scored in
+        chunks whose workspace fits the free HBM (``users_per_call`` overrides); a user's scores do not depend on the chunk."""
+        if self._device().type != "cuda":
+            raise NotImplementedError("gram_amd.GRAM.score_all_items runs on a ROCm device (model.to('cuda')); there is no CPU path")
+        if input_ids.dim() != 3:
+            raise ValueError("input_ids must be (B, N, L)")
+        if prefix_allowed_tokens_fn is None or self._closure_trie(prefix_allowed_tokens_fn) is None:
+            raise ValueError("score_all_items needs the Trie closure form of prefix_allowed_tokens_fn (the Trie is what is scored)")
+        if len(candidates) < 1:
+            raise ValueError("score_all_items: `candidates` is empty")
+        dev = self._device()
+        V = int(self.config.vocab_size)
+        flat = self._flat_trie(prefix_allowed_tokens_fn)
+        rows, tables = flat.decoder_rows_on(dev, start_token=int(self.config.decoder_start_token_id))
+        _ranks_host, ranks = flat.item_ranks_on(dev, candidates)
+        _ctrie, (t_off, t_tok, t_node) = flat.to_device(dev)
+        outs, _Lp = self._tf_chunks(input_ids, attention_mask, None, None,
+                                    lambda cid, cmask, handle, ws, _dec, _lab, *comp: torch.ops.gram.score_trie(
+                                        cid, cmask, handle, ws, t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len),
+                                        *tables, int(rows.n_leaves), V, False, *comp)[0],
+                                    users_per_call=users_per_call, trie_rows=(int(rows.Q), int(rows.n_leaves)))
+        leaf = outs[0] if len(outs) == 1 else torch.cat(outs)
+        scores = leaf.index_select(1, ranks.to(torch.int64))
+        if length_penalty is not None:
+            lens = torch.tensor([len(c) - 1 for c in candidates], dtype=torch.float64, device=dev)  # labels: the start token is not one
+            scores = (scores.double() / lens ** float(length_penalty)).float()
+        return scores
+
     def _check_labels(self, labels: torch.Tensor) -> torch.Tensor:
         V = self.config.vocab_size
         if labels.numel() and not bool(((labels >= 0) & (labels < V) | (labels == -100)).all()):
@@ -355,20 +394,38 @@ class GRAM(nn.Module):
         (the attention buffers of ``cross_attentions`` / ``passage_attention``)."""
         handle = self._pack()
         lib = _lib.load()
-        dev = self._device()
         Lp = (int(L) + 31) // 32 * 32
-        free, _total = torch.cuda.mem_get_info(dev)
-        if self._workspace is not None and self._workspace.device == dev:
-            free += self._workspace.numel()
-        pc_have = 0 if self._pcache is None else int(self._pcache["x"].shape[0])
-        pc_more = max(0, int(getattr(self, "_pcache_reserve", 0)) - pc_have)
-        budget = int(free * headroom) - pc_more * self._CACHE_L * (self.config.d_model * 4 + 4)
         per_user_out = C_ * T * 4 * (2 + (self.config.vocab_size if want_logits else 0)) + int(extra_per_user)
 
         def need(b):
             w = lib.gram_workspace_bytes_tf(handle, b, N, Lp, C_, T)
             return -1 if w < 0 else w + b * per_user_out
 
+        return self._largest_chunk(need, limit, headroom)
+
+    def max_users_per_call_trie(self, N: int, L: int, Q: int, n_out: int, limit: int = 1 << 20, headroom: float = 0.9) -> int:
+        """``max_users_per_call_tf`` for the one-pass scoring of a Trie (gram_workspace_bytes_trie): Q decoder rows and ``n_out``
+        fp32 outputs per user."""
+        handle = self._pack()
+        lib = _lib.load()
+        Lp = (int(L) + 31) // 32 * 32
+
+        def need(b):
+            w = lib.gram_workspace_bytes_trie(handle, b, N, Lp, Q)
+            return -1 if w < 0 else w + b * 4 * int(n_out)
+
+        return self._largest_chunk(need, limit, headroom)
+
+    def _largest_chunk(self, need, limit: int, headroom: float) -> int:
+        """Largest B <= limit with 0 <= need(B) <= the free HBM (this model's workspace counts as free) * headroom, net of what a
+        reserved passage cache will still allocate; at least 1."""
+        dev = self._device()
+        free, _total = torch.cuda.mem_get_info(dev)
+        if self._workspace is not None and self._workspace.device == dev:
+            free += self._workspace.numel()
+        pc_have = 0 if self._pcache is None else int(self._pcache["x"].shape[0])
+        pc_more = max(0, int(getattr(self, "_pcache_reserve", 0)) - pc_have)
+        budget = int(free * headroom) - pc_more * self._CACHE_L * (self.config.d_model * 4 + 4)
         lo, hi = 1, max(1, int(limit))
         if 0 <= need(hi) <= budget:
             return hi
@@ -381,27 +438,36 @@ class GRAM(nn.Module):
         return lo
 
     def _tf_chunks(self, input_ids, attention_mask, dec, lab, call, want_logits: bool = False, extra_bytes=None,
-                   users_per_call: Optional[int] = None):
+                   users_per_call: Optional[int] = None, trie_rows=None):
         """The teacher-forced pass over user chunks whose workspace and outputs fit the free HBM: ``call(ids, mask, handle, workspace,
         dec, lab, compaction fields)`` per chunk -> (the list of its results, the padded passage length).  ``extra_bytes(Lp)``: further
-        output bytes per user."""
+        output bytes per user.  ``trie_rows=(Q, n_out)``: the one-pass scoring of a Trie instead -- Q decoder rows and n_out fp32
+        outputs per user, the workspace of gram_workspace_bytes_trie, no dec / lab (``call`` gets None for both)."""
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()
         B, N, L = input_ids.shape
-        _, Cn, T = dec.shape
-        if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN:
-            raise ValueError(f"sequences of 1..{_lib.GRAM_MAX_DEC_LEN} positions are supported (got {T})")
         ids = input_ids.to(dev, torch.int64)
         mask = attention_mask.to(dev).ne(0).view(torch.uint8) if attention_mask.dtype != torch.bool else attention_mask.to(dev).view(torch.uint8)
         Lp = (L + 31) // 32 * 32  # masked padding is invisible to attention: pad L to the kernel tile (as generate)
         if Lp != L:
             ids = torch.nn.functional.pad(ids, (0, Lp - L))
             mask = torch.nn.functional.pad(mask, (0, Lp - L))
-        dec = dec.to(dev, torch.int32).contiguous()
-        lab = lab.to(dev, torch.int32).contiguous()
-        step = int(users_per_call) if users_per_call else self.max_users_per_call_tf(N, Lp, Cn, T, want_logits, limit=B,
-                                                                                     extra_per_user=extra_bytes(Lp) if extra_bytes else 0)
+        if trie_rows is None:
+            _, Cn, T = dec.shape
+            if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN:
+                raise ValueError(f"sequences of 1..{_lib.GRAM_MAX_DEC_LEN} positions are supported (got {T})")
+            dec = dec.to(dev, torch.int32).contiguous()
+            lab = lab.to(dev, torch.int32).contiguous()
+            step = int(users_per_call) if users_per_call else self.max_users_per_call_tf(
+                N, Lp, Cn, T, want_logits, limit=B, extra_per_user=extra_bytes(Lp) if extra_bytes else 0)
+            ws_bytes = lambda nb: lib.gram_workspace_bytes_tf(handle, nb, N, Lp, Cn, T)  # noqa: E731
+            size = f"C={Cn} T={T}"
+        else:
+            Qr, n_out = trie_rows
+            step = int(users_per_call) if users_per_call else self.max_users_per_call_trie(N, Lp, Qr, n_out, limit=B)
+            ws_bytes = lambda nb: lib.gram_workspace_bytes_trie(handle, nb, N, Lp, Qr)  # noqa: E731
+            size = f"Q={Qr}"
         from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
         outs = []
         for b0 in range(0, B, max(1, step)):
@@ -409,14 +475,17 @@ class GRAM(nn.Module):
             nb = b1 - b0
             cid, cmask = ids[b0:b1].contiguous(), mask[b0:b1].contiguous()
             comp, _harvest = self._plan(cid, cmask, nb, N, Lp)
-            need = lib.gram_workspace_bytes_tf(handle, nb, N, Lp, Cn, T)
+            need = ws_bytes(nb)
             if need < 0:
-                raise _lib.GramHipError(f"unsupported problem size B={nb} N={N} L={Lp} C={Cn} T={T} (N <= max_item_num+1, L <= 128, "
+                raise _lib.GramHipError(f"unsupported problem size B={nb} N={N} L={Lp} {size} (N <= max_item_num+1, L <= 128, "
                                         f"N*L <= 4096, T <= {_lib.GRAM_MAX_DEC_LEN})")
             ws = self._ensure_workspace(need)
             ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
-            # (a chunk's slice of dec / lab starts wherever the rows before it end: a copy is 16-byte aligned, as the ops require)
-            cdec, clab = (dec[b0:b1], lab[b0:b1]) if dec[b0:b1].data_ptr() % 16 == 0 else (dec[b0:b1].clone(), lab[b0:b1].clone())
+            if trie_rows is not None:
+                cdec = clab = None
+            else:
+                # (a chunk's slice of dec / lab starts wherever the rows before it end: a copy is 16-byte aligned, as the ops require)
+                cdec, clab = (dec[b0:b1], lab[b0:b1]) if dec[b0:b1].data_ptr() % 16 == 0 else (dec[b0:b1].clone(), lab[b0:b1].clone())
             outs.append(call(cid, cmask, int(handle), ws, cdec, clab, ct["comp_map"], ct["comp_ids"], ct["comp_mask"], ct["cache_slot"],
                              ct["cache_x"], int(ct["n_cached"]), int(ct["cache_L"])))
         return outs, Lp

@@ -12,6 +12,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
                                      ``GRAM.score_sequences``
     torch.ops.gram.teacher_forced_attn  the same pass with its cross-attention probabilities (gram_teacher_forced_ex) --
                                      ``GRAM.cross_attentions`` and ``GRAM.passage_attention``
+    torch.ops.gram.score_trie        every leaf of the Trie scored in one decoder pass over its internal nodes (gram_score_trie) --
+                                     ``GRAM.score_all_items``
     torch.ops.gram.linear            nn.Linear without bias: A @ W^T on the 16-bit MFMA (gram_gemm_bf16, 16-bit epilogue)
     torch.ops.gram.enc_self_attn     T5Attention self branch on (P*L, 3*inner) q|k|v rows (gram_enc_self_attn)
     torch.ops.gram.cross_attn_decode the fusion read of one decoder layer and step over the beam-shared bank
@@ -274,6 +276,72 @@ def _(input_ids, attention_mask, handle, workspace, decoder_input_ids, labels, v
             decoder_input_ids.new_empty((B, Q, N) if want_scores else (0,), **f))
 
 
+# ---------------------------------------------------------------------------------------------- every item in one pass over the Trie
+@torch.library.custom_op("gram::score_trie", mutates_args=("workspace",), device_types="cuda")
+def score_trie(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor, trie_child_tok: Tensor,
+               trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, row_tokens: Tensor, row_pos: Tensor, row_anc: Tensor,
+               row_node: Tensor, node_row: Tensor, node_tok: Tensor, node_leaf: Tensor, n_leaves: int, vocab_size: int, want_nodes: bool,
+               comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor],
+               cache_x: Optional[Tensor], n_cached: int, cache_L: int) -> Tuple[Tensor, Tensor]:
+    """input_ids i64 (B,N,L), attention_mask u8 (B,N,L), ``handle`` a gram_model_t* as int, ``workspace`` a u8 scratch tensor of
+    gram_workspace_bytes_trie; the Trie as its CSR arrays (gram_trie_t) and its row tables (gram_trie_rows_t,
+    ``FlatTrie.decoder_rows``): row_tokens / row_pos / row_node i32 (Q,), row_anc i32 (Q, Tq), node_row / node_tok / node_leaf i32
+    (n_nodes,); comp_* / cache_* the gram_compaction_t fields (None = off).  Returns (log p(item | user) f32 (B, n_leaves) by leaf
+    rank, the per-edge terms f32 (B, n_nodes) by the node an edge enters -- empty unless want_nodes)."""
+    lib = _lib.load()
+    dev = input_ids.device
+    if input_ids.dim() != 3 or row_anc.dim() != 2:
+        raise ValueError("score_trie: input_ids must be (B, N, L) and row_anc (Q, Tq)")
+    B, N, L = input_ids.shape
+    Q, Tq = row_anc.shape
+    n_nodes = trie_child_off.numel() - 1
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),)), ("row_tokens", row_tokens, (Q,)),
+                           ("row_pos", row_pos, (Q,)), ("row_anc", row_anc, (Q, Tq)), ("row_node", row_node, (Q,)),
+                           ("node_row", node_row, (n_nodes,)), ("node_tok", node_tok, (n_nodes,)), ("node_leaf", node_leaf, (n_nodes,))):
+        _check(name, t, torch.int32, shape, dev)
+    if Q < 1 or not 1 <= Tq <= _lib.GRAM_MAX_DEC_LEN or n_nodes < 3 or not 1 <= n_leaves < n_nodes:
+        raise ValueError(f"score_trie: need Q >= 1 rows, 1 <= Tq <= {_lib.GRAM_MAX_DEC_LEN}, a Trie with a leaf (got Q={Q}, Tq={Tq}, "
+                         f"n_nodes={n_nodes}, n_leaves={n_leaves})")
+    # the tables index the embedding, the lm_head, the rows and the outputs on the device: out-of-range entries are refused here
+    lim = torch.stack([row_tokens.min(), row_tokens.max(), row_pos.min(), row_pos.max(), row_anc.min(), row_anc.max(), row_node.min(),
+                       row_node.max(), node_row.min(), node_row.max(), node_tok.min(), node_tok.max(), node_leaf.min(),
+                       node_leaf.max()]).tolist()
+    ok = (0 <= lim[0] and lim[1] < vocab_size and 0 <= lim[2] and lim[3] < Tq and 0 <= lim[4] and lim[5] < Q and 0 <= lim[6]
+          and lim[7] < n_nodes and -1 <= lim[8] and lim[9] < Q and -1 <= lim[10] and lim[11] < vocab_size and -1 <= lim[12]
+          and lim[13] < n_leaves)
+    if not ok:
+        raise ValueError("score_trie: a row table entry is out of range (tokens in [0, vocab), pos in [0, Tq), anc in [0, Q), "
+                         "row_node in [0, n_nodes), node_row in [-1, Q), node_tok in [-1, vocab), node_leaf in [-1, n_leaves))")
+    trie = _lib.Trie(trie_child_off.data_ptr(), trie_child_tok.data_ptr(), trie_child_node.data_ptr(), n_nodes, trie_child_tok.numel(),
+                     trie_max_fanout, trie_min_seq_len)
+    rows = _lib.TrieRows(row_tokens.data_ptr(), row_pos.data_ptr(), row_anc.data_ptr(), row_node.data_ptr(), node_row.data_ptr(),
+                         node_tok.data_ptr(), node_leaf.data_ptr(), Q, Tq, n_nodes, n_leaves)
+    comp = None
+    if comp_map is not None:
+        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
+                               _p(cache_slot))
+    leaf = torch.empty(B, n_leaves, dtype=torch.float32, device=dev)
+    nodes = torch.empty((B, n_nodes) if want_nodes else (0,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.gram_score_trie(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
+                                 C.byref(comp) if comp is not None else None, C.byref(trie), C.byref(rows), workspace.data_ptr(),
+                                 workspace.numel(), leaf.data_ptr(), nodes.data_ptr() if want_nodes else None, _stream(input_ids))
+    _lib.check(rc, "gram_score_trie")
+    return leaf, nodes
+
+
+@score_trie.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len,
+      row_tokens, row_pos, row_anc, row_node, node_row, node_tok, node_leaf, n_leaves, vocab_size, want_nodes, comp_map, comp_ids,
+      comp_mask, cache_slot, cache_x, n_cached, cache_L):
+    B = input_ids.shape[0]
+    f = dict(dtype=torch.float32)
+    return (input_ids.new_empty(B, n_leaves, **f), input_ids.new_empty((B, trie_child_off.numel() - 1) if want_nodes else (0,), **f))
+
+
 # ---------------------------------------------------------------------------------------------- linear
 @torch.library.custom_op("gram::linear", mutates_args=(), device_types="cuda")
 def linear(a: Tensor, w: Tensor, relu: bool = False) -> Tensor:
@@ -407,4 +475,4 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
-__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]
+__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "score_trie", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]

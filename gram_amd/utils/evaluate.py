@@ -102,3 +102,43 @@ def hit_ranks_from_ids(pred_ids: np.ndarray, scores: np.ndarray, gold_ids: np.nd
     rel = np.take_along_axis(pred_ids, order, axis=1) == gold_ids[:, None]
     first = rel.argmax(axis=1)
     return np.where(rel.any(axis=1), first, -1).astype(np.int16)
+
+
+def full_ranking(scores, target_idx, ks: Sequence[int], sequence_ids=None):
+    """Exact full-ranking metrics from the score of EVERY candidate (``GRAM.score_all_items``), computed on the scores' device.
+
+    scores (B, M) tensor, one column per Trie leaf or per candidate; target_idx (B,) the column of each user's held-out item; ks the
+    cut-offs.  A user's rank is 1 + the number of DISTINCT sequences that score strictly higher than its target (ties do not push
+    the target down).  Columns indexed by candidate may repeat a sequence: pass ``sequence_ids`` (M,), an integer identity per
+    column that two columns share exactly when they spell the same sequence (``FlatTrie.item_ranks``), and only the first column
+    of every sequence is counted; columns indexed by leaf rank need none.  Returns a dict of (B,) tensors: ``"rank"`` (int64),
+    ``"mrr"`` = 1 / rank, and per k ``"hit@k"`` = [rank <= k] and ``"ndcg@k"`` = [rank <= k] / log2(rank + 1) (float64; leave-one-out,
+    IDCG = 1, the value :func:`ndcg_at_k` gives a gold at position rank - 1).  The caller sums or averages over users."""
+    import torch
+
+    if scores.dim() != 2:
+        raise ValueError("full_ranking: scores must be (B, M)")
+    B, M = scores.shape
+    dev = scores.device
+    tgt = torch.as_tensor(target_idx, device=dev).to(torch.int64).reshape(-1)
+    if tgt.numel() != B or (B and (int(tgt.min()) < 0 or int(tgt.max()) >= M)):
+        raise ValueError(f"full_ranking: target_idx must hold one column index in [0, {M}) per user")
+    higher = scores > scores.gather(1, tgt[:, None])
+    if sequence_ids is not None:
+        sid = torch.as_tensor(sequence_ids, device=dev).to(torch.int64).reshape(-1)
+        if sid.numel() != M:
+            raise ValueError(f"full_ranking: sequence_ids must hold one identity per column ({M})")
+        order = torch.argsort(sid, stable=True)
+        srt = sid[order]
+        first_sorted = torch.ones(M, dtype=torch.bool, device=dev)
+        first_sorted[1:] = srt[1:] != srt[:-1]
+        first = torch.empty(M, dtype=torch.bool, device=dev)
+        first[order] = first_sorted
+        higher = higher & first[None, :]
+    rank = 1 + higher.sum(dim=1)
+    out = {"rank": rank, "mrr": 1.0 / rank.double()}
+    for k in ks:
+        hit = (rank <= int(k)).double()
+        out[f"hit@{int(k)}"] = hit
+        out[f"ndcg@{int(k)}"] = hit / torch.log2(rank.double() + 1.0)
+    return out

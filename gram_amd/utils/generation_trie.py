@@ -122,6 +122,15 @@ def exact_match(predictions, targets, k):
     return correct
 
 
+class DecoderRows:
+    """Host arrays of ``gram_trie_rows_t`` (:meth:`FlatTrie.decoder_rows`): int32 ``tokens`` / ``pos`` / ``row_node`` [Q], ``anc``
+    [Q][Tq], ``node_row`` / ``node_tok`` / ``node_leaf`` [n_nodes], and the counts Q, Tq, n_nodes, n_leaves."""
+    ARRAYS = ("tokens", "pos", "anc", "row_node", "node_row", "node_tok", "node_leaf")
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 class FlatTrie:
     """CSR layout of a :class:`Trie` (include/gram_hip.h ``gram_trie_t``).
 
@@ -136,6 +145,7 @@ class FlatTrie:
         self._device = {}
         self._node_item = None
         self._leaf_ranges = None
+        self._decoder_rows = {}
         seqs = trie.sequences() if isinstance(trie, Trie) else None
         if seqs:
             self._from_sequences(seqs)
@@ -300,6 +310,83 @@ class FlatTrie:
             lo[lv] = lo[parent[lv]] + sib[lv]
         self._leaf_ranges = (lo.astype(np.int32), (lo + cnt).astype(np.int32))
         return self._leaf_ranges
+
+    def decoder_rows(self, start_token: int = 0) -> "DecoderRows":
+        """The row tables of the one-pass scoring of every item (include/gram_hip.h ``gram_trie_rows_t``, ``GRAM.score_all_items``).
+
+        A teacher-forced decoder row depends on its prefix only, so one row per distinct proper prefix scores every candidate: the
+        rows are the INTERNAL nodes below the root (nodes with children; leaves get none, nothing is predicted after EOS), in node
+        order, which keeps every depth contiguous.  HF's first decoder input is the start token and the constraint is asked
+        ``get([start])``: row 0 is the root's child carrying ``start_token``, and it must be the root's only child (``generate``
+        could never return a candidate that starts otherwise, so its score is undefined) -- ``ValueError`` if not, or if a row would
+        sit at a position beyond ``GRAM_MAX_DEC_LEN``.  Built once per Trie and start token from the CSR arrays alone (both
+        constructors), one vectorised pass per level."""
+        cached = self._decoder_rows.get(int(start_token))
+        if cached is not None:
+            return cached
+        from .. import _lib
+
+        n = self.n_nodes
+        fan = np.diff(self.child_off).astype(np.int64)
+        root_toks = self.child_tok[int(self.child_off[0]):int(self.child_off[1])]
+        if int(start_token) not in root_toks.tolist():
+            raise ValueError(f"decoder_rows: no candidate starts with the decoder start token {int(start_token)}")
+        if len(root_toks) != 1:
+            raise ValueError(f"decoder_rows: a candidate starts with a token other than the decoder start token {int(start_token)} "
+                             f"(generate could never return it: its score is undefined)")
+        child = self.child_node.astype(np.int64)
+        parent = np.zeros(n, dtype=np.int64)
+        parent[child] = np.repeat(np.arange(n, dtype=np.int64), fan)
+        node_tok = np.full(n, -1, dtype=np.int64)
+        node_tok[child] = self.child_tok
+        depth = np.zeros(n, dtype=np.int64)
+        levels, frontier = [], np.zeros(1, dtype=np.int64)
+        while frontier.size:
+            levels.append(frontier)
+            counts = fan[frontier]
+            first = self.child_off[frontier].astype(np.int64)
+            edges = np.repeat(first - (np.cumsum(counts) - counts), counts) + np.arange(int(counts.sum()), dtype=np.int64)
+            frontier = child[edges]
+            depth[frontier] = len(levels)
+        internal = (fan > 0) & (np.arange(n) > 0)
+        row_node = np.nonzero(internal)[0]
+        Q = int(row_node.size)
+        if Q < 1:
+            raise ValueError("decoder_rows: the Trie has no candidate longer than the start token")
+        row_of = np.full(n, -1, dtype=np.int64)
+        row_of[row_node] = np.arange(Q)
+        pos = depth[row_node] - 1
+        Tq = int(pos.max()) + 1
+        if Tq > _lib.GRAM_MAX_DEC_LEN:
+            raise ValueError(f"decoder_rows: the longest candidate needs {Tq} decoder positions; at most {_lib.GRAM_MAX_DEC_LEN} "
+                             f"(GRAM_MAX_DEC_LEN) are supported")
+        if (np.diff(pos) < 0).any():
+            raise ValueError("decoder_rows: the Trie's nodes are not numbered level by level")
+        anc = np.zeros((Q, Tq), dtype=np.int64)
+        parent_row = row_of[parent[row_node]]  # -1 for row 0 (its parent is the root)
+        for t in range(Tq):
+            rows = np.nonzero(pos == t)[0]
+            if t:
+                anc[rows, :t] = anc[parent_row[rows], :t]
+            anc[rows, t] = rows
+        lo, hi = self.leaf_ranges()
+        leaf = (fan == 0) & (np.arange(n) > 0)
+        out = DecoderRows(tokens=node_tok[row_node].astype(np.int32), pos=pos.astype(np.int32), anc=anc.astype(np.int32),
+                          row_node=row_node.astype(np.int32), node_row=row_of[parent].astype(np.int32), node_tok=node_tok.astype(np.int32),
+                          node_leaf=np.where(leaf, lo, -1).astype(np.int32), Q=Q, Tq=Tq, n_nodes=n, n_leaves=int(hi[0]))
+        out.node_row[0] = -1  # (the root is its own parent in `parent`)
+        self._decoder_rows[int(start_token)] = out
+        return out
+
+    def decoder_rows_on(self, device, start_token: int = 0):
+        """(:meth:`decoder_rows`, its seven arrays as device tensors in ``gram_trie_rows_t``'s field order), uploaded once per device."""
+        import torch
+
+        key = ("rows", str(device), int(start_token))
+        if key not in self._device:
+            rows = self.decoder_rows(start_token)
+            self._device[key] = (rows, tuple(torch.from_numpy(np.ascontiguousarray(getattr(rows, f))).to(device) for f in DecoderRows.ARRAYS))
+        return self._device[key]
 
     def item_ranks(self, candidates: Sequence[Sequence[int]]) -> np.ndarray:
         """int32 [len(candidates)]: the leaf rank (:meth:`leaf_ranges`) of every candidate -- the token sequences the Trie was

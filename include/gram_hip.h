@@ -633,6 +633,66 @@ int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* input_ids, cons
                            void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
                            const gram_xattn_out_t* attn_host, void* stream);
 
+/* ---- every catalogue item in one decoder pass over the Trie (GRAM.score_all_items) -----------------------------------------
+ * The teacher-forced pass above spends one decoder row per (candidate, position); two candidates that share an id prefix share every
+ * decoder state along it (a teacher-forced row depends on its prefix only: gram_t5.py:181-263 with the causal self-attention of
+ * gram_t5_modeling.py:586-593).  Here the rows of a user are the INTERNAL NODES of the flat Trie below the root -- one per distinct
+ * proper prefix -- each attending to its ancestors, and a leaf's log p(item | user) is the sum of the edge terms along its path.
+ * Rows are user-major (b, i): B users x Q rows, R = B * Q. */
+
+/* The row tables of a Trie (gram_amd.utils.generation_trie.FlatTrie.decoder_rows), device pointers.  Row order follows node order, so
+ * every depth is contiguous; row 0 is the root's only child, the decoder start token. */
+typedef struct {
+  const int32_t* tokens;    /* [Q]       decoder input of the row: its node's own token                                        */
+  const int32_t* pos;       /* [Q]       position t of the row = depth of its node - 1                                         */
+  const int32_t* anc;       /* [Q][Tq]   row of the ancestor at every position j <= pos[i]; anc[i][pos[i]] = i; rest unused    */
+  const int32_t* row_node;  /* [Q]       Trie node of the row                                                                  */
+  const int32_t* node_row;  /* [n_nodes] row of the node's PARENT (the row that predicts the node); -1: the root and row 0's   */
+  const int32_t* node_tok;  /* [n_nodes] token on the edge into the node                                                       */
+  const int32_t* node_leaf; /* [n_nodes] leaf rank (FlatTrie.leaf_ranges) of a leaf, -1 elsewhere                              */
+  int32_t Q, Tq;            /* rows; Tq = max pos + 1 <= GRAM_MAX_DEC_LEN                                                      */
+  int32_t n_nodes, n_leaves;
+} gram_trie_rows_t;
+
+/* Causal self-attention of Q rows per user where row i (global row b * Q + i) attends to the rows anc[i][0 .. pos[i]] of the same
+ * user (T5Attention.forward self branch with the causal mask, gram_t5_modeling.py:586-593, on the prefix row i stands for).  qkv:
+ * planar pieces [B * Q][3 * inner], qkv_pstride elements apart; bias f32 [H][GRAM_MAX_DEC_LEN] by distance pos[i] - j; out as
+ * gram_dec_self_attn_tf_split's (interleaved [rows][2 * inner] when pieces = 2).  The expression is gram_dec_self_attn_tf_split's: a
+ * tree row and the same prefix there give the same bits.  pos / anc entries out of range are clamped, not followed.  A null pointer,
+ * Tq outside 1..GRAM_MAX_DEC_LEN, H outside 1..16, pieces outside 1..2 or a piece stride shorter than the rows: GRAM_E_ARG before
+ * any launch. */
+int gram_dec_self_attn_tree_split(const void* qkv, const int32_t* pos, const int32_t* anc, const float* bias, void* out, int B, int Q,
+                                  int Tq, int H, int pieces, int64_t qkv_pstride, void* stream);
+
+/* out i32 [B * Q]: out[b * Q + i] = tokens[i], the decoder inputs of gram_score_trie's rows. */
+int gram_trie_repeat_tokens(const int32_t* tokens, int32_t* out, int B, int Q, void* stream);
+
+/* Item scores from the final hidden rows (the lm_head and log-softmax of gram_t5.py:181-263 at the Trie's tokens only).  For every edge (row i -> child node c with token tok):
+ * term[b][c] = hidden[b * Q + i] . E[tok] - lse[b * Q + i], the dot product being gram_label_logprob_split's (E = lm_head_f32 when
+ * pieces = 2, lm_head_bf16 when 1); leaf_logp[b][rank] = the sum of the terms along the leaf's path in position order, starting from
+ * 0.f -- the sum gram_label_logprob_split and the beam's running score make (one writer per element, no atomics).  Two launches: the
+ * terms of the edges into rows go to row_edge (device scratch f32 [B * Q]), then every leaf adds its own term to those of its path.
+ * leaf_logp f32 [B][n_leaves] by leaf rank; node_logp f32 [B][n_nodes] or NULL: the term of the edge into every node (0 for the
+ * root and row 0's node).  hidden and lse as gram_label_logprob_split takes them. */
+int gram_trie_leaf_logprob_split(const void* hidden, const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse,
+                                 const gram_trie_rows_t* rows_host, int B, int V, int pieces, float* row_edge, float* leaf_logp,
+                                 float* node_logp, void* stream);
+
+/* Bytes of scratch gram_score_trie needs: gram_workspace_bytes_tf's layout with R = B * Q rows (and the same shape checks with B * Q
+ * in place of B * C * T), plus the repeated tokens and the edge terms, [B * Q] each.  < 0: GRAM_E_ARG. */
+int64_t gram_workspace_bytes_trie(const gram_model_t* m, int B, int N, int L, int Q);
+
+/* log p(item | user) of every leaf of the Trie -- T5ForConditionalGeneration_GRAM.forward with labels (gram_t5.py:181-263) for every
+ * candidate at once, each shared prefix computed once: the encoder as gram_generate_ex runs it, the decoder layers over the B * Q rows of
+ * rows_host (the decoder inputs are rows_host->tokens repeated per user by gram_trie_repeat_tokens: the caller passes no token
+ * tensor) with gram_dec_self_attn_tree_split as the self-attention and gram_cross_attn_rows_split as the cross-attention, the lm_head
+ * with its LSE partials (no logits), gram_lse_combine, gram_trie_leaf_logprob_split.  trie_host: the Trie the tables were built from
+ * (its n_nodes must equal rows_host's).  leaf_logp f32 [B][n_leaves], node_logp f32 [B][n_nodes] or NULL.  Shapes and pointers are
+ * checked before any launch (GRAM_E_ARG). */
+int gram_score_trie(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                    const gram_compaction_t* compaction_host, const gram_trie_t* trie_host, const gram_trie_rows_t* rows_host,
+                    void* workspace, int64_t workspace_bytes, float* leaf_logp, float* node_logp, void* stream);
+
 /* ---- live per-kernel timing (bench.py) ------------------------------------------------ */
 enum gram_kernel_kind {
   GRAM_K_GEMM = 0,          /* work = 2*M*N*K flops per launch                              */

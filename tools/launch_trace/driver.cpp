@@ -22,12 +22,12 @@ T* fake() {
   return (T*)g_next;
 }
 
-enum Entry { GENERATE, ENCODE_FUSED, ENCODE_PASSAGES, DECODE_STEP, TEACHER_FORCED };
+enum Entry { GENERATE, ENCODE_FUSED, ENCODE_PASSAGES, DECODE_STEP, TEACHER_FORCED, SCORE_TRIE };
 enum Live { OFF, NONE, SOME, ALL };  // live rows off, or on with gram_live_rows reporting no row, some rows, every row
 struct Case {
   const char* name;
   Entry entry;
-  int pieces, fold, B, N, L, K, T;  // K: beams, or sequences per user of the teacher-forced pass; T: max_length
+  int pieces, fold, B, N, L, K, T;  // K: beams, or sequences per user of the teacher-forced pass; T: max_length (SCORE_TRIE: K * T rows per user)
   Live live;
   bool comp, capped, logits;  // a gram_compaction_t with cached passages; every stage capped to one piece; teacher-forced logits stored
   bool tables;                // the handle has token tables: the trace starts with their build (workspace offsets: the build's scratch)
@@ -73,6 +73,10 @@ const Case kCases[] = {
     {"tf_p2_attn_scores", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4, OFF, false, false, false, false, 2},
     // gram_generate_items: the train of generate_p2 with every search step in its per-user-filter form
     {"generate_p2_items", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, true},
+    // gram_score_trie over Q = 12 rows per user: the train of tf_folded / tf_p2 (the same 24 rows) with the tokens repeated per user,
+    // the tree self-attention in every layer and the Trie reduction in place of the label log-probs
+    {"score_trie_folded", SCORE_TRIE, 1, 1, 2, 3, 32, 3, 4},
+    {"score_trie_p2", SCORE_TRIE, 2, 1, 2, 3, 32, 3, 4},
 };
 
 gram_model_t* make_model(int pieces, int fold) {
@@ -125,6 +129,10 @@ int run(const Case& c) {
   trace_line("gram_workspace_bytes_tf", gram_workspace_bytes_tf(m, B, N, L, K, T));
   trace_line("gram_workspace_encoder_x_offset", gram_workspace_encoder_x_offset(m, B, N, L, K, T));
   g_ws_bytes = c.entry == TEACHER_FORCED ? gram_workspace_bytes_tf(m, B, N, L, K, T) : gram_workspace_bytes(m, B, N, L, K, T);
+  if (c.entry == SCORE_TRIE) {
+    g_ws_bytes = gram_workspace_bytes_trie(m, B, N, L, K * T);
+    trace_line("gram_workspace_bytes_trie", g_ws_bytes);
+  }
   g_ws = (char*)calloc(g_ws_bytes, 1);  // zeroed, and touched only where a stub writes: a large case costs address space alone
   int32_t width = -1;
   void* io[5] = {fake(), fake(), fake(), fake(), fake()};  // the remaining inputs and outputs of the entry, in its argument order
@@ -152,6 +160,11 @@ int run(const Case& c) {
       }
       return gram_teacher_forced(m, ids, mask, B, N, L, c.comp ? &comp : nullptr, (int32_t*)io[0], (int32_t*)io[1], K, T, g_ws, g_ws_bytes,
                                  c.logits ? (float*)io[2] : nullptr, (float*)io[3], (float*)io[4], st);
+    case SCORE_TRIE: {
+      const gram_trie_rows_t rows{fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), fake<int32_t>(),
+                                  fake<int32_t>(), K * T, T, trie.n_nodes, 27};
+      return gram_score_trie(m, ids, mask, B, N, L, c.comp ? &comp : nullptr, &trie, &rows, g_ws, g_ws_bytes, (float*)io[3], (float*)io[4], st);
+    }
   }
   return GRAM_E_ARG;
 }

@@ -50,6 +50,9 @@ void put(const gram_beam_state_t* s) {
 }
 void put(const gram_trie_t* t) { fields(t->child_off, t->child_tok, t->child_node, t->n_nodes, t->n_edges, t->max_fanout, t->min_seq_len); }
 void put(const gram_user_items_t* u) { fields(u->leaf_lo, u->leaf_hi, u->ranks, u->count, u->stride, u->mode); }
+void put(const gram_trie_rows_t* r) {
+  fields(r->tokens, r->pos, r->anc, r->row_node, r->node_row, r->node_tok, r->node_leaf, r->Q, r->Tq, r->n_nodes, r->n_leaves);
+}
 void put(const gram_live_rows_t* l) { fields(l->rows, l->rowpos, l->users, l->tokens, l->counts); }
 template <class... A>
 int rec(const char* name, A... a) {
@@ -123,6 +126,15 @@ int gram_cross_attn_rows_split(const void* q, const void* k, const void* vt, con
 int gram_label_logprob_split(const void* hidden, const void* lm16, const float* lm32, int d, const float* lse, const int32_t* labels, int n_seq,
                              int T, int V, int pieces, float* token_logp, float* seq_logp, void* st) {
   REC(hidden, lm16, lm32, d, lse, labels, n_seq, T, V, pieces, token_logp, seq_logp, st);
+}
+int gram_dec_self_attn_tree_split(const void* qkv, const int32_t* pos, const int32_t* anc, const float* bias, void* out, int B, int Q, int Tq,
+                                  int H, int pieces, int64_t qkv_ps, void* st) {
+  REC(qkv, pos, anc, bias, out, B, Q, Tq, H, pieces, qkv_ps, st);
+}
+int gram_trie_repeat_tokens(const int32_t* tokens, int32_t* out, int B, int Q, void* st) { REC(tokens, out, B, Q, st); }
+int gram_trie_leaf_logprob_split(const void* hidden, const void* lm16, const float* lm32, int d, const float* lse, const gram_trie_rows_t* rows,
+                                 int B, int V, int pieces, float* row_edge, float* leaf_logp, float* node_logp, void* st) {
+  REC(hidden, lm16, lm32, d, lse, rows, B, V, pieces, row_edge, leaf_logp, node_logp, st);
 }
 int gram_cross_attn_probs_split(const void* q, const void* k, const uint8_t* mask, float* probs, int B, int Q, int H, int S, int pieces,
                                 int64_t q_ps, int64_t bank_ps, const uint32_t* key_bits, void* st) {
