@@ -24,6 +24,9 @@ struct gram_model {
   float s_wkv = 1.f, s_lm = 1.f;
   // layer 0's q|k|v per token (gram_model_build_token_tables), [pieces][vocab][3 * inner] each; null: none, layer 0 runs its QKV GEMM
   const p16 *enc_qkv0 = nullptr, *dec_qkv0 = nullptr;
+  // longest passage the whole-path entry points take (gram_model_set_max_passage_len); above GRAM_MAX_PASSAGE_LEN the encoder's
+  // self-attention is the long kernel at every L
+  int max_L = GRAM_MAX_PASSAGE_LEN;
 };
 
 namespace {
@@ -160,7 +163,7 @@ Workspace carve(const gram_model* m, void* ws, int B, int N, int L, int K, int T
 }
 
 int check_shapes(const gram_model* m, int B, int N, int L, int K, int Tmax) {
-  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > GRAM_MAX_PASSAGE_LEN || (L & 31) || K < 1 ||
+  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > m->max_L || (L & 31) || N * L > 4096 || K < 1 ||
       K > GRAM_MAX_BEAMS || Tmax < 2 || Tmax > GRAM_MAX_DEC_LEN)
     return GRAM_E_ARG;
   return 0;
@@ -330,6 +333,13 @@ int encoder_layers(const gram_model* m, const Workspace& w, const int64_t* ids, 
     TRY(sublayer(nc, {GRAM_STAGE_ENC_ATTN, m->enc_ln1[i], m->enc_wqkv[i], m->s_enc_wqkv[i], r.qkv, C_PLANAR, r.ps_qkv, 3 * inner,
                       GRAM_EPI_BF16, r.attn, inner, m->enc_wo[i], m->s_enc_wo[i], tab != nullptr},
                  i == 0, [&] {  // (unfolded: stride 0, as for the GEMM in front)
+                   if (m->max_L > GRAM_MAX_PASSAGE_LEN) {  // a long-mode handle: the tiled kernel at every L
+                     if (tab)
+                       return gram_enc_self_attn_long_rows_split(tab, ids, c.enc_bias_f32, mask, r.attn, P, L, c.n_heads, w.pieces,
+                                                                 (int64_t)c.vocab * 3 * inner, st);
+                     return gram_enc_self_attn_long_split(r.qkv, c.enc_bias_f32, mask, r.attn, P, L, c.n_heads, w.pieces,
+                                                          c.fold_norm ? r.ps_qkv : 0, st);
+                   }
                    if (tab)
                      return gram_enc_self_attn_rows_split(tab, ids, c.enc_bias_f32, mask, r.attn, P, L, c.n_heads, w.pieces,
                                                           (int64_t)c.vocab * 3 * inner, st);
@@ -559,6 +569,12 @@ extern "C" gram_model_t* gram_model_create(const gram_model_desc_t* d) {
     m->d.w_scales = nullptr;  // (consumed)
   }
   return m;
+}
+
+extern "C" int gram_model_set_max_passage_len(gram_model_t* m, int Lmax) {
+  if (!m || Lmax < GRAM_MAX_PASSAGE_LEN || Lmax > GRAM_MAX_LONG_PASSAGE_LEN || (Lmax & 31)) return GRAM_E_ARG;
+  m->max_L = Lmax;
+  return 0;
 }
 
 extern "C" void gram_model_destroy(gram_model_t* m) {
@@ -802,7 +818,7 @@ extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_i
 namespace {
 
 int check_shapes_tf(const gram_model* m, int B, int N, int L, int C, int T) {
-  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > GRAM_MAX_PASSAGE_LEN || (L & 31) || N * L > 4096 || C < 1 ||
+  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > m->max_L || (L & 31) || N * L > 4096 || C < 1 ||
       T < 1 || T > GRAM_MAX_DEC_LEN || (int64_t)B * C * T > INT32_MAX / 4)
     return GRAM_E_ARG;
   return 0;

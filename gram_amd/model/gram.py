@@ -258,6 +258,43 @@ class GRAM(nn.Module):
             self._stage_caps = caps
             self._invalidate()
 
+    _max_passage_len = _lib.GRAM_MAX_PASSAGE_LEN  # (class default: a model starts at the short kernel's limit)
+
+    def set_max_passage_len(self, n: int) -> None:
+        """Longest (padded) passage the model takes: a multiple of 32 in [128, 512], default 128 (``--item_prompt_max_len`` of the
+        reference, arguments.py:293-298).  Above 128 the encoder's self-attention is the tiled kernel for long passages at EVERY
+        length (gram_model_set_max_passage_len), so a passage's bits never depend on the batch it was padded with; at 128 the model
+        launches what it always launched.  N * L <= 4096 holds in every mode.  The passage cache is cleared and its rows become
+        ``n`` long.  The kernel indexes the encoder's relative bias by clamp(key - query, -127, 127): a config whose bucket
+        function is not constant beyond +-127 (relative_attention_max_distance > 128) is refused for n > 128."""
+        n = int(n)
+        if n % 32 or not _lib.GRAM_MAX_PASSAGE_LEN <= n <= _lib.GRAM_MAX_LONG_PASSAGE_LEN:
+            raise ValueError(f"set_max_passage_len: a multiple of 32 in [{_lib.GRAM_MAX_PASSAGE_LEN}, {_lib.GRAM_MAX_LONG_PASSAGE_LEN}] "
+                             f"is supported (got {n})")
+        if n > _lib.GRAM_MAX_PASSAGE_LEN:
+            c = self.config
+            # (the bucket is monotone in the distance: equal at 127 and at n - 1 means constant in between)
+            ends = torch.tensor([-(n - 1), -127, 127, n - 1])
+            b = relative_position_bucket(ends, True, c.relative_attention_num_buckets, c.relative_attention_max_distance)
+            if int(b[0]) != int(b[1]) or int(b[2]) != int(b[3]):
+                raise ValueError(f"set_max_passage_len({n}): the relative-position buckets of this config (num_buckets="
+                                 f"{c.relative_attention_num_buckets}, max_distance={c.relative_attention_max_distance}) are not constant "
+                                 f"beyond distance +-127, which passages longer than {_lib.GRAM_MAX_PASSAGE_LEN} tokens need")
+        self._max_passage_len = n
+        self._CACHE_L = n
+        self._pcache = None  # (rows of another length)
+        if self._packed is not None and self._packed[1] == self._version:
+            _lib.check(_lib.load().gram_model_set_max_passage_len(self._packed[2], n), "gram_model_set_max_passage_len")
+
+    def _check_passage_len(self, L: int) -> int:
+        """The padded passage length of a call, or a ValueError that names the way out."""
+        Lp = (int(L) + 31) // 32 * 32
+        if Lp > self._max_passage_len:
+            hint = (f"call set_max_passage_len({min(Lp, _lib.GRAM_MAX_LONG_PASSAGE_LEN)}) first" if Lp <= _lib.GRAM_MAX_LONG_PASSAGE_LEN
+                    else f"set_max_passage_len goes up to {_lib.GRAM_MAX_LONG_PASSAGE_LEN}")
+            raise ValueError(f"passages of {L} tokens (padded to {Lp}) exceed this model's limit of {self._max_passage_len}: {hint}")
+        return Lp
+
     def _invalidate(self) -> None:
         self._version += 1
         self._pcache = None  # cached encoder states belong to the old weights
@@ -443,6 +480,7 @@ class GRAM(nn.Module):
         dec, lab, compaction fields)`` per chunk -> (the list of its results, the padded passage length).  ``extra_bytes(Lp)``: further
         output bytes per user.  ``trie_rows=(Q, n_out)``: the one-pass scoring of a Trie instead -- Q decoder rows and n_out fp32
         outputs per user, the workspace of gram_workspace_bytes_trie, no dec / lab (``call`` gets None for both)."""
+        self._check_passage_len(input_ids.shape[-1])
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()
@@ -477,7 +515,7 @@ class GRAM(nn.Module):
             comp, _harvest = self._plan(cid, cmask, nb, N, Lp)
             need = ws_bytes(nb)
             if need < 0:
-                raise _lib.GramHipError(f"unsupported problem size B={nb} N={N} L={Lp} {size} (N <= max_item_num+1, L <= 128, "
+                raise _lib.GramHipError(f"unsupported problem size B={nb} N={N} L={Lp} {size} (N <= max_item_num+1, L <= {self._max_passage_len}, "
                                         f"N*L <= 4096, T <= {_lib.GRAM_MAX_DEC_LEN})")
             ws = self._ensure_workspace(need)
             ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
@@ -730,6 +768,8 @@ class GRAM(nn.Module):
         if not handle:
             raise _lib.GramHipError("gram_model_create rejected the configuration (dims must be multiples of 128, heads <= 16)")
         self._packed = (dev, self._version, handle, keep)
+        if self._max_passage_len != _lib.GRAM_MAX_PASSAGE_LEN:
+            _lib.check(lib.gram_model_set_max_passage_len(handle, self._max_passage_len), "gram_model_set_max_passage_len")
         self._build_token_tables(handle, keep)
         return handle
 
@@ -757,7 +797,7 @@ class GRAM(nn.Module):
         if need < 0:
             raise _lib.GramHipError(
                 f"unsupported problem size B={B} N={N} L={L} K={K} max_length={max_length} "
-                f"(N <= max_item_num+1, L <= 128, K <= 64, max_length <= {_lib.GRAM_MAX_DEC_LEN}; "
+                f"(N <= max_item_num+1, L <= {self._max_passage_len}, N*L <= 4096, K <= 64, max_length <= {_lib.GRAM_MAX_DEC_LEN}; "
                 f"the Trie's fan-out is not limited)"
             )
         return self._ensure_workspace(need)
@@ -819,27 +859,33 @@ class GRAM(nn.Module):
         return cached[1]
 
     # ------------------------------------------------------------------ which passages the encoder runs on
-    _CACHE_L = _lib.GRAM_MAX_PASSAGE_LEN
-    _KEY_MULT: Dict[torch.device, torch.Tensor] = {}
+    _CACHE_L = _lib.GRAM_MAX_PASSAGE_LEN  # row length of the passage cache: the model's set_max_passage_len
+    _KEY_MULT: Dict[tuple, torch.Tensor] = {}  # (device, width) -> multipliers
 
     @staticmethod
-    def _canonical(rows_ids: torch.Tensor, rows_mask: torch.Tensor) -> torch.Tensor:
-        """(P, 128) int32: token id where valid, -1 elsewhere -- the identity of a passage (position-wise)."""
+    def _canonical(rows_ids: torch.Tensor, rows_mask: torch.Tensor, width: int = _lib.GRAM_MAX_PASSAGE_LEN) -> torch.Tensor:
+        """(P, width) int32: token id where valid, -1 elsewhere -- the identity of a passage (position-wise).  ``width`` is the
+        cache's row length and never below the rows' own (a negative pad would cut tokens off: two passages that differ only
+        behind the cut would then share an identity)."""
         canon = torch.where(rows_mask.bool(), rows_ids, rows_ids.new_full((), -1)).to(torch.int32)
-        return torch.nn.functional.pad(canon, (0, GRAM._CACHE_L - canon.shape[1]), value=-1)
+        if canon.shape[1] > width:
+            raise ValueError(f"passages of {canon.shape[1]} tokens do not fit the passage cache's rows of {width}")
+        return torch.nn.functional.pad(canon, (0, width - canon.shape[1]), value=-1)
 
     @staticmethod
     def _passage_keys(canon: torch.Tensor) -> torch.Tensor:
-        # 64-bit key, overflow-free ((id+1) < 2^15, multiplier < 2^31, 128 terms); a key match is always
-        # confirmed against the stored tokens, so a collision costs a miss, never a wrong hit
-        mult = GRAM._KEY_MULT.get(canon.device)
+        # 64-bit key over the row's own width, overflow-free ((id+1) < 2^15, multiplier < 2^31, at most 512 = 2^9 terms: the sum
+        # stays below 2^55 < 2^63); a key match is always confirmed against the stored tokens, so a collision costs a miss, never a
+        # wrong hit
+        width = int(canon.shape[1])
+        mult = GRAM._KEY_MULT.get((canon.device, width))
         if mult is None:
             g = torch.Generator().manual_seed(0x6772616D)
-            mult = torch.randint(1, 2 ** 31 - 1, (GRAM._CACHE_L,), generator=g, dtype=torch.int64).to(canon.device)
-            GRAM._KEY_MULT[canon.device] = mult
+            mult = torch.randint(1, 2 ** 31 - 1, (width,), generator=g, dtype=torch.int64).to(canon.device)
+            GRAM._KEY_MULT[(canon.device, width)] = mult
         return ((canon.to(torch.int64) + 1) * mult).sum(dim=1)
 
-    # The passage cache: x f32 [capacity][128][d] (the encoder's residual stream before the final norm), canon i32 [capacity][128]
+    # The passage cache: x f32 [capacity][_CACHE_L][d] (the encoder's residual stream before the final norm), canon i32 [capacity][_CACHE_L]
     # (the tokens: the identity of a passage), n rows in use, keys (sorted) / perm over the rows in use.
     def _pcache_rows(self, n_new: int):
         """Make room for n_new more passages; returns (cache dict, first new row).  The buffers grow geometrically (a dataset's item
@@ -887,7 +933,7 @@ class GRAM(nn.Module):
         for every user and every slot.  Passages registered here (``(P, L)`` or ``(B, N, L)`` ids + mask, e.g. all
         item prompts of the dataset) are encoded once; ``generate`` then recognises them by their tokens and runs the
         encoder only on the rest.  Results are bit-identical with and without the cache.  The cache holds the fp32
-        residual stream (128 x d_model x 4 B per passage) on the device and is dropped whenever the weights change.
+        residual stream (max passage length x d_model x 4 B per passage) on the device and is dropped whenever the weights change.
         Returns the number of passages cached so far."""
         handle = self._pack()
         lib = _lib.load()
@@ -897,7 +943,7 @@ class GRAM(nn.Module):
         if ids.shape != mask.shape or ids.shape[1] > self._CACHE_L:
             raise ValueError(f"passages must be (P, L <= {self._CACHE_L}) ids with a mask of the same shape")
         keep = mask.any(dim=1)
-        canon = self._canonical(ids[keep], mask[keep])
+        canon = self._canonical(ids[keep], mask[keep], self._CACHE_L)
         canon = canon[self._first_unseen(canon)]
         n_new = int(canon.shape[0])
         if n_new == 0:
@@ -954,7 +1000,7 @@ class GRAM(nn.Module):
             return None, None
         rows_ids, rows_mask = ids.view(B * N, Lp), mask.view(B * N, Lp)
         active = rows_mask.ne(0).any(dim=1)
-        canon = self._canonical(rows_ids, rows_mask) if (have or harvest) else None
+        canon = self._canonical(rows_ids, rows_mask, self._CACHE_L) if (have or harvest) else None
         if have:
             hit, slot = self._lookup(canon, self._passage_keys(canon))
             hit &= active
@@ -1044,6 +1090,7 @@ class GRAM(nn.Module):
                 warnings.warn(f"gram_amd.GRAM.generate ignores the keyword argument {k!r}")
         if input_ids.dim() != 3:
             raise ValueError("input_ids must be (B, N, L)")
+        self._check_passage_len(input_ids.shape[-1])
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()

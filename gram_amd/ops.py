@@ -16,6 +16,7 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
                                      ``GRAM.score_all_items``
     torch.ops.gram.linear            nn.Linear without bias: A @ W^T on the 16-bit MFMA (gram_gemm_bf16, 16-bit epilogue)
     torch.ops.gram.enc_self_attn     T5Attention self branch on (P*L, 3*inner) q|k|v rows (gram_enc_self_attn)
+    torch.ops.gram.enc_self_attn_long  the same for passages of up to 512 tokens (gram_enc_self_attn_long_split)
     torch.ops.gram.cross_attn_decode the fusion read of one decoder layer and step over the beam-shared bank
     torch.ops.gram.trie_step         one Trie-constrained beam-search step on dense logits (gram_row_lse + gram_beam_step)
 """
@@ -397,6 +398,33 @@ def _(qkv, bias, mask, num_heads):
     return qkv.new_empty(qkv.shape[0], num_heads * 64)
 
 
+@torch.library.custom_op("gram::enc_self_attn_long", mutates_args=(), device_types="cuda")
+def enc_self_attn_long(qkv: Tensor, bias: Tensor, mask: Tensor, num_heads: int) -> Tensor:
+    """``enc_self_attn`` for passages of up to 512 tokens (gram_enc_self_attn_long_split, one piece): the same operands; the bias
+    index is clamp(key - query, -127, 127) + 127, so the (H, 255) table must be constant beyond +-127."""
+    dt = _lib.piece_dtype()
+    if mask.dim() != 2:
+        raise ValueError("enc_self_attn_long: mask must be (P, L)")
+    P, L = mask.shape
+    inner = num_heads * 64
+    _check("qkv", qkv, dt, (P * L, 3 * inner))
+    _check("bias", bias, torch.float32, (num_heads, 255), qkv.device)
+    _check("mask", mask, torch.uint8, None, qkv.device)
+    if L < 32 or L > _lib.GRAM_MAX_LONG_PASSAGE_LEN or L % 32 or num_heads < 1:
+        raise ValueError(f"enc_self_attn_long: L must be a multiple of 32 in [32, {_lib.GRAM_MAX_LONG_PASSAGE_LEN}] (got {L})")
+    out = torch.empty(P * L, inner, dtype=dt, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        rc = _lib.load().gram_enc_self_attn_long_split(qkv.data_ptr(), bias.data_ptr(), mask.data_ptr(), out.data_ptr(), P, L, num_heads,
+                                                       1, 0, _stream(qkv))
+    _lib.check(rc, "gram_enc_self_attn_long_split")
+    return out
+
+
+@enc_self_attn_long.register_fake
+def _(qkv, bias, mask, num_heads):
+    return qkv.new_empty(qkv.shape[0], num_heads * 64)
+
+
 # ---------------------------------------------------------------------------------------------- cross-attention decode
 @torch.library.custom_op("gram::cross_attn_decode", mutates_args=(), device_types="cuda")
 def cross_attn_decode(q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor, num_beams: int) -> Tensor:
@@ -475,4 +503,4 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
-__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "score_trie", "linear", "enc_self_attn", "cross_attn_decode", "trie_step"]
+__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "score_trie", "linear", "enc_self_attn", "enc_self_attn_long", "cross_attn_decode", "trie_step"]

@@ -312,6 +312,12 @@ class BaseRunner:
             phases[name] = phases.get(name, 0.0) + now - t_phase
             t_phase = now
 
+        # --item_prompt_max_len above 128 (arguments.py:293-298): the model takes passages of up to 512 tokens once told so
+        prompt_len = int(getattr(getattr(testloader, "collate_fn", None), "item_prompt_max_len", 0) or _arg(self.args, "item_prompt_max_len", 128))
+        prompt_len = (prompt_len + 31) // 32 * 32
+        gen_model = self._generate_model()
+        if prompt_len > 128 and hasattr(gen_model, "set_max_passage_len") and getattr(gen_model, "_max_passage_len", 128) != prompt_len:
+            gen_model.set_max_passage_len(prompt_len)
         self._warm_passage_cache(testloader)
         lap("passage_cache")
         candidates = testloader.dataset.all_items

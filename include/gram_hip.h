@@ -39,7 +39,8 @@ extern "C" {
 #define GRAM_MAX_BEAMS 64      /* K <= 64 (reference default 50, headline 20)             */
 #define GRAM_MAX_DEC_LEN 64    /* max_length <= 64 (reference: the longest candidate, 8..12, for the "split" / "t5_token" id
                                   types, 50 for "term": single_runner_gram.py:629-637); also the row stride of dec_bias_f32 */
-#define GRAM_MAX_PASSAGE_LEN 128 /* L <= 128 (arguments.py:293-298), L % 32 == 0          */
+#define GRAM_MAX_PASSAGE_LEN 128 /* L <= 128 on a default handle (arguments.py:293-298), L % 32 == 0 */
+#define GRAM_MAX_LONG_PASSAGE_LEN 512 /* L <= 512 on a handle raised by gram_model_set_max_passage_len; N * L <= 4096 always */
 
 /* ---- GEMM epilogues ------------------------------------------------------------------ */
 enum gram_epilogue {
@@ -171,6 +172,21 @@ int gram_enc_self_attn_split(const void* qkv, const float* bias, const uint8_t* 
  * between the table's pieces.  Same bits as gram_enc_self_attn_split on the gathered rows. */
 int gram_enc_self_attn_rows_split(const void* qkv_table, const int64_t* ids, const float* bias, const uint8_t* mask, void* out,
                                   int P, int L, int H, int pieces, int64_t qkv_pstride, void* stream);
+/* Encoder self-attention for passages of up to GRAM_MAX_LONG_PASSAGE_LEN tokens: gram_enc_self_attn_split's operands and conventions
+ * (planar q|k|v pieces, output interleaved at two pieces, unscaled scores, u8 key mask with finfo.min, fp32 softmax) for any
+ * L = 32 n, 32 <= L <= 512.  One workgroup per (head, passage, block of 128 queries) walks the keys in tiles of 128 with an online
+ * softmax.  The bias table stays [H][255]: the index is clamp(key - query, -127, 127) + 127, which is T5's bucket function wherever
+ * relative_attention_max_distance <= 128 (the caller checks).  A key tile without a valid key is not fetched when the passage has a
+ * valid key; a passage without one gets the uniform row over its L keys.  A row's bits depend on the row's passage alone -- its
+ * tokens and valid keys -- not on L, P or the passage's place in the batch; they are NOT those of gram_enc_self_attn_split at
+ * L <= 128 (another summation order).  A null pointer, a misaligned qkv / out or a piece stride shorter than the rows:
+ * GRAM_E_ARG before any launch. */
+int gram_enc_self_attn_long_split(const void* qkv, const float* bias, const uint8_t* mask, void* out, int P, int L, int H,
+                                  int pieces, int64_t qkv_pstride, void* stream);
+/* ... with the q|k|v rows taken from a per-token table (gram_enc_self_attn_rows_split's contract).  Same bits as
+ * gram_enc_self_attn_long_split on the gathered rows. */
+int gram_enc_self_attn_long_rows_split(const void* qkv_table, const int64_t* ids, const float* bias, const uint8_t* mask, void* out,
+                                       int P, int L, int H, int pieces, int64_t qkv_pstride, void* stream);
 /* users/rowpos NULL: all B users, rows b*K + beam; else the live-row form (gram_cross_attn_decode_live, B = n_users).
  * key_bits: gram_mask_key_bits(mask) computed once per generate (the mask is the same for every head, layer and step), or
  * NULL: every workgroup packs its user's bits from the mask bytes itself. */
@@ -455,6 +471,14 @@ typedef struct gram_model gram_model_t;
  * and fold_norm (tests/test_model_shapes_host.py). */
 gram_model_t* gram_model_create(const gram_model_desc_t* desc_host);
 void gram_model_destroy(gram_model_t* m);
+
+/* Longest passage the handle's whole-path entry points take (default GRAM_MAX_PASSAGE_LEN).  Lmax must be a multiple of 32 in
+ * [GRAM_MAX_PASSAGE_LEN, GRAM_MAX_LONG_PASSAGE_LEN] (GRAM_E_ARG otherwise).  A handle with Lmax > 128 runs the long encoder
+ * self-attention (gram_enc_self_attn_long[_rows]_split) at EVERY L, so that a passage's bits never depend on the padded length of
+ * the batch it landed in; a handle at 128 launches exactly what it always launched.  Every whole-path entry point and workspace
+ * query returns GRAM_E_ARG for L > Lmax or N * L > 4096 before any launch.  The caller guarantees that the encoder's bias is
+ * constant beyond distance +-127 (relative_attention_max_distance <= 128) before raising the limit. */
+int gram_model_set_max_passage_len(gram_model_t* m, int Lmax);
 
 /* Layer-0 q|k|v per TOKEN.  T5 has no absolute positions: the first sublayer of each stack norms the raw embedding row of a token
  * (row-local) and multiplies it by layer 0's W_qkv, so its q|k|v row depends on the token id and the weights only.  The two tables

@@ -33,6 +33,7 @@ struct Case {
   bool tables;                // the handle has token tables: the trace starts with their build (workspace offsets: the build's scratch)
   int attn;                   // gram_teacher_forced_ex: 1 = every layer's probabilities, 2 = one layer of scratch + token and passage scores
   bool items;                 // gram_generate_items: per-user item filters (gram_user_items_t)
+  int max_L;                  // != 0: gram_model_set_max_passage_len first (a long-mode handle: the tiled encoder attention at every L)
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -77,6 +78,11 @@ const Case kCases[] = {
     // the tree self-attention in every layer and the Trie reduction in place of the label log-probs
     {"score_trie_folded", SCORE_TRIE, 1, 1, 2, 3, 32, 3, 4},
     {"score_trie_p2", SCORE_TRIE, 2, 1, 2, 3, 32, 3, 4},
+    // long-mode handles (gram_model_set_max_passage_len(256)): the trains of generate_p1_folded / generate_p2_tables with the long
+    // encoder attention in place of the short one, at L = 32 and at a length a default handle refuses
+    {"generate_long_32", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 256},
+    {"generate_long_160", GENERATE, 1, 1, 2, 3, 160, 4, 4, SOME, false, false, false, false, 0, false, 256},
+    {"generate_p2_tables_long_160", GENERATE, 2, 1, 2, 3, 160, 4, 4, SOME, false, false, false, true, 0, false, 256},
 };
 
 gram_model_t* make_model(int pieces, int fold) {
@@ -105,6 +111,7 @@ gram_model_t* make_model(int pieces, int fold) {
 int run(const Case& c) {
   gram_model_t* m = make_model(c.pieces, c.fold);
   if (!m) return GRAM_E_ARG;
+  if (c.max_L) trace_line("gram_model_set_max_passage_len", gram_model_set_max_passage_len(m, c.max_L));
   void* st = fake();
   const int64_t* ids = fake<int64_t>();
   const uint8_t* mask = fake<uint8_t>();

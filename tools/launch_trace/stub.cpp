@@ -97,6 +97,14 @@ int gram_enc_self_attn_rows_split(const void* table, const int64_t* ids, const f
                                   int pieces, int64_t ps, void* st) {
   REC(table, ids, bias, mask, out, P, L, H, pieces, ps, st);
 }
+int gram_enc_self_attn_long_split(const void* qkv, const float* bias, const uint8_t* mask, void* out, int P, int L, int H, int pieces,
+                                  int64_t ps, void* st) {
+  REC(qkv, bias, mask, out, P, L, H, pieces, ps, st);
+}
+int gram_enc_self_attn_long_rows_split(const void* table, const int64_t* ids, const float* bias, const uint8_t* mask, void* out, int P, int L,
+                                       int H, int pieces, int64_t ps, void* st) {
+  REC(table, ids, bias, mask, out, P, L, H, pieces, ps, st);
+}
 int gram_iota_i32(int32_t* out, int n, void* st) { REC(out, n, st); }
 int gram_gather_passage_x(const float* cache_x, const int32_t* slot, float* x, int n, int L, int cache_L, int d, void* st) {
   REC(cache_x, slot, x, n, L, cache_L, d, st);
