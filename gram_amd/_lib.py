@@ -16,6 +16,9 @@ GRAM_MAX_BEAMS = 64
 GRAM_MAX_DEC_LEN = 64
 GRAM_MAX_PASSAGE_LEN = 128
 GRAM_MAX_LONG_PASSAGE_LEN = 512  # on a handle raised by gram_model_set_max_passage_len (GRAM.set_max_passage_len)
+GRAM_MAX_FUSED_LEN = 4096        # fused tokens N * L
+GRAM_MAX_LONG_FUSED_LEN = 16384  # on a handle raised by gram_model_set_max_fused_len (GRAM.set_max_fused_tokens)
+GRAM_KEY_BITS_LONG_WORDS, GRAM_KEY_BITS_LONG_STRIDE = 512, 528  # a row of gram_mask_key_bits_long: step words | valid steps | zeros
 EPI_BF16, EPI_BF16_RELU, EPI_F32_ADD, EPI_F32, EPI_KV_BANK = range(5)
 K_GEMM, K_ENC_ATTN, K_CROSS_ATTN, K_DEC_SELF_ATTN, K_ROWOPS, K_LSE, K_BEAM = range(7)
 E_ARG, E_WORKSPACE, E_BEAM, E_NONFINITE = -1, -2, -3, -4
@@ -199,6 +202,12 @@ SIGNATURES = {
     "gram_enc_self_attn_long_rows_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp]),
     "gram_model_set_max_passage_len": (C.c_int, [vp, C.c_int]),
     "gram_mask_key_bits": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    # fused contexts of up to GRAM_MAX_LONG_FUSED_LEN tokens
+    "gram_model_set_max_fused_len": (C.c_int, [vp, C.c_int]),
+    "gram_mask_key_bits_long": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    "gram_cross_attn_long_scratch_bytes": (i64, [C.c_int, C.c_int, C.c_int]),
+    "gram_cross_attn_long_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, i64, i64, vp, vp, vp]),
+    "gram_cross_attn_rows_long_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, vp, vp, vp, vp]),
     "gram_dec_self_attn_split": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, vp]),
     "gram_dec_self_attn_rows_split": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64,
                                                 vp]),

@@ -154,6 +154,10 @@ __device__ __forceinline__ float row_xscale(float sum, float minblk) {
   return __uint_as_float((uint32_t)(e + 127) << 23);
 }
 
+// tf_attn.hip: fills rowmap i32 [B * (1 + 2 * GRAM_MAX_BEAMS)] -- users[b] = b | full[b * 64 + i] = b * Q + i | tail[b * kt + i] = b * Q + i,
+// kt = Q % GRAM_MAX_BEAMS -- the live-row tables of a cross-attention over Q > GRAM_MAX_BEAMS rows per user, one group of rows per call
+int gram_tf_rowmap(int32_t* rowmap, int B, int Q, void* stream);
+
 // products of the two-piece mode (gram_hip.h, gram_split_t): (A piece, B piece) pairs, smallest first
 template <int S> struct SplitTab;
 template <> struct SplitTab<1> { static constexpr int NP = 1; static constexpr int A[3] = {0, 0, 0}; static constexpr int B[3] = {0, 0, 0}; };

@@ -1434,8 +1434,9 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const p16* __restrict__
   auto kv_locate = [&](int tm0, int tn0, int J0) {
     KVLoc q;
     q.mblk = tm0 + wr * 128 + J0 * 16;
-    // mblk, pL, S are multiples of 32: (mblk/32) / (x/32), dividend < 2^25 and divisor <= 128 -> multiply-high is exact
-    // (error term < divisor, dividend * error < 2^32); flat < 2^27 with pN <= 22 likewise; n-tiles < 2^16 by inner/256
+    // mblk, pL, S are multiples of 32: (mblk/32) / (x/32) by multiply-high with floor(2^32 / d) + 1, exact while dividend * e < 2^32,
+    // e = d - (2^32 mod d) <= d: divisor S/32 <= 512 and pL/32 <= 128 with the dividend bounded by the host guard (launch_pp:
+    // (M/32) * (S/32) < 2^32, M < 2^30); flat < 2^26 with pN <= 64 likewise; n-tiles < 2^16 by inner/256
     int b_, s0;
     if (ep.pmap) {
       const int pp = (int)udiv_magic((uint32_t)q.mblk >> 5, (uint32_t)ep.pL >> 5, ep.mg_pL32), l = q.mblk - pp * ep.pL, flat = ep.pmap[pp];
@@ -1886,7 +1887,8 @@ int launch_pp(const void* A, const void* W, int M, int N, int K, int lda, EpiArg
   {
     if constexpr (EPI == PP_KV_K || EPI == PP_KV_V) {  // a tile inside one layer's K or V block, 32-row blocks inside one passage
       if (ep.inner % 256 || ((ep.pmap ? ep.pL : ep.S) % 32) || M % 32) return GRAM_E_ARG;
-      if (ep.S > 4096 || (ep.pmap && (ep.pL > 4096 || ep.pN > 64 || (long)ep.B * ep.pN >= (1l << 26))) || M >= (1 << 30)) return GRAM_E_ARG;
+      // (kv_locate's multiply-high divisions: x / d is exact while x * d < 2^32 -- identity path x = M / 32, d = S / 32 <= 512)
+      if (ep.S > 16384 || (uint64_t)(M >> 5) * (uint64_t)(ep.S >> 5) >= (1ull << 32) || (ep.pmap && (ep.pL > 4096 || ep.pN > 64 || (long)ep.B * ep.pN >= (1l << 26))) || M >= (1 << 30)) return GRAM_E_ARG;
       ep.mg_pL32 = magic_u32(ep.pmap ? ep.pL >> 5 : 1);
       ep.mg_S32 = magic_u32(ep.S >> 5);
       ep.mg_pN = magic_u32(ep.pmap ? ep.pN : 1);

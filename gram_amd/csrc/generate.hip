@@ -27,6 +27,10 @@ struct gram_model {
   // longest passage the whole-path entry points take (gram_model_set_max_passage_len); above GRAM_MAX_PASSAGE_LEN the encoder's
   // self-attention is the long kernel at every L
   int max_L = GRAM_MAX_PASSAGE_LEN;
+  // longest fused context N * L they take (gram_model_set_max_fused_len); above GRAM_MAX_FUSED_LEN the cross-attention is the long
+  // form (xattn_long.hip) at every S
+  int max_S = GRAM_MAX_FUSED_LEN;
+  bool long_xattn() const { return max_S > GRAM_MAX_FUSED_LEN; }
 };
 
 namespace {
@@ -82,6 +86,8 @@ struct Workspace {
   gram_live_rows_t live;
   int32_t* width;
   uint32_t* key_bits;  // [B][128]  the cross-attention's bit view of the mask (gram_mask_key_bits), once per generate
+                       // (a handle with a raised fused limit: [B][GRAM_KEY_BITS_LONG_STRIDE], gram_mask_key_bits_long)
+  float* xa_scratch;   // such a handle only: the long cross-attention's partials (gram_cross_attn_long_scratch_bytes)
   int32_t* rowmap;     // teacher-forced pass only: gram_cross_attn_rows_split's row tables [B * (1 + 2 * GRAM_MAX_BEAMS)]
   int64_t bytes;
   // two-piece mode (gram_split_t): what a GEMM reads (h, attn, u) is ONE interleaved buffer of twice the row length;
@@ -106,6 +112,16 @@ Rows take_rows(Carve& cv, const gram_model_desc_t& c, int64_t P, int64_t rows, b
   r.xs[0] = cv.take<float>(rows);
   r.xs[1] = cv.take<float>(rows);
   return r;
+}
+// the key bits of B users, and on a handle with a raised fused limit the long cross-attention's scratch for `rows` (user, row) slots
+void take_key_bits(Carve& cv, Workspace& w, const gram_model* m, int64_t B, int64_t rows, int S) {
+  if (!m->long_xattn()) {
+    w.key_bits = cv.take<uint32_t>(B * 128);
+    return;
+  }
+  w.key_bits = cv.take<uint32_t>(B * GRAM_KEY_BITS_LONG_STRIDE);
+  const int64_t n = gram_cross_attn_long_scratch_bytes((int)rows, m->d.n_heads, S) / (int64_t)sizeof(float);
+  w.xa_scratch = n > 0 ? cv.take<float>(n) : nullptr;  // (S <= 4096: one segment, nothing to merge)
 }
 void take_bank(Carve& cv, Workspace& w, const gram_model_desc_t& c, int64_t B, int64_t S) {
   w.ps_bank = c.n_dec_layers * B * c.n_heads * S * 64;
@@ -157,13 +173,13 @@ Workspace carve(const gram_model* m, void* ws, int B, int N, int L, int K, int T
   w.live.tokens = cv.take<int32_t>(R);
   w.live.counts = cv.take<int32_t>(4);
   w.width = cv.take<int32_t>(4);
-  w.key_bits = cv.take<uint32_t>((int64_t)B * 128);
+  take_key_bits(cv, w, m, B, R, N * L);
   w.bytes = (cv.off + 255) & ~(int64_t)255;
   return w;
 }
 
 int check_shapes(const gram_model* m, int B, int N, int L, int K, int Tmax) {
-  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > m->max_L || (L & 31) || N * L > 4096 || K < 1 ||
+  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > m->max_L || (L & 31) || N * L > m->max_S || K < 1 ||
       K > GRAM_MAX_BEAMS || Tmax < 2 || Tmax > GRAM_MAX_DEC_LEN)
     return GRAM_E_ARG;
   return 0;
@@ -367,7 +383,8 @@ int encode(const gram_model* m, const Workspace& w, const int64_t* ids, const ui
   const gram_model_desc_t& c = m->d;
   const int d = c.d_model, inner = c.n_heads * 64, H = c.n_heads;
   const int Pe = P - cached.n, Me = P * L;
-  TRY(gram_mask_key_bits(full_mask, w.key_bits, B, N * L, st));
+  if (m->long_xattn()) TRY(gram_mask_key_bits_long(full_mask, w.key_bits, B, N * L, st));
+  else TRY(gram_mask_key_bits(full_mask, w.key_bits, B, N * L, st));
   if (Pe > 0) TRY(encoder_layers(m, w, ids, mask, L, Pe, st));
   if (cached.n > 0) TRY(gram_gather_passage_x(cached.x, cached.slot, w.enc.x + (size_t)Pe * L * d, cached.n, L, cached.cache_L, d, st));
   // final norm + per-passage position embedding = the late fusion (gram.py:238-255); the
@@ -465,6 +482,10 @@ int decode_step(const gram_model* m, const Workspace& w, const int32_t* tokens, 
                                         live ? R_cache : R, R, live ? live->rows : nullptr, H, t, Tmax, w.pieces, r.ps_qkv, w.ps_cache, st);
       },
       [&](int i) {
+        if (m->long_xattn())
+          return gram_cross_attn_long_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn,
+                                            live ? live->n_users : B, K, H, S, live ? live->users : nullptr,
+                                            live ? live->rowpos : nullptr, w.pieces, r.ps_qx, w.ps_bank, w.key_bits, w.xa_scratch, st);
         return gram_cross_attn_decode_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn,
                                             live ? live->n_users : B, K, H, S, live ? live->users : nullptr, live ? live->rowpos : nullptr,
                                             w.pieces, r.ps_qx, w.ps_bank, w.key_bits, st);
@@ -574,6 +595,12 @@ extern "C" gram_model_t* gram_model_create(const gram_model_desc_t* d) {
 extern "C" int gram_model_set_max_passage_len(gram_model_t* m, int Lmax) {
   if (!m || Lmax < GRAM_MAX_PASSAGE_LEN || Lmax > GRAM_MAX_LONG_PASSAGE_LEN || (Lmax & 31)) return GRAM_E_ARG;
   m->max_L = Lmax;
+  return 0;
+}
+
+extern "C" int gram_model_set_max_fused_len(gram_model_t* m, int Smax) {
+  if (!m || Smax < GRAM_MAX_FUSED_LEN || Smax > GRAM_MAX_LONG_FUSED_LEN || (Smax & 31)) return GRAM_E_ARG;
+  m->max_S = Smax;
   return 0;
 }
 
@@ -818,7 +845,7 @@ extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_i
 namespace {
 
 int check_shapes_tf(const gram_model* m, int B, int N, int L, int C, int T) {
-  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > m->max_L || (L & 31) || N * L > 4096 || C < 1 ||
+  if (!m || B < 1 || N < 1 || N > m->d.max_passages || L < 32 || L > m->max_L || (L & 31) || N * L > m->max_S || C < 1 ||
       T < 1 || T > GRAM_MAX_DEC_LEN || (int64_t)B * C * T > INT32_MAX / 4)
     return GRAM_E_ARG;
   return 0;
@@ -832,7 +859,7 @@ Workspace carve_tf(const gram_model* m, void* ws, int B, int N, int L, int C, in
   Carve cv(ws);
   Workspace w{};
   const int64_t P = w.pieces = c.pieces > 1 ? c.pieces : 1;
-  w.key_bits = cv.take<uint32_t>((int64_t)B * 128);
+  take_key_bits(cv, w, m, B, (int64_t)B * ((int64_t)C * T < GRAM_MAX_BEAMS ? C * T : GRAM_MAX_BEAMS), N * L);
   w.rowmap = cv.take<int32_t>((int64_t)B * (1 + 2 * GRAM_MAX_BEAMS));
   take_bank(cv, w, c, B, (int64_t)N * L);
   const int64_t shared = cv.off;
@@ -868,11 +895,17 @@ int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, c
         return gram_dec_self_attn_tf_split(r.qkv, c.dec_bias_f32, r.attn, R / T, T, H, w.pieces, r.ps_qkv, st);
       },
       [&](int i) {
-        TRY(gram_cross_attn_rows_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S, w.pieces,
-                                       r.ps_qx, w.ps_bank, w.key_bits, w.rowmap, st));
+        if (m->long_xattn())
+          TRY(gram_cross_attn_rows_long_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S,
+                                              w.pieces, r.ps_qx, w.ps_bank, w.key_bits, w.xa_scratch, w.rowmap, st));
+        else
+          TRY(gram_cross_attn_rows_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S, w.pieces,
+                                         r.ps_qx, w.ps_bank, w.key_bits, w.rowmap, st));
         if (!attn) return 0;
         float* p = attn->probs ? attn->probs + (size_t)i * B * H * Q * S : attn->layer_probs;
-        TRY(gram_cross_attn_probs_split(r.qx, w.bank_k + i * bank_layer, mask, p, B, Q, H, S, w.pieces, r.ps_qx, w.ps_bank, w.key_bits, st));
+        // (the probabilities read the short form's key bits; a handle that carved the long form's lets the kernel pack them from the mask)
+        TRY(gram_cross_attn_probs_split(r.qx, w.bank_k + i * bank_layer, mask, p, B, Q, H, S, w.pieces, r.ps_qx, w.ps_bank,
+                                        m->long_xattn() ? nullptr : w.key_bits, st));
         return attn->token_scores ? gram_xattn_head_sum(p, attn->token_scores, B, Q, H, S, /*first=*/i == 0, st) : 0;
       },
       st));
@@ -906,6 +939,7 @@ extern "C" int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* inpu
   // the attention outputs are the caller's memory: one layer of probabilities at least, and the passage scores are a reduction of the
   // token scores
   if (attn && ((!attn->probs && !attn->layer_probs) || (attn->passage_scores && !attn->token_scores))) return GRAM_E_ARG;
+  if (attn && N * L > GRAM_MAX_FUSED_LEN) return GRAM_E_ARG;  // probabilities stop at 4096 keys (gram_cross_attn_probs_split)
   TRY(check_compaction(comp, B, N));  // (as gram_generate_ex)
   Workspace w = carve_tf(m, workspace, B, N, L, C, T);
   if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;

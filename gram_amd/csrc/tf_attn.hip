@@ -151,6 +151,16 @@ extern "C" int gram_dec_self_attn_tf_split(const void* qkv, const float* bias, v
   return 0;
 }
 
+// the row tables of a grouped cross-attention over Q > GRAM_MAX_BEAMS rows per user (common.h; also xattn_long.hip's)
+int gram_tf_rowmap(int32_t* rowmap, int B, int Q, void* stream) {
+  int32_t* users = rowmap;
+  int32_t* full = users + B;
+  int32_t* tail = full + (size_t)B * GRAM_MAX_BEAMS;
+  hipLaunchKernelGGL(tf_rowmap_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, users, full, tail, Q, Q % GRAM_MAX_BEAMS);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int gram_cross_attn_rows_split(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out,
                                           int B, int Q, int H, int S, int pieces, int64_t q_pstride, int64_t bank_pstride,
                                           const uint32_t* key_bits, int32_t* rowmap, void* stream) {
@@ -159,12 +169,11 @@ extern "C" int gram_cross_attn_rows_split(const void* q, const void* k_layer, co
     return gram_cross_attn_decode_split(q, k_layer, vt_layer, mask, out, B, Q, H, S, nullptr, nullptr, pieces, q_pstride, bank_pstride,
                                         key_bits, stream);
   if (!rowmap || (int64_t)B * Q > INT32_MAX) return GRAM_E_ARG;
-  const int kt = Q % GRAM_MAX_BEAMS;
   int32_t* users = rowmap;
   int32_t* full = users + B;
   int32_t* tail = full + (size_t)B * GRAM_MAX_BEAMS;
-  hipLaunchKernelGGL(tf_rowmap_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, users, full, tail, Q, kt);
-  GRAM_CHECK_LAUNCH();
+  const int e0 = gram_tf_rowmap(rowmap, B, Q, stream);
+  if (e0) return e0;
   const size_t inner = (size_t)H * 64;
   for (int r0 = 0; r0 < Q; r0 += GRAM_MAX_BEAMS) {
     const int kc = Q - r0 < GRAM_MAX_BEAMS ? Q - r0 : GRAM_MAX_BEAMS;

@@ -264,7 +264,8 @@ class GRAM(nn.Module):
         """Longest (padded) passage the model takes: a multiple of 32 in [128, 512], default 128 (``--item_prompt_max_len`` of the
         reference, arguments.py:293-298).  Above 128 the encoder's self-attention is the tiled kernel for long passages at EVERY
         length (gram_model_set_max_passage_len), so a passage's bits never depend on the batch it was padded with; at 128 the model
-        launches what it always launched.  N * L <= 4096 holds in every mode.  The passage cache is cleared and its rows become
+        launches what it always launched.  N * L stays within the model's fused limit in every mode (4096 unless raised:
+        ``set_max_fused_tokens``).  The passage cache is cleared and its rows become
         ``n`` long.  The kernel indexes the encoder's relative bias by clamp(key - query, -127, 127): a config whose bucket
         function is not constant beyond +-127 (relative_attention_max_distance > 128) is refused for n > 128."""
         n = int(n)
@@ -294,6 +295,34 @@ class GRAM(nn.Module):
                     else f"set_max_passage_len goes up to {_lib.GRAM_MAX_LONG_PASSAGE_LEN}")
             raise ValueError(f"passages of {L} tokens (padded to {Lp}) exceed this model's limit of {self._max_passage_len}: {hint}")
         return Lp
+
+    _max_fused_tokens = _lib.GRAM_MAX_FUSED_LEN  # (class default: a model starts at the short cross-attention's limit)
+
+    def set_max_fused_tokens(self, n: int) -> None:
+        """Longest fused context N * L (passages x padded passage length) the model takes: a multiple of 32 in [4096, 16384],
+        default 4096.  The reference's default history (``--max_his 20``: 21 passages) needs 4704 at 224 tokens per passage and
+        10752 at 512.  Above 4096 the decoder's cross-attention is the segmented kernel at EVERY length
+        (gram_model_set_max_fused_len), so a user's bits never depend on the batch it was padded with; at 4096 the model launches
+        what it always launched.  The passage cache stays: cached passages do not depend on N * L.  ``cross_attentions`` and
+        ``passage_attention`` stay limited to 4096 fused tokens.  The cross K/V bank is what grows: layers x heads x 64 x (K, V^T) x
+        2 B x pieces per fused key and user -- 73.7 KB at T5-base and two pieces, 0.79 GB per user at N * L = 10752; the users per
+        call follow from the workspace queries (``max_users_per_call``)."""
+        n = int(n)
+        if n % 32 or not _lib.GRAM_MAX_FUSED_LEN <= n <= _lib.GRAM_MAX_LONG_FUSED_LEN:
+            raise ValueError(f"set_max_fused_tokens: a multiple of 32 in [{_lib.GRAM_MAX_FUSED_LEN}, {_lib.GRAM_MAX_LONG_FUSED_LEN}] "
+                             f"is supported (got {n})")
+        self._max_fused_tokens = n
+        if self._packed is not None and self._packed[1] == self._version:
+            _lib.check(_lib.load().gram_model_set_max_fused_len(self._packed[2], n), "gram_model_set_max_fused_len")
+
+    def _check_fused_len(self, N: int, L: int) -> int:
+        """The fused length N * (L padded to 32) of a call, or a ValueError that names the way out."""
+        S = int(N) * ((int(L) + 31) // 32 * 32)
+        if S > self._max_fused_tokens:
+            hint = (f"call set_max_fused_tokens({S}) first" if S <= _lib.GRAM_MAX_LONG_FUSED_LEN
+                    else f"set_max_fused_tokens goes up to {_lib.GRAM_MAX_LONG_FUSED_LEN}")
+            raise ValueError(f"{N} passages of {L} tokens are {S} fused tokens, above this model's limit of {self._max_fused_tokens}: {hint}")
+        return S
 
     def _invalidate(self) -> None:
         self._version += 1
@@ -429,6 +458,7 @@ class GRAM(nn.Module):
         """Largest B <= limit whose teacher-forced workspace (gram_workspace_bytes_tf) and outputs fit the free HBM, net of what a
         reserved passage cache will still allocate (``reserve_passage_cache``).  ``extra_per_user``: further output bytes per user
         (the attention buffers of ``cross_attentions`` / ``passage_attention``)."""
+        self._check_fused_len(N, L)
         handle = self._pack()
         lib = _lib.load()
         Lp = (int(L) + 31) // 32 * 32
@@ -443,6 +473,7 @@ class GRAM(nn.Module):
     def max_users_per_call_trie(self, N: int, L: int, Q: int, n_out: int, limit: int = 1 << 20, headroom: float = 0.9) -> int:
         """``max_users_per_call_tf`` for the one-pass scoring of a Trie (gram_workspace_bytes_trie): Q decoder rows and ``n_out``
         fp32 outputs per user."""
+        self._check_fused_len(N, L)
         handle = self._pack()
         lib = _lib.load()
         Lp = (int(L) + 31) // 32 * 32
@@ -481,6 +512,7 @@ class GRAM(nn.Module):
         output bytes per user.  ``trie_rows=(Q, n_out)``: the one-pass scoring of a Trie instead -- Q decoder rows and n_out fp32
         outputs per user, the workspace of gram_workspace_bytes_trie, no dec / lab (``call`` gets None for both)."""
         self._check_passage_len(input_ids.shape[-1])
+        self._check_fused_len(input_ids.shape[1], input_ids.shape[2])
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()
@@ -516,7 +548,7 @@ class GRAM(nn.Module):
             need = ws_bytes(nb)
             if need < 0:
                 raise _lib.GramHipError(f"unsupported problem size B={nb} N={N} L={Lp} {size} (N <= max_item_num+1, L <= {self._max_passage_len}, "
-                                        f"N*L <= 4096, T <= {_lib.GRAM_MAX_DEC_LEN})")
+                                        f"N*L <= {self._max_fused_tokens}, T <= {_lib.GRAM_MAX_DEC_LEN})")
             ws = self._ensure_workspace(need)
             ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
             if trie_rows is not None:
@@ -546,6 +578,10 @@ class GRAM(nn.Module):
         of torch.ops.gram.teacher_forced_attn, with the attention buffers counted in the chunk budget."""
         if attention_mask.shape != input_ids.shape:
             raise ValueError("attention_mask must have input_ids' shape (B, N, L)")
+        S = int(input_ids.shape[1]) * ((int(input_ids.shape[2]) + 31) // 32 * 32)
+        if S > _lib.GRAM_MAX_FUSED_LEN:
+            raise ValueError(f"cross-attention probabilities are limited to {_lib.GRAM_MAX_FUSED_LEN} fused tokens (got N*L = {S}): "
+                             f"cross_attentions / passage_attention do not take the longer contexts set_max_fused_tokens allows")
         V, H, nl = int(self.config.vocab_size), int(self.config.num_heads), int(self.config.num_decoder_layers)
         N, Q = input_ids.shape[1], dec.shape[1] * dec.shape[2]
 
@@ -770,6 +806,8 @@ class GRAM(nn.Module):
         self._packed = (dev, self._version, handle, keep)
         if self._max_passage_len != _lib.GRAM_MAX_PASSAGE_LEN:
             _lib.check(lib.gram_model_set_max_passage_len(handle, self._max_passage_len), "gram_model_set_max_passage_len")
+        if self._max_fused_tokens != _lib.GRAM_MAX_FUSED_LEN:
+            _lib.check(lib.gram_model_set_max_fused_len(handle, self._max_fused_tokens), "gram_model_set_max_fused_len")
         self._build_token_tables(handle, keep)
         return handle
 
@@ -797,7 +835,7 @@ class GRAM(nn.Module):
         if need < 0:
             raise _lib.GramHipError(
                 f"unsupported problem size B={B} N={N} L={L} K={K} max_length={max_length} "
-                f"(N <= max_item_num+1, L <= {self._max_passage_len}, N*L <= 4096, K <= 64, max_length <= {_lib.GRAM_MAX_DEC_LEN}; "
+                f"(N <= max_item_num+1, L <= {self._max_passage_len}, N*L <= {self._max_fused_tokens}, K <= 64, max_length <= {_lib.GRAM_MAX_DEC_LEN}; "
                 f"the Trie's fan-out is not limited)"
             )
         return self._ensure_workspace(need)
@@ -816,6 +854,7 @@ class GRAM(nn.Module):
         size their GPU batches with, whatever ``--eval_batch_size`` the loader was built with (results do not depend on the batch a
         user is scored in).  Memory held by this model's current workspace counts as free (it is re-used or replaced); the handle's
         token tables (_build_token_tables) are allocated by the time the free memory is read, so they are already subtracted."""
+        self._check_fused_len(N, L)
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()
@@ -1091,6 +1130,7 @@ class GRAM(nn.Module):
         if input_ids.dim() != 3:
             raise ValueError("input_ids must be (B, N, L)")
         self._check_passage_len(input_ids.shape[-1])
+        self._check_fused_len(input_ids.shape[1], input_ids.shape[2])
         handle = self._pack()
         lib = _lib.load()
         dev = self._device()

@@ -18,6 +18,7 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
     torch.ops.gram.enc_self_attn     T5Attention self branch on (P*L, 3*inner) q|k|v rows (gram_enc_self_attn)
     torch.ops.gram.enc_self_attn_long  the same for passages of up to 512 tokens (gram_enc_self_attn_long_split)
     torch.ops.gram.cross_attn_decode the fusion read of one decoder layer and step over the beam-shared bank
+    torch.ops.gram.cross_attn_long   the same over up to 16 384 fused keys (gram_cross_attn_long_split)
     torch.ops.gram.trie_step         one Trie-constrained beam-search step on dense logits (gram_row_lse + gram_beam_step)
 """
 from __future__ import annotations
@@ -453,6 +454,39 @@ def _(q, k_bank, vt_bank, mask, num_beams):
     return torch.empty_like(q)
 
 
+@torch.library.custom_op("gram::cross_attn_long", mutates_args=(), device_types="cuda")
+def cross_attn_long(q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor, num_beams: int) -> Tensor:
+    """``cross_attn_decode`` over up to 16 384 fused keys (gram_mask_key_bits_long + gram_cross_attn_long_split, one piece): the same
+    operands.  A row's bits depend on the query row and the user's valid 32-key steps in order, not on the batch or on S; they are
+    not ``cross_attn_decode``'s bits (another summation order)."""
+    dt = _lib.piece_dtype()
+    if k_bank.dim() != 4 or k_bank.shape[-1] != 64:
+        raise ValueError("cross_attn_long: k_bank must be (B, H, S, 64)")
+    B, H, S, _ = k_bank.shape
+    if S < 32 or S % 32 or S > _lib.GRAM_MAX_LONG_FUSED_LEN or not 1 <= num_beams <= _lib.GRAM_MAX_BEAMS:
+        raise ValueError(f"cross_attn_long: S must be a multiple of 32 in [32, {_lib.GRAM_MAX_LONG_FUSED_LEN}] and "
+                         f"1 <= num_beams <= {_lib.GRAM_MAX_BEAMS}")
+    _check("k_bank", k_bank, dt)
+    _check("vt_bank", vt_bank, dt, (B, H, S // 32, 64, 32), k_bank.device)  # V^T blocked by 32 keys
+    _check("q", q, dt, (B * num_beams, H * 64), k_bank.device)
+    _check("mask", mask, torch.uint8, (B, S), k_bank.device)
+    lib = _lib.load()
+    out = torch.empty_like(q)
+    bits = torch.empty(B, _lib.GRAM_KEY_BITS_LONG_STRIDE, dtype=torch.int32, device=q.device)
+    scratch = torch.empty(max(1, int(lib.gram_cross_attn_long_scratch_bytes(B * num_beams, H, S)) // 4), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.check(lib.gram_mask_key_bits_long(mask.data_ptr(), bits.data_ptr(), B, S, _stream(q)), "gram_mask_key_bits_long")
+        rc = lib.gram_cross_attn_long_split(q.data_ptr(), k_bank.data_ptr(), vt_bank.data_ptr(), mask.data_ptr(), out.data_ptr(), B, num_beams,
+                                            H, S, None, None, 1, 0, 0, bits.data_ptr(), scratch.data_ptr(), _stream(q))
+    _lib.check(rc, "gram_cross_attn_long_split")
+    return out
+
+
+@cross_attn_long.register_fake
+def _(q, k_bank, vt_bank, mask, num_beams):
+    return torch.empty_like(q)
+
+
 # ---------------------------------------------------------------------------------------------- Trie-constrained search step
 @torch.library.custom_op("gram::trie_step", mutates_args=("tokens", "node", "beam_scores", "seq", "anc", "done", "n_hyps", "hyp_score",
                                                           "worst", "hyp_len", "hyp_tok", "error"), device_types="cuda")
@@ -503,4 +537,4 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
-__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "score_trie", "linear", "enc_self_attn", "enc_self_attn_long", "cross_attn_decode", "trie_step"]
+__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "score_trie", "linear", "enc_self_attn", "enc_self_attn_long", "cross_attn_decode", "cross_attn_long", "trie_step"]

@@ -287,6 +287,21 @@ class BaseRunner:
     def _decode(self, ids: torch.Tensor) -> List:
         return self._decode_rows(ids.detach().cpu().tolist())
 
+    def _raise_model_limits(self, testloader) -> None:
+        """Tell the model what the run's prompts need before its first call: passages above 128 tokens and fused contexts above 4096."""
+        # --item_prompt_max_len above 128 (arguments.py:293-298): the model takes passages of up to 512 tokens once told so
+        prompt_len = int(getattr(getattr(testloader, "collate_fn", None), "item_prompt_max_len", 0) or _arg(self.args, "item_prompt_max_len", 128))
+        prompt_len = (prompt_len + 31) // 32 * 32
+        gen_model = self._generate_model()
+        if prompt_len > 128 and hasattr(gen_model, "set_max_passage_len") and getattr(gen_model, "_max_passage_len", 128) != prompt_len:
+            gen_model.set_max_passage_len(prompt_len)
+        # ... and the default history (--max_his 20: 21 passages) times a long prompt is more than 4096 fused tokens
+        fused = (int(_arg(self.args, "max_his", 20)) + 1) * prompt_len
+        if fused > 4096 and hasattr(gen_model, "set_max_fused_tokens"):
+            fused = min(16384, (fused + 31) // 32 * 32)
+            if getattr(gen_model, "_max_fused_tokens", 4096) != fused:
+                gen_model.set_max_fused_tokens(fused)
+
     def _score_loader(self, testloader):
         """Per-user hit ranks for one loader: (ranks int16 [n], total generate() seconds, examples, user ids, pred rows).
 
@@ -312,12 +327,7 @@ class BaseRunner:
             phases[name] = phases.get(name, 0.0) + now - t_phase
             t_phase = now
 
-        # --item_prompt_max_len above 128 (arguments.py:293-298): the model takes passages of up to 512 tokens once told so
-        prompt_len = int(getattr(getattr(testloader, "collate_fn", None), "item_prompt_max_len", 0) or _arg(self.args, "item_prompt_max_len", 128))
-        prompt_len = (prompt_len + 31) // 32 * 32
-        gen_model = self._generate_model()
-        if prompt_len > 128 and hasattr(gen_model, "set_max_passage_len") and getattr(gen_model, "_max_passage_len", 128) != prompt_len:
-            gen_model.set_max_passage_len(prompt_len)
+        self._raise_model_limits(testloader)
         self._warm_passage_cache(testloader)
         lap("passage_cache")
         candidates = testloader.dataset.all_items

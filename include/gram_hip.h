@@ -40,7 +40,9 @@ extern "C" {
 #define GRAM_MAX_DEC_LEN 64    /* max_length <= 64 (reference: the longest candidate, 8..12, for the "split" / "t5_token" id
                                   types, 50 for "term": single_runner_gram.py:629-637); also the row stride of dec_bias_f32 */
 #define GRAM_MAX_PASSAGE_LEN 128 /* L <= 128 on a default handle (arguments.py:293-298), L % 32 == 0 */
-#define GRAM_MAX_LONG_PASSAGE_LEN 512 /* L <= 512 on a handle raised by gram_model_set_max_passage_len; N * L <= 4096 always */
+#define GRAM_MAX_LONG_PASSAGE_LEN 512 /* L <= 512 on a handle raised by gram_model_set_max_passage_len */
+#define GRAM_MAX_FUSED_LEN 4096       /* S = N * L <= 4096 on a default handle */
+#define GRAM_MAX_LONG_FUSED_LEN 16384 /* S <= 16 384 on a handle raised by gram_model_set_max_fused_len */
 
 /* ---- GEMM epilogues ------------------------------------------------------------------ */
 enum gram_epilogue {
@@ -195,6 +197,34 @@ int gram_cross_attn_decode_split(const void* q, const void* k_layer, const void*
                                  int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits, void* stream);
 /* key_bits u32 [B][128]: bit j of word st = mask[b][32*st + j] != 0 (st < S/32). */
 int gram_mask_key_bits(const uint8_t* mask, uint32_t* key_bits, int B, int S, void* stream);
+/* ---- cross-attention over up to GRAM_MAX_LONG_FUSED_LEN fused keys (the form a handle raised by gram_model_set_max_fused_len runs) ----
+ * key_bits for the long form, u32 [B][GRAM_KEY_BITS_LONG_STRIDE]: words 0 .. GRAM_KEY_BITS_LONG_WORDS-1 of a row are the step words
+ * (bit j of word st = mask[b][32*st + j] != 0, zero for st >= S/32), word GRAM_KEY_BITS_LONG_WORDS is the number of nonzero step
+ * words (the user's valid 32-key steps; 0 = no valid key), the rest of the row is zero.  Any S = 32 n, 32 <= S <= 16 384; mask
+ * 16-byte aligned.  The bits belong to the S they were packed for. */
+#define GRAM_KEY_BITS_LONG_WORDS 512
+#define GRAM_KEY_BITS_LONG_STRIDE 528
+int gram_mask_key_bits_long(const uint8_t* mask, uint32_t* key_bits, int B, int S, void* stream);
+/* Bytes of fp32 scratch gram_cross_attn_long_split needs for `rows` = B * K (user, beam) slots: one unnormalised partial
+ * (O[64], m, l: 68 floats) per slot, head and segment of 4096 keys; 0 for S <= 4096 (one segment stores directly).  GRAM_E_ARG for
+ * rows or H < 1 or an S the kernel does not take. */
+int64_t gram_cross_attn_long_scratch_bytes(int rows, int H, int S);
+/* gram_cross_attn_decode_split's operands and conventions (planar Q pieces, K bank [s][64], V^T bank blocked by 32 keys, unscaled
+ * scores, masked keys at finfo.min, fp32 softmax, output interleaved at two pieces, users/rowpos NULL or the live-row form) for any
+ * S = 32 n, 32 <= S <= 16 384.  Split-key: a user's valid 32-key steps, counted in key order, are cut into segments of 128; one
+ * workgroup per (head, user, segment) writes an unnormalised partial softmax to `scratch`, and a second kernel folds a row's
+ * partials in ascending segment order (launched only for S > 4096; a user whose valid steps fit one segment is stored by that
+ * segment).  No atomics, one fixed summation order.  A row's bits depend on its query row and on the user's valid steps in order:
+ * not on B, the user's place in the batch, K, the live-row form, or where the masked steps lie between the valid ones (the
+ * batch's L and N) -- and they are NOT gram_cross_attn_decode_split's bits.  Fully masked steps are never fetched and masked keys
+ * contribute exactly nothing, whatever the bank holds there; a user without a valid key gets the uniform row over exactly S keys.
+ * key_bits: gram_mask_key_bits_long of the same mask and S (required; `mask` itself is not read).  scratch: 16-byte aligned,
+ * gram_cross_attn_long_scratch_bytes(B * K, H, S) bytes, may be NULL for S <= 4096.  GRAM_E_ARG before any launch: a null q / k_layer /
+ * vt_layer / out / key_bits, a misaligned pointer, S out of range, K > GRAM_MAX_BEAMS, or (two pieces) q_pstride < B*K*H*64 in the
+ * all-rows form or bank_pstride < H*S*64. */
+int gram_cross_attn_long_split(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out, int B, int K,
+                               int H, int S, const int32_t* users, const int32_t* rowpos, int pieces, int64_t q_pstride,
+                               int64_t bank_pstride, const uint32_t* key_bits, float* scratch, void* stream);
 /* rows NULL: all R rows; else the live-row form (gram_dec_self_attn_live). */
 int gram_dec_self_attn_split(const void* qkv, void* kcache, void* vcache, const int32_t* anc, const float* bias, void* out,
                              int R, int n_rows, const int32_t* rows, int H, int t, int Tmax, int pieces, int64_t qkv_pstride,
@@ -476,9 +506,19 @@ void gram_model_destroy(gram_model_t* m);
  * [GRAM_MAX_PASSAGE_LEN, GRAM_MAX_LONG_PASSAGE_LEN] (GRAM_E_ARG otherwise).  A handle with Lmax > 128 runs the long encoder
  * self-attention (gram_enc_self_attn_long[_rows]_split) at EVERY L, so that a passage's bits never depend on the padded length of
  * the batch it landed in; a handle at 128 launches exactly what it always launched.  Every whole-path entry point and workspace
- * query returns GRAM_E_ARG for L > Lmax or N * L > 4096 before any launch.  The caller guarantees that the encoder's bias is
+ * query returns GRAM_E_ARG for L > Lmax or N * L above the handle's fused limit (gram_model_set_max_fused_len; 4096 by default)
+ * before any launch.  The caller guarantees that the encoder's bias is
  * constant beyond distance +-127 (relative_attention_max_distance <= 128) before raising the limit. */
 int gram_model_set_max_passage_len(gram_model_t* m, int Lmax);
+
+/* Longest fused context S = N * L the handle's whole-path entry points take (default GRAM_MAX_FUSED_LEN).  Smax must be a multiple
+ * of 32 in [GRAM_MAX_FUSED_LEN, GRAM_MAX_LONG_FUSED_LEN] (GRAM_E_ARG otherwise, the limit unchanged).  A handle with Smax > 4096 runs
+ * the long cross-attention (gram_mask_key_bits_long, gram_cross_attn_long_split, gram_cross_attn_rows_long_split) at EVERY S -- in the
+ * decode step's all-rows and live-row forms, the teacher-forced pass and gram_score_trie -- so that a user's bits never depend on
+ * whether its batch crossed 4096; its workspaces hold the wider key bits and the long form's scratch.  A handle at 4096 launches
+ * exactly what it always launched.  Cross-attention probabilities stay limited to 4096 keys: gram_teacher_forced_ex with attention
+ * outputs returns GRAM_E_ARG for N * L > 4096 on any handle. */
+int gram_model_set_max_fused_len(gram_model_t* m, int Smax);
 
 /* Layer-0 q|k|v per TOKEN.  T5 has no absolute positions: the first sublayer of each stack norms the raw embedding row of a token
  * (row-local) and multiplies it by layer 0's W_qkv, so its q|k|v row depends on the token id and the weights only.  The two tables
@@ -610,6 +650,13 @@ int gram_dec_self_attn_tf_split(const void* qkv, const float* bias, void* out, i
 int gram_cross_attn_rows_split(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out, int B, int Q,
                                int H, int S, int pieces, int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits,
                                int32_t* rowmap, void* stream);
+/* The same over up to 16 384 fused keys: gram_cross_attn_long_split with K = Q for Q <= GRAM_MAX_BEAMS, one live-row call of it per
+ * group of <= GRAM_MAX_BEAMS rows above (same bits as those calls made by hand).  key_bits: gram_mask_key_bits_long; scratch:
+ * gram_cross_attn_long_scratch_bytes(B * min(Q, GRAM_MAX_BEAMS), H, S) bytes, reused by every group; rowmap as above.  GRAM_E_ARG
+ * before any launch: gram_cross_attn_long_split's cases, a NULL rowmap for Q > GRAM_MAX_BEAMS, or (two pieces) q_pstride < B*Q*H*64. */
+int gram_cross_attn_rows_long_split(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out, int B,
+                                    int Q, int H, int S, int pieces, int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits,
+                                    float* scratch, int32_t* rowmap, void* stream);
 
 /* Label log-probs from the final hidden rows: token_logp[r] = hidden[r] . E[labels[r]] - lse[r] for labels[r] >= 0 (0 otherwise),
  * the dot product being gram_beam_step_sparse_split's (E = lm_head_f32 when pieces = 2, lm_head_bf16 when 1), lse from

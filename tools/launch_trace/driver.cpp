@@ -34,6 +34,7 @@ struct Case {
   int attn;                   // gram_teacher_forced_ex: 1 = every layer's probabilities, 2 = one layer of scratch + token and passage scores
   bool items;                 // gram_generate_items: per-user item filters (gram_user_items_t)
   int max_L;                  // != 0: gram_model_set_max_passage_len first (a long-mode handle: the tiled encoder attention at every L)
+  int max_S;                  // != 0: gram_model_set_max_fused_len first (the long cross-attention at every S; the model takes 40 passages)
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -83,15 +84,22 @@ const Case kCases[] = {
     {"generate_long_32", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 256},
     {"generate_long_160", GENERATE, 1, 1, 2, 3, 160, 4, 4, SOME, false, false, false, false, 0, false, 256},
     {"generate_p2_tables_long_160", GENERATE, 2, 1, 2, 3, 160, 4, 4, SOME, false, false, false, true, 0, false, 256},
+    // handles with a raised fused limit (gram_model_set_max_fused_len(16384)): the train of generate_p1_folded with the long key bits and
+    // the long cross-attention in place of the short ones, then N * L = 21 * 224 = 4704 -- a context a default handle refuses -- through
+    // generate, the teacher-forced pass and the Trie pass
+    {"generate_fused_32", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 16384},
+    {"generate_fused_4704", GENERATE, 2, 1, 2, 21, 224, 4, 4, SOME, false, false, false, false, 0, false, 256, 16384},
+    {"tf_fused_4704", TEACHER_FORCED, 2, 1, 2, 21, 224, 3, 4, OFF, false, false, false, false, 0, false, 256, 16384},
+    {"score_trie_fused_4704", SCORE_TRIE, 2, 1, 2, 21, 224, 3, 4, OFF, false, false, false, false, 0, false, 256, 16384},
 };
 
-gram_model_t* make_model(int pieces, int fold) {
+gram_model_t* make_model(int pieces, int fold, int max_passages) {
   enum { NL = 2 };
   static const float* ln[5][NL];
   static const void* w[10][NL];
   static float scales[10 * NL + 2];
   gram_model_desc_t d{};
-  d.vocab = 256, d.d_model = 128, d.d_ff = 256, d.n_heads = 2, d.n_enc_layers = d.n_dec_layers = NL, d.max_passages = 5;
+  d.vocab = 256, d.d_model = 128, d.d_ff = 256, d.n_heads = 2, d.n_enc_layers = d.n_dec_layers = NL, d.max_passages = max_passages;
   d.tie_word_embeddings = d.use_position_embedding = 1, d.fold_norm = fold, d.eps = 1e-6f, d.pieces = pieces;
   d.embed_f32 = fake<float>(), d.lm_head_bf16 = fake(), d.pos_emb_f32 = fake<float>(), d.enc_bias_f32 = fake<float>();
   d.dec_bias_f32 = fake<float>(), d.enc_final_ln = fake<float>(), d.dec_final_ln = fake<float>();
@@ -109,9 +117,10 @@ gram_model_t* make_model(int pieces, int fold) {
 }
 
 int run(const Case& c) {
-  gram_model_t* m = make_model(c.pieces, c.fold);
+  gram_model_t* m = make_model(c.pieces, c.fold, c.max_S ? 40 : 5);
   if (!m) return GRAM_E_ARG;
   if (c.max_L) trace_line("gram_model_set_max_passage_len", gram_model_set_max_passage_len(m, c.max_L));
+  if (c.max_S) trace_line("gram_model_set_max_fused_len", gram_model_set_max_fused_len(m, c.max_S));
   void* st = fake();
   const int64_t* ids = fake<int64_t>();
   const uint8_t* mask = fake<uint8_t>();

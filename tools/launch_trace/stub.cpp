@@ -124,6 +124,20 @@ int gram_cross_attn_decode_split(const void* q, const void* k, const void* vt, c
                                  const uint32_t* key_bits, void* st) {
   REC(q, k, vt, mask, out, B, K, H, S, users, rowpos, pieces, q_ps, bank_ps, key_bits, st);
 }
+int gram_mask_key_bits_long(const uint8_t* mask, uint32_t* key_bits, int B, int S, void* st) { REC(mask, key_bits, B, S, st); }
+int64_t gram_cross_attn_long_scratch_bytes(int rows, int H, int S) {  // (the product's size: a query, not a launch -- nothing recorded)
+  return S <= GRAM_MAX_FUSED_LEN ? 0 : (int64_t)rows * H * ((S + 4095) / 4096) * 68 * 4;
+}
+int gram_cross_attn_long_split(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int B, int K, int H, int S,
+                               const int32_t* users, const int32_t* rowpos, int pieces, int64_t q_ps, int64_t bank_ps,
+                               const uint32_t* key_bits, float* scratch, void* st) {
+  REC(q, k, vt, mask, out, B, K, H, S, users, rowpos, pieces, q_ps, bank_ps, key_bits, scratch, st);
+}
+int gram_cross_attn_rows_long_split(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int B, int Q, int H, int S,
+                                    int pieces, int64_t q_ps, int64_t bank_ps, const uint32_t* key_bits, float* scratch, int32_t* rowmap,
+                                    void* st) {
+  REC(q, k, vt, mask, out, B, Q, H, S, pieces, q_ps, bank_ps, key_bits, scratch, rowmap, st);
+}
 int gram_dec_self_attn_tf_split(const void* qkv, const float* bias, void* out, int n_seq, int T, int H, int pieces, int64_t qkv_ps, void* st) {
   REC(qkv, bias, out, n_seq, T, H, pieces, qkv_ps, st);
 }
