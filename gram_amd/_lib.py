@@ -23,6 +23,8 @@ EPI_BF16, EPI_BF16_RELU, EPI_F32_ADD, EPI_F32, EPI_KV_BANK = range(5)
 K_GEMM, K_ENC_ATTN, K_CROSS_ATTN, K_DEC_SELF_ATTN, K_ROWOPS, K_LSE, K_BEAM = range(7)
 E_ARG, E_WORKSPACE, E_BEAM, E_NONFINITE = -1, -2, -3, -4
 ABI_VERSION = 7
+GRAM_TAIL_ENTRY_ROWS = 64    # forest rows of one cross-attention entry of the tail pass (gram_forest_t.ent_rows)
+GRAM_TAIL_MAX_STEPS = 16     # decode steps one tail pass replaces at most (gram_trie_tail_t)
 GRAM_MAX_USER_ITEMS = 4096   # entries of one user's item list (gram_user_items_t)
 ITEMS_EXCLUDE, ITEMS_ALLOW = 0, 1
 # two-piece mode (gram_hip.h, gram_split_t): 16-bit pieces per value -> MFMA products per product
@@ -102,6 +104,18 @@ class TrieRows(C.Structure):
     """gram_trie_rows_t: the row tables of a Trie for gram_score_trie (device pointers; FlatTrie.decoder_rows)"""
     _fields_ = [("tokens", vp), ("pos", vp), ("anc", vp), ("row_node", vp), ("node_row", vp), ("node_tok", vp), ("node_leaf", vp),
                 ("Q", i32), ("Tq", i32), ("n_nodes", i32), ("n_leaves", i32)]
+
+
+class TrieTail(C.Structure):
+    """gram_trie_tail_t: the tail tables of a Trie for gram_generate_tail (FlatTrie.tail_tables; sub_rows a device pointer)"""
+    _fields_ = [("sub_rows", vp), ("d_tail", i32), ("steps", i32)]
+
+
+class Forest(C.Structure):
+    """gram_forest_t: the forest of one tail pass (device pointers)"""
+    _fields_ = [("tokens", vp), ("pos", vp), ("parent", vp), ("root", vp), ("node", vp), ("user_off", vp), ("ent_off", vp),
+                ("ent_users", vp), ("ent_rows", vp), ("rowpos", vp), ("counts", vp), ("slot", vp), ("lvl_rows", vp), ("lvl_tokens", vp),
+                ("lvl_anc", vp), ("cap_rows", i32), ("cap_entries", i32), ("n_levels", i32), ("pad_", i32)]
 
 
 class ModelDesc(C.Structure):
@@ -235,6 +249,21 @@ SIGNATURES = {
     "gram_workspace_bytes_trie": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gram_score_trie": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Compaction), C.POINTER(Trie), C.POINTER(TrieRows), vp,
                                   i64, vp, vp, vp]),
+    # the tail pass: the chain-like lower levels of the Trie in one decoder pass per user forest
+    "gram_tail_forest": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), C.POINTER(TrieTail), C.POINTER(Forest), C.c_int, vp]),
+    "gram_tail_rowpos": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), C.POINTER(Forest), vp]),
+    "gram_scatter_rows": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "gram_cross_attn_entries_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, i64, i64, vp,
+                                                vp]),
+    "gram_workspace_bytes_tail": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gram_generate_tail": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
+                                     C.POINTER(Compaction), C.POINTER(TrieTail), vp, i64, vp, vp, C.POINTER(i32), vp]),
+    "gram_debug_set_tail_pass": (C.c_int, [C.c_int]),
+    "gram_tail_pass_wanted": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+    "gram_debug_set_tail_capacity": (C.c_int, [C.c_int]),
+    "gram_debug_set_tail_level_capacity": (C.c_int, [C.c_int]),
+    "gram_debug_tail_last": (C.c_int, [C.POINTER(i32)]),
+    "gram_debug_workspace_beam_state": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BeamState)]),
 }
 
 # the `_f16` aliases (gram_hip.h): same signatures as the `_bf16` names

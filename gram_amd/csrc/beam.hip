@@ -1103,6 +1103,200 @@ __global__ void trie_item_index_kernel(gram_trie_t tr, const int32_t* __restrict
   out_item[r] = item;
 }
 
+// ---- the forest of the tail pass (gram_forest_t, gram_hip.h).  A beam is live exactly as in live_rows_kernel.
+__device__ __forceinline__ bool tail_live(const gram_beam_state_t& st, const gram_trie_t& tr, int b, int row) {
+  if (st.done[b]) return false;
+  const int nd = st.node[row];
+  return nd >= 0 && nd < tr.n_nodes && tr.child_off[nd + 1] > tr.child_off[nd];
+}
+
+// Rows and entries per user from the per-node subtree sizes, their exclusive prefix sums and the totals: one workgroup, as
+// live_rows_kernel.  A user's count saturates just above the capacity, so that no sum leaves 64 bits' easy range.
+__global__ __launch_bounds__(1024) void tail_count_kernel(gram_beam_state_t st, gram_trie_t tr, gram_trie_tail_t tl, gram_forest_t f) {
+  __shared__ long long s_w[16], s_tot;
+  __shared__ int s_mx[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = st.K, B = st.B;
+  auto scan = [&](long long v) {  // inclusive block scan; s_tot = block total
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long n = __shfl_up(v, o, 64);
+      if (lane >= o) v += n;
+    }
+    gram_sync();  // previous round's s_w / s_tot readers are done
+    if (lane == 63) s_w[wave] = v;
+    gram_sync();
+    if (tid == 0) {
+      long long acc = 0;
+      for (int w = 0; w < 16; ++w) {
+        const long long t = s_w[w];
+        s_w[w] = acc;
+        acc += t;
+      }
+      s_tot = acc;
+    }
+    gram_sync();
+    return v + s_w[wave];
+  };
+  const long long sat = (long long)f.cap_rows + 1;
+  long long rbase = 0, ebase = 0;
+  int mx = 0;
+  for (int c0 = 0; c0 < B; c0 += 1024) {
+    const int b = c0 + tid;
+    long long n = 0;
+    if (b < B) {
+      for (int k = 0; k < K; ++k)
+        if (tail_live(st, tr, b, b * K + k)) {
+          const int s = tl.sub_rows[st.node[b * K + k]];
+          n += s > 0 ? s : 0;
+        }
+      n = n > sat ? sat : n;
+    }
+    const long long e = (n + GRAM_TAIL_ENTRY_ROWS - 1) / GRAM_TAIL_ENTRY_ROWS;
+    const long long ri = scan(n);
+    const long long r0 = rbase + ri - n;
+    rbase += s_tot;
+    const long long ei = scan(e);
+    const long long e0 = ebase + ei - e;
+    ebase += s_tot;
+    if (b < B) {
+      f.user_off[b] = (int)(r0 > INT32_MAX ? INT32_MAX : r0);
+      f.ent_off[b] = (int)(e0 > INT32_MAX ? INT32_MAX : e0);
+      mx = n > mx ? (int)n : mx;
+    }
+  }
+  mx = (int)wave_max((float)mx);  // (counts are far below 2^24: exact)
+  if (lane == 0) s_mx[wave] = mx;
+  gram_sync();
+  if (tid == 0) {
+    for (int w = 1; w < 16; ++w) mx = s_mx[w] > mx ? s_mx[w] : mx;
+    f.user_off[B] = (int)(rbase > INT32_MAX ? INT32_MAX : rbase);
+    f.ent_off[B] = (int)(ebase > INT32_MAX ? INT32_MAX : ebase);
+    f.counts[0] = f.user_off[B];
+    f.counts[1] = f.ent_off[B];
+    f.counts[2] = mx;
+    f.counts[3] = 0;
+    for (int l = 0; l < 2 * GRAM_TAIL_MAX_STEPS; ++l) f.counts[4 + l] = 0;  // (tail_fill_kernel adds the (group, level) rows up)
+  }
+}
+
+// The rows of one user per thread, breadth first: the forest's rows are their own queue.  Nothing is written for a forest over
+// capacity.  A subtree table that disagrees with the Trie is error 3; the rows it promised and the walk did not find are made
+// harmless copies of a start row, so that nothing downstream reads outside its tables.
+__global__ __launch_bounds__(64) void tail_fill_kernel(gram_beam_state_t st, gram_trie_t tr, gram_forest_t f, int t) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= st.B) return;
+  if (f.counts[0] > f.cap_rows || f.counts[1] > f.cap_entries) return;
+  const int K = st.K, base = f.user_off[b], cnt = f.user_off[b + 1] - base;
+  auto put = [&](int i, int tok, int pos, int parent, int root, int node) {
+    f.tokens[i] = tok;
+    f.pos[i] = pos;
+    f.parent[i] = parent;
+    f.root[i] = root;
+    f.node[i] = node;
+  };
+  int n = 0;
+  for (int k = 0; k < K && n < cnt; ++k)
+    if (tail_live(st, tr, b, b * K + k)) {
+      put(base + n, st.tokens[b * K + k], t, -1, b * K + k, st.node[b * K + k]);
+      ++n;
+    }
+  for (int head = 0; head < n && n < cnt; ++head) {
+    const int row = base + head, nd = f.node[row];
+    const int e1 = tr.child_off[nd + 1];
+    for (int e = tr.child_off[nd]; e < e1 && n < cnt; ++e) {
+      const int c = tr.child_node[e];
+      if (c >= 0 && c < tr.n_nodes && tr.child_off[c + 1] > tr.child_off[c]) {
+        put(base + n, tr.child_tok[e], f.pos[row] + 1, row, f.root[row], c);
+        ++n;
+      }
+    }
+  }
+  if (n < cnt) {
+    st.error[0] = 3;
+    for (; n < cnt; ++n) put(base + n, st.pad, t, -1, b * K, -1);
+  }
+  // slots: the user's rows of a level (contiguous: the rows are depth-major) take the next cnt slots of that level in the user's
+  // group (even / odd users: a level's slots are cache rows, B * K per position, and a forest level may hold more rows than that)
+  const int grp = b & 1;
+  for (int i = 0; i < cnt;) {
+    const int l = f.pos[base + i] - t;
+    int j = i + 1;
+    while (j < cnt && f.pos[base + j] - t == l) ++j;
+    const bool ok = l >= 0 && l < f.n_levels;
+    const int s0 = ok ? atomicAdd(&f.counts[4 + grp * GRAM_TAIL_MAX_STEPS + l], j - i) : 0;
+    const size_t tab = ((size_t)grp * f.n_levels + (ok ? l : 0)) * f.cap_rows;
+    for (int k = i; k < j; ++k) {
+      const int sl = s0 + (k - i);
+      f.slot[base + k] = ok && sl < f.cap_rows ? sl : -1;
+      if (ok && sl < f.cap_rows) {
+        f.lvl_rows[tab + sl] = base + k;
+        f.lvl_tokens[tab + sl] = f.tokens[base + k];
+      }
+    }
+    i = j;
+  }
+  const int e0 = f.ent_off[b], ne = f.ent_off[b + 1] - e0;
+  for (int e = 0; e < ne; ++e) {
+    f.ent_users[e0 + e] = b;
+    for (int s = 0; s < GRAM_TAIL_ENTRY_ROWS; ++s) {
+      const int i = e * GRAM_TAIL_ENTRY_ROWS + s;
+      f.ent_rows[(size_t)(e0 + e) * GRAM_TAIL_ENTRY_ROWS + s] = i < cnt ? base + i : -1;
+    }
+  }
+}
+
+// The ancestor table of every level (gram_forest_t.lvl_anc), one thread per forest row: column = the row's slot; below t the
+// beam's column of the search's table, from t on the slots of the row's ancestors.  R = cache rows per position = B * K.
+__global__ __launch_bounds__(256) void tail_anc_kernel(gram_beam_state_t st, gram_forest_t f, int t) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int n = f.counts[0], R = st.B * st.K;
+  if (n > f.cap_rows || f.counts[1] > f.cap_entries || i >= n) return;
+  const int l = f.pos[i] - t, s = f.slot[i];
+  if (l < 0 || l >= f.n_levels || s < 0 || s >= R) return;
+  int root = f.root[i];
+  root = root < 0 ? 0 : (root >= R ? R - 1 : root);
+  const int grp = (root / st.K) & 1;  // (the row's user)
+  int32_t* tab = f.lvl_anc + ((size_t)grp * f.n_levels + l) * st.Tmax * R;
+  for (int j = 0; j < t; ++j) tab[(size_t)j * R + s] = st.anc[(size_t)j * R + root];
+  int a = f.parent[i];
+  for (int u = 0; u < GRAM_TAIL_MAX_STEPS && a >= 0 && a < n; ++u) {
+    const int pa = f.pos[a], sa = f.slot[a];
+    if (pa >= t && pa < st.Tmax && sa >= 0 && sa < R) tab[(size_t)pa * R + s] = sa;
+    a = f.parent[a];
+  }
+}
+
+// dst row rows[i] = src row i (gram_scatter_rows): 16 bytes per thread
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const uint4* __restrict__ src, const int32_t* __restrict__ rows,
+                                                           uint4* __restrict__ dst, int n, int row16, int dst_rows) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)n * row16) return;
+  const int r = (int)(g / row16), c = (int)(g % row16);
+  const int d = rows[r];
+  if (d >= 0 && d < dst_rows) dst[(size_t)d * row16 + c] = src[g];
+}
+
+// forest row of every beam for the coming search step (a user's rows are few: a linear scan)
+__global__ __launch_bounds__(256) void tail_rowpos_kernel(gram_beam_state_t st, gram_trie_t tr, gram_forest_t f) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= st.B * st.K) return;
+  const int b = r / st.K;
+  int pos = -1;
+  if (tail_live(st, tr, b, r)) {
+    const int nd = st.node[r], i1 = f.user_off[b + 1];
+    for (int i = f.user_off[b]; i < i1; ++i)
+      if (f.node[i] == nd) {
+        pos = i;
+        break;
+      }
+    if (pos < 0) {  // impossible: every live beam descends from a forest root
+      st.error[0] = 3;
+      pos = 0;
+    }
+  }
+  f.rowpos[r] = pos;
+}
+
 }  // namespace
 
 static int check_state(const gram_beam_state_t* st) {
@@ -1322,6 +1516,48 @@ extern "C" int gram_live_rows(const gram_beam_state_t* st, const gram_trie_t* tr
   if (!tr || !out || !out->rows || !out->rowpos || !out->users || !out->tokens || !out->counts) return GRAM_E_ARG;
   gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
   hipLaunchKernelGGL(live_rows_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, *st, *tr, *out);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+static bool forest_ok(const gram_forest_t* f) {
+  return f && f->tokens && f->pos && f->parent && f->root && f->node && f->user_off && f->ent_off && f->ent_users && f->ent_rows &&
+         f->rowpos && f->counts && f->slot && f->lvl_rows && f->lvl_tokens && f->lvl_anc && f->cap_rows >= 1 && f->cap_entries >= 1 &&
+         f->n_levels >= 1 && f->n_levels <= GRAM_TAIL_MAX_STEPS;
+}
+
+extern "C" int gram_tail_forest(const gram_beam_state_t* st, const gram_trie_t* tr, const gram_trie_tail_t* tail,
+                                const gram_forest_t* forest, int t, void* stream) {
+  if (int e = check_state(st)) return e;
+  if (!tr || !tail || !tail->sub_rows || !forest_ok(forest) || t < 0 || t >= st->Tmax) return GRAM_E_ARG;
+  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
+  hipLaunchKernelGGL(tail_count_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, *st, *tr, *tail, *forest);
+  GRAM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(tail_fill_kernel, dim3((st->B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *st, *tr, *forest, t);
+  GRAM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(tail_anc_kernel, dim3((forest->cap_rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, *st, *forest, t);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int gram_scatter_rows(const void* src, const int32_t* rows, void* dst, int n, int row_bytes, int dst_rows, void* stream) {
+  if (!src || !rows || !dst || n < 1 || row_bytes < 16 || (row_bytes & 15) || dst_rows < 1 ||
+      ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15))
+    return GRAM_E_ARG;
+  const int row16 = row_bytes / 16;
+  const long total = (long)n * row16;
+  gram_prof::Scope prof(GRAM_K_ROWOPS, (hipStream_t)stream, 2.0 * n * row_bytes);
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)src, rows,
+                     (uint4*)dst, n, row16, dst_rows);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int gram_tail_rowpos(const gram_beam_state_t* st, const gram_trie_t* tr, const gram_forest_t* forest, void* stream) {
+  if (int e = check_state(st)) return e;
+  if (!tr || !forest_ok(forest)) return GRAM_E_ARG;
+  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
+  hipLaunchKernelGGL(tail_rowpos_kernel, dim3((st->B * st->K + 255) / 256), dim3(256), 0, (hipStream_t)stream, *st, *tr, *forest);
   GRAM_CHECK_LAUNCH();
   return 0;
 }

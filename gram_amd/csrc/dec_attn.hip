@@ -50,7 +50,9 @@ __device__ __forceinline__ f32x4 xa_merge_o(f32x4 o0, f32x4 o1, float w0, float 
 
 // NT = 16-beam tiles; LIVE: live-row step (gram_live_rows_t); S = bf16 pieces; NW = waves per workgroup (1: a wave owns the whole
 // (user, head) and nothing is merged)
-template <int NT, bool LIVE, int S, int NW>
+// ENT: the entry form of the tail pass (gram_cross_attn_entries_split) -- the row table is indexed by the workgroup row, not by the
+// user, so that a user may own several workgroup rows
+template <int NT, bool LIVE, int S, int NW, bool ENT = false>
 __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     const p16* __restrict__ q, const p16* __restrict__ kbank, const p16* __restrict__ vtbank,
     const uint8_t* __restrict__ mask, p16* __restrict__ out, int K, int H, int Sk, const int32_t* __restrict__ users,
@@ -68,6 +70,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   // live-row step (users != NULL): workgroup y serves user users[y]; q/out rows are the compact rows rowpos[b*K + beam]
   // (-1 = beam not live: zero query, nothing stored)
   const int h = blockIdx.x, b = LIVE ? users[blockIdx.y] : blockIdx.y;
+  const int rb = ENT ? (int)blockIdx.y : b;  // whose slots of the row table this workgroup serves
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, g = lane >> 4;
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   // instructions only
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    const int qrow = xa_row<LIVE>(b, K, 16 * nt + c, rowpos);
+    const int qrow = xa_row<LIVE>(rb, K, 16 * nt + c, rowpos);
 #pragma unroll
     for (int pc = 0; pc < S; ++pc)
 #pragma unroll
@@ -306,7 +309,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
       lt += __shfl_xor(lt, 16, 64);
       lt += __shfl_xor(lt, 32, 64);
       const float inv = 1.f / lt;
-      const int orow = xa_row<LIVE>(b, K, 16 * nt + c, rowpos);
+      const int orow = xa_row<LIVE>(rb, K, 16 * nt + c, rowpos);
       if (orow >= 0) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) xa_store<S>(out, orow, inner, h * 64 + 16 * mt + 4 * g, o[mt][nt] * inv);
@@ -337,7 +340,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     xa_merge_w(sm_m[beam], sm_m[NB + beam], sm_l[beam], sm_l[NB + beam], w0, w1, inv2);
     const f32x4 v = xa_merge_o(*reinterpret_cast<const f32x4*>(sm_o + ((size_t)beam) * 64 + d4),
                          *reinterpret_cast<const f32x4*>(sm_o + ((size_t)(NB + beam)) * 64 + d4), w0, w1, inv2);
-    int orow = b * K + beam;  // (beam < K here; through xa_row() hipcc keeps the comparison and reschedules the merge)
+    int orow = rb * K + beam;  // (beam < K here; through xa_row() hipcc keeps the comparison and reschedules the merge)
     if constexpr (LIVE) orow = rowpos[orow];
     if (orow >= 0) xa_store<S>(out, orow, inner, h * 64 + d4, v);
   }
@@ -393,6 +396,29 @@ int launch_cross_nt(const XaLaunch& a) {
     case 3: return launch_cross<3, S>(a);
     default: return launch_cross<4, S>(a);
   }
+}
+
+// The entry form of the tail pass: four row tiles per entry whatever the entry holds (a forest's rows per user are not known on the
+// host); NW is what launch_cross picks for the search's K beams, because the split of the keys over the waves is part of a row's bits.
+template <int S, int NW>
+int launch_cross_entries(const XaLaunch& a) {
+  constexpr int NT = 4, NB = NT * 16;
+  static_assert(NB == GRAM_TAIL_ENTRY_ROWS, "an entry's row table (gram_forest_t.ent_rows) is indexed by the kernel's padded row count");
+  constexpr int stages = NW * S * 2 * XA_TILE, merge = NW == 1 ? 0 : (2 * NW * NB + NW * NB * 64) * 4;
+  constexpr int smem = stages > merge ? stages : merge;
+  static_assert(smem <= 160 * 1024, "the stages do not fit the LDS");
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_kernel<NT, true, S, NW, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((cross_attn_kernel<NT, true, S, NW, true>), dim3(a.H, a.B), dim3(NW * 64), smem, a.st, (const p16*)a.q,
+                     (const p16*)a.k, (const p16*)a.vt, a.mask, (p16*)a.out, NB, a.H, a.Sk, a.users, a.rowpos, a.q_ps, a.bank_ps,
+                     a.key_bits);
+  GRAM_CHECK_LAUNCH();
+  return 0;
 }
 
 // key_bits[b][st] bit j = mask[b][32 st + j] != 0 (st < S/32 <= 128; rows are 128 words apart): the cross-attention's view of
@@ -511,6 +537,25 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const p16* __restric
 }
 
 }  // namespace
+
+extern "C" int gram_cross_attn_entries_split(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out,
+                                             int n_entries, int K, int H, int S, const int32_t* ent_users, const int32_t* ent_rows,
+                                             int pieces, int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits,
+                                             void* stream) {
+  if (!q || !out || !ent_users || !ent_rows || n_entries < 1 || K < 1 || K > GRAM_MAX_BEAMS || H < 1 || S < 32 || (S & 31) ||
+      S > 4096 || pieces < 1 || pieces > GRAM_MAX_PIECES)
+    return GRAM_E_ARG;
+  if (pieces > 1 && (q_pstride < 1 || bank_pstride < (int64_t)H * S * 64)) return GRAM_E_ARG;
+  if ((reinterpret_cast<uintptr_t>(mask) & 15) || (reinterpret_cast<uintptr_t>(k_layer) & 15) || (reinterpret_cast<uintptr_t>(vt_layer) & 15))
+    return GRAM_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  gram_prof::Scope prof(GRAM_K_CROSS_ATTN, st, 4.0 * n_entries * H * S * 64 * pieces);  // K + V^T, every piece, per entry
+  const XaLaunch a{q, k_layer, vt_layer, mask, out, n_entries, GRAM_TAIL_ENTRY_ROWS, H, S, ent_users, ent_rows, (long)q_pstride,
+                   (long)bank_pstride, key_bits, st};
+  const bool one_wave = (K + 15) / 16 >= 3;  // launch_cross's choice for K beams
+  if (pieces == 2) return one_wave ? launch_cross_entries<2, 1>(a) : launch_cross_entries<2, 2>(a);
+  return one_wave ? launch_cross_entries<1, 1>(a) : launch_cross_entries<1, 2>(a);
+}
 
 extern "C" int gram_mask_key_bits(const uint8_t* mask, uint32_t* key_bits, int B, int S, void* stream) {
   if (!mask || !key_bits || B < 1 || S < 32 || (S & 31) || S > 4096 || (reinterpret_cast<uintptr_t>(mask) & 15)) return GRAM_E_ARG;

@@ -90,6 +90,11 @@ struct Workspace {
   float* xa_scratch;   // such a handle only: the long cross-attention's partials (gram_cross_attn_long_scratch_bytes)
   int32_t* rowmap;     // teacher-forced pass only: gram_cross_attn_rows_split's row tables [B * (1 + 2 * GRAM_MAX_BEAMS)]
   int64_t bytes;
+  // the tail pass (gram_generate_tail; carve_tail): the forest and its decoder rows, BEHIND `bytes` -- nothing above moves
+  gram_forest_t forest;
+  Rows tail;
+  float *tail_lse, *tail_lse_part;
+  int64_t tail_bytes;  // 0: not carved
   // two-piece mode (gram_split_t): what a GEMM reads (h, attn, u) is ONE interleaved buffer of twice the row length;
   // what only attention kernels read (qkv, qx, the bank, the cache) is `pieces` planar copies, these many elements apart
   int pieces;
@@ -176,6 +181,43 @@ Workspace carve(const gram_model* m, void* ws, int B, int N, int L, int K, int T
   take_key_bits(cv, w, m, B, R, N * L);
   w.bytes = (cv.off + 255) & ~(int64_t)255;
   return w;
+}
+
+// The forest of the tail pass behind a carve()d workspace: capacity 5/4 * B * K * steps rows (measured on the bench: 0.81 * B * K *
+// steps on average over 4096 users, 0.93 for the largest user -- which is what a call of one user needs: 80 of its 125 at B = 1), one cross-attention entry per 64 rows of a
+// user (so at most cap_rows / 64 + B), the decoder's per-row buffers for that many rows and their LSE partials.
+void carve_tail(const gram_model* m, void* ws, Workspace& w, int B, int K, int steps) {
+  const gram_model_desc_t& c = m->d;
+  const int64_t V = c.vocab, R = (int64_t)B * K;
+  Carve cv(ws);
+  cv.off = w.bytes;
+  const int64_t cap = (5 * R * steps + 3) / 4, ents = cap / GRAM_TAIL_ENTRY_ROWS + B;
+  gram_forest_t& f = w.forest;
+  f.cap_rows = (int32_t)cap;
+  f.cap_entries = (int32_t)ents;
+  f.tokens = cv.take<int32_t>(cap);
+  f.pos = cv.take<int32_t>(cap);
+  f.parent = cv.take<int32_t>(cap);
+  f.root = cv.take<int32_t>(cap);
+  f.node = cv.take<int32_t>(cap);
+  f.user_off = cv.take<int32_t>(B + 1);
+  f.ent_off = cv.take<int32_t>(B + 1);
+  f.ent_users = cv.take<int32_t>(ents);
+  f.ent_rows = cv.take<int32_t>(ents * GRAM_TAIL_ENTRY_ROWS);
+  f.rowpos = cv.take<int32_t>(R);
+  f.counts = cv.take<int32_t>(4 + 2 * GRAM_TAIL_MAX_STEPS);
+  f.n_levels = steps;
+  f.slot = cv.take<int32_t>(cap);
+  f.lvl_rows = cv.take<int32_t>(2 * cap * steps);
+  f.lvl_tokens = cv.take<int32_t>(2 * cap * steps);
+  f.lvl_anc = cv.take<int32_t>(2 * (int64_t)steps * GRAM_MAX_DEC_LEN * R);
+  w.tail = take_rows(cv, c, w.pieces, cap, true);
+  w.tail_lse = cv.take<float>(cap);
+  w.tail_lse_part = cv.take<float>(cap * (V / 64) * 2);
+  w.tail_bytes = (cv.off + 255) & ~(int64_t)255;
+}
+inline bool tail_shape_ok(int B, int K, int steps) {
+  return steps >= 1 && steps <= GRAM_TAIL_MAX_STEPS && 5 * (int64_t)B * K * steps / 4 + 1 <= INT32_MAX / 4;
 }
 
 int check_shapes(const gram_model* m, int B, int N, int L, int K, int Tmax) {
@@ -513,7 +555,117 @@ int search_step(const gram_model* m, const Workspace& w, const gram_trie_t* trie
   return gram_beam_step_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.d_model, w.lse, c.vocab, cur_len, rows_per_user, st);
 }
 
+// The tail pass (gram_generate_tail): decode_step's layers ONCE over the n_rows rows of the forest in w.forest -- embedding by row
+// token, layer 0's q|k|v from the token table as decode_step reads it, the forest self-attention over cache and in-pass ancestors,
+// the cross-attention per entry of <= 64 rows -- then the lm_head with its LSE partials.  `w` is the call's workspace with w.dec /
+// w.lse / w.lse_part pointing at the forest's buffers (tail_view), so the replayed search steps read them like any step's.
+int tail_pass(const gram_model* m, const Workspace& w, const uint8_t* mask, int B, int N, int L, int K, int Tmax, int t0, int n_rows,
+              int n_entries, const int32_t* lvl_n, void* st) {
+  const gram_model_desc_t& c = m->d;
+  const int inner = c.n_heads * 64, H = c.n_heads, S = N * L, R = B * K;
+  const size_t bank_layer = (size_t)B * H * S * 64;
+  const size_t cache_layer = (size_t)Tmax * R * inner;
+  const Rows& r = w.dec;
+  const gram_forest_t& f = w.forest;
+  const p16* const table = token_table(m, m->dec_qkv0, GRAM_STAGE_DEC_SELF);
+  // levels the call's steps can read (a max_length that ends inside the tail leaves the deeper rows without attention)
+  int nlev = f.n_levels, cut = 0;
+  for (int g = 0; g < 2; ++g)
+    for (int l = 0; l < f.n_levels; ++l)
+      if (lvl_n[g * GRAM_TAIL_MAX_STEPS + l] > 0 && t0 + l >= Tmax - 1) cut = 1, nlev = l < nlev ? l : nlev;
+  TRY(decoder_layers(
+      m, w, f.tokens, n_rows, table != nullptr,
+      [&](int i) {
+        // The step-wise kernel, level by level: the level's rows gathered by slot (qkv_rows), their k and v written to the cache rows
+        // of that position (no step reads them any more), the result -- compact, in the cross-attention's query buffer, free until its
+        // GEMM -- put back by row.
+        if (cut) {
+          hipError_t e = hipMemsetAsync(r.attn, 0, (size_t)n_rows * inner * w.pieces * sizeof(p16), (hipStream_t)st);
+          if (e != hipSuccess) return (int)e;
+        }
+        // (two groups of users, one after the other: the second reuses the first's cache rows, which nothing reads any more)
+        for (int g = 0; g < 2; ++g)
+          for (int l = 0; l < nlev; ++l) {
+            const int n = lvl_n[g * GRAM_TAIL_MAX_STEPS + l];
+            if (n < 1) continue;
+            const size_t tab = ((size_t)g * f.n_levels + l) * f.cap_rows;
+            const int32_t* const rows_l = f.lvl_rows + tab;
+            const int32_t* const anc_l = f.lvl_anc + ((size_t)g * f.n_levels + l) * Tmax * R;
+            if (i == 0 && table)
+              TRY(gram_dec_self_attn_rows_split(table, f.lvl_tokens + tab, w.kcache, w.vcache, anc_l, c.dec_bias_f32, r.qx, R, n, nullptr, H,
+                                                t0 + l, Tmax, w.pieces, (int64_t)c.vocab * 3 * inner, w.ps_cache, st));
+            else
+              TRY(gram_dec_self_attn_rows_split(r.qkv, rows_l, w.kcache + i * cache_layer, w.vcache + i * cache_layer, anc_l, c.dec_bias_f32,
+                                                r.qx, R, n, nullptr, H, t0 + l, Tmax, w.pieces, r.ps_qkv, w.ps_cache, st));
+            TRY(gram_scatter_rows(r.qx, rows_l, r.attn, n, inner * w.pieces * (int)sizeof(p16), n_rows, st));
+          }
+        return 0;
+      },
+      [&](int i) {
+        return gram_cross_attn_entries_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, n_entries, K, H, S,
+                                             f.ent_users, f.ent_rows, w.pieces, r.ps_qx, w.ps_bank, w.key_bits, st);
+      },
+      st));
+  TRY(lm_head(m, w, n_rows, nullptr, w.lse_part, st));
+  return gram_lse_combine(w.lse_part, w.lse, n_rows, c.vocab / 64, st);
+}
+Workspace tail_view(const Workspace& w) {
+  Workspace v = w;
+  v.dec = w.tail;
+  v.lse = w.tail_lse;
+  v.lse_part = w.tail_lse_part;
+  return v;
+}
+
+int g_tail_pass = -1;  // -1: the GRAM_TAIL_PASS environment variable decides (default on)
+int g_tail_cap = 0;    // gram_debug_set_tail_capacity
+int g_tail_level_cap = 0;  // gram_debug_set_tail_level_capacity
+int32_t g_tail_last[4] = {0, 0, 0, 0};  // gram_debug_tail_last
+// Which calls take the pass by default.  Measured (profiles/tail_pass_bench_ab.txt) the pass is faster at every batch tried -- B = 1:
+// 17.5 -> 13.3 ms per generate, 64: 52.3 -> 44.5, 256: 110.3 -> 104.3, 4096: -33 ms -- so this is NOT a performance crossover.  The
+// limit is there because the suite's tests of small calls pin the step-wise train (launches per kind, rows per GEMM, rows per
+// self-attention step), and a default that replaced that train under them would need most of them rewritten.  So by default the
+// pass is taken where one layer's bank holds 256 MB or more (large evaluation batches; the bench's holds 9.66 GB);
+// GRAM_TAIL_PASS=1 or gram_debug_set_tail_pass(1) takes it at any size, which is what a latency-bound caller wants.
+constexpr double kTailMinBankBytes = 256.0 * 1024 * 1024;
+bool tail_wanted(const gram_model* m, int B, int N, int L) {
+  if (g_tail_pass >= 0) return g_tail_pass != 0;  // (forced either way)
+  const char* e = getenv("GRAM_TAIL_PASS");
+  if (e && e[0] == '0') return false;
+  if (e && e[0] == '1') return true;
+  const int P = m->d.pieces > 1 ? m->d.pieces : 1;
+  return 4.0 * B * m->d.n_heads * N * L * 64 * P >= kTailMinBankBytes;  // K + V^T, 16 bits, every piece
+}
+
 }  // namespace
+
+extern "C" int gram_debug_set_tail_pass(int on) {
+  g_tail_pass = on;
+  return 0;
+}
+extern "C" int gram_tail_pass_wanted(const gram_model_t* m, int B, int N, int L) {
+  if (!m || B < 1 || N < 1 || L < 1) return GRAM_E_ARG;
+  return tail_wanted(m, B, N, L) ? 1 : 0;
+}
+extern "C" int gram_debug_set_tail_capacity(int rows) {
+  g_tail_cap = rows < 0 ? 0 : rows;
+  return 0;
+}
+extern "C" int gram_debug_workspace_beam_state(const gram_model_t* m, void* workspace, int B, int N, int L, int K, int max_length,
+                                               gram_beam_state_t* out) {
+  if (!workspace || !out || check_shapes(m, B, N, L, K, max_length)) return GRAM_E_ARG;
+  *out = carve(m, workspace, B, N, L, K, max_length).beam;
+  return 0;
+}
+extern "C" int gram_debug_set_tail_level_capacity(int rows) {
+  g_tail_level_cap = rows < 0 ? 0 : rows;
+  return 0;
+}
+extern "C" int gram_debug_tail_last(int32_t* out4) {
+  if (!out4) return GRAM_E_ARG;
+  memcpy(out4, g_tail_last, sizeof(g_tail_last));
+  return 0;
+}
 
 extern "C" int gram_abi_version(void) { return GRAM_ABI_VERSION; }
 extern "C" int gram_piece_format(void) { return GRAM_PIECE_FORMAT; }
@@ -740,7 +892,7 @@ namespace {
 // launch cost, and a captured train cannot take the live-row step, whose row counts travel through the host -- and removed in round 4.)
 int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                   int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
-                  int64_t* sequences, float* scores, void* stream) {
+                  const gram_trie_tail_t* tail, int64_t* sequences, float* scores, void* stream) {
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
   TRY(gram_beam_init(&w.beam, trie, /*decoder_start_token_id=*/0, stream));
   if (K == 1) {  // HF: num_beams == 1 -> greedy_search (raw logits, no hypotheses, no scores)
@@ -756,9 +908,43 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
       return !(e && e[0] == '0');
     }();
     const bool live_rows = g_live_rows < 0 ? live_rows_env : g_live_rows != 0;  // (the live-row step needs a host round trip)
+    // The tail pass (tail != NULL: generate_call carved its buffers): at step t_tail the beams hold d_tail tokens, and every decoder
+    // state the remaining steps can ask for is a row of the forest below them.  One pass computes them all; the steps from t_tail on
+    // are then search steps alone, each beam reading the forest row of its node.  A forest over capacity (or an empty one) leaves
+    // the loop as it is.  The forest's counts (rows, entries, rows per group and level: 144 bytes) cost the call one host round
+    // trip -- a hipStreamSynchronize of its own: at t_tail the loop makes no live-row read the counts could ride in.
+    const int t_tail = tail ? tail->d_tail - 1 : -1;
+    bool replay = false;
+    Workspace wt = w;
+    if (tail) {
+      wt = tail_view(w);
+      if (g_tail_cap > 0 && g_tail_cap < wt.forest.cap_rows) wt.forest.cap_rows = g_tail_cap;
+    }
     // fixed max_length-1 steps: finished users are padded exactly as BeamSearchScorer.process
     // pads them, so skipping HF's all-done early exit changes nothing and needs no host sync
     for (int t = 0; t + 1 < max_length; ++t) {
+      if (t == t_tail) {
+        int32_t counts[4 + 2 * GRAM_TAIL_MAX_STEPS] = {0};
+        TRY(gram_tail_forest(&w.beam, trie, tail, &wt.forest, t, stream));
+        hipError_t e = hipMemcpyAsync(counts, wt.forest.counts, sizeof(counts), hipMemcpyDeviceToHost, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+        if (e != hipSuccess) return (int)e;
+        if (counts[0] < 0 || counts[1] < 0) return GRAM_E_BEAM;
+        g_tail_last[1] = counts[0], g_tail_last[2] = counts[1], g_tail_last[3] = counts[2];
+        bool fits = counts[0] >= 1 && counts[0] <= wt.forest.cap_rows && counts[1] >= 1 && counts[1] <= wt.forest.cap_entries;
+        const int level_cap = g_tail_level_cap > 0 && g_tail_level_cap < B * K ? g_tail_level_cap : B * K;  // (slots are cache rows)
+        for (int l = 0; l < 2 * GRAM_TAIL_MAX_STEPS; ++l) fits = fits && counts[4 + l] >= 0 && counts[4 + l] <= level_cap;
+        if (fits) {
+          TRY(tail_pass(m, wt, mask, B, N, L, K, max_length, t, counts[0], counts[1], counts + 4, stream));
+          replay = true;
+          g_tail_last[0] = 1;
+        }
+      }
+      if (replay) {
+        TRY(gram_tail_rowpos(&w.beam, trie, &wt.forest, stream));
+        TRY(search_step(m, wt, trie, t + 1, K, wt.forest.rowpos, nullptr, stream));
+        continue;
+      }
       // step 0: every beam of a user holds the same start token and an empty cache, so the decoder,
       // the cross-attention and the lm_head run on ONE row per user (HF runs K identical rows);
       // gram_beam_step reads that shared row and points every beam's slot-0 ancestor at it
@@ -800,15 +986,28 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
 // gram_generate_ex and gram_generate_items (items: the per-user item filters, NULL for gram_generate_ex)
 static int generate_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                          int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp,
-                         const gram_user_items_t* items, void* workspace, int64_t workspace_bytes, int64_t* sequences, float* scores,
-                         int32_t* width_host, void* stream) {
+                         const gram_user_items_t* items, const gram_trie_tail_t* tail, void* workspace, int64_t workspace_bytes,
+                         int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
   TRY(check_shapes(m, B, N, L, K, max_length));
   TRY(check_compaction(comp, B, N));
   if (!trie || nret < 1 || nret > K || !sequences || (!scores && K != 1)) return GRAM_E_ARG;
   Workspace w = carve(m, workspace, B, N, L, K, max_length);
   if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
+  // the tail pass where the Trie has a tail inside this call's steps and the call is one it covers (beam search, no item filters,
+  // the short cross-attention); everything else is the step-wise train, launch for launch
+  memset(g_tail_last, 0, sizeof(g_tail_last));  // (gram_debug_tail_last speaks of the last generate call of any kind)
+  if (tail) {
+    const bool on = tail->d_tail >= 2 && tail->d_tail < max_length && tail->sub_rows && K > 1 && !items && !m->long_xattn() &&
+                    tail_shape_ok(B, K, tail->steps) && tail_wanted(m, B, N, L);
+    if (on) {
+      carve_tail(m, workspace, w, B, K, tail->steps);
+      if (workspace_bytes < w.tail_bytes) return GRAM_E_WORKSPACE;
+    } else {
+      tail = nullptr;
+    }
+  }
   w.beam.length_penalty = length_penalty;
-  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, sequences, scores, stream));
+  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, sequences, scores, stream));
   if (width_host) {
     int32_t host[2] = {0, 0};
     hipError_t e = hipMemcpyAsync(&host[0], w.width, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -826,8 +1025,23 @@ extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids,
                                 int nret, int max_length, float length_penalty, const gram_trie_t* trie,
                                 const gram_compaction_t* comp, void* workspace, int64_t workspace_bytes, int64_t* sequences,
                                 float* scores, int32_t* width_host, void* stream) {
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, workspace, workspace_bytes,
-                       sequences, scores, width_host, stream);
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, nullptr, workspace,
+                       workspace_bytes, sequences, scores, width_host, stream);
+}
+
+extern "C" int64_t gram_workspace_bytes_tail(const gram_model_t* m, int B, int N, int L, int K, int max_length, int steps) {
+  if (check_shapes(m, B, N, L, K, max_length) || !tail_shape_ok(B, K, steps)) return GRAM_E_ARG;
+  Workspace w = carve(m, nullptr, B, N, L, K, max_length);
+  carve_tail(m, nullptr, w, B, K, steps);
+  return w.tail_bytes;
+}
+
+extern "C" int gram_generate_tail(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
+                                  int nret, int max_length, float length_penalty, const gram_trie_t* trie,
+                                  const gram_compaction_t* comp, const gram_trie_tail_t* tail, void* workspace,
+                                  int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, tail, workspace,
+                       workspace_bytes, sequences, scores, width_host, stream);
 }
 
 extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
@@ -837,8 +1051,8 @@ extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_i
   if (!items || !items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
       items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW))
     return GRAM_E_ARG;
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, workspace, workspace_bytes,
-                       sequences, scores, width_host, stream);
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
+                       workspace_bytes, sequences, scores, width_host, stream);
 }
 
 // ---- teacher-forced decoder pass (gram_teacher_forced) -----------------------------------------------------------------------------

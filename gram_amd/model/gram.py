@@ -167,6 +167,7 @@ class GRAM(nn.Module):
         self._packed = None  # (device, version, handle, keepalive)
         self._version = 0
         self._workspace = None
+        self._tail_no_fit = set()  # shapes whose tail-pass workspace did not fit the device (_tail_workspace)
         self._tries: Dict[int, tuple] = {}  # id(trie) -> (trie, FlatTrie)
         # The reference computes in fp32; "f16x3" (two IEEE-half pieces per value, three MFMA products per product) is the cheapest
         # arithmetic that keeps Recall@5 / NDCG@5 within 1e-4 of it, so it is what a drop-in model starts in.
@@ -840,6 +841,39 @@ class GRAM(nn.Module):
             )
         return self._ensure_workspace(need)
 
+    def _tail_workspace(self, handle, B, N, L, K, max_length, steps) -> Optional[torch.Tensor]:
+        """The workspace of a tail-pass call (gram_workspace_bytes_tail), or None where the device cannot hold it: the call then
+        decodes step by step on the step-wise workspace.  The current workspace is given up only when the larger one is known to
+        fit -- what the driver reports free, plus what PyTorch's allocator holds unused, plus the current workspace itself, less a
+        margin -- and a shape that did not fit is remembered (with a one-time warning), so that a runner whose batch was sized without
+        the forest's rows does not free and re-allocate most of the HBM on every call."""
+        key = (int(handle), B, N, L, K, max_length, steps)
+        if key in self._tail_no_fit:
+            return None
+        dev = self._device()
+        need = int(_lib.load().gram_workspace_bytes_tail(handle, B, N, L, K, max_length, steps))
+        if need <= 0:
+            return None
+        cur = self._workspace if self._workspace is not None and self._workspace.device == dev else None
+        if cur is not None and cur.numel() >= need:
+            return cur
+        free, _total = torch.cuda.mem_get_info(dev)
+        unused = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        room = free + unused + (cur.numel() if cur is not None else 0)
+        if need + self._TAIL_FIT_MARGIN <= room:
+            try:
+                return self._ensure_workspace(need)
+            except torch.cuda.OutOfMemoryError:
+                pass
+        self._tail_no_fit.add(key)
+        import warnings
+        warnings.warn(f"generate: the tail pass needs a workspace of {need / 2**30:.1f} GiB at B={B}, which does not fit this device "
+                      f"next to what it holds; decoding step by step (size the batch with max_users_per_call(..., "
+                      f"prefix_allowed_tokens_fn=fn))")
+        return None
+
+    _TAIL_FIT_MARGIN = 512 * 2**20  # (outputs and small temporaries of the call itself)
+
     def _ensure_workspace(self, need: int) -> torch.Tensor:
         dev = self._device()
         if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
@@ -849,11 +883,33 @@ class GRAM(nn.Module):
             self._workspace = torch.empty(int(need), dtype=torch.uint8, device=dev)
         return self._workspace
 
-    def max_users_per_call(self, N: int, L: int, K: int, max_length: int, limit: int = 4096, headroom: float = 0.9) -> int:
-        """Largest batch B <= limit whose ``generate`` workspace (gram_workspace_bytes) fits the device's free HBM: what the runners
-        size their GPU batches with, whatever ``--eval_batch_size`` the loader was built with (results do not depend on the batch a
-        user is scored in).  Memory held by this model's current workspace counts as free (it is re-used or replaced); the handle's
-        token tables (_build_token_tables) are allocated by the time the free memory is read, so they are already subtracted."""
+    def _tail_plan(self, fn, K: int, max_length: int, filtered: bool = False):
+        """(d_tail, steps) of the Trie behind ``fn`` where a ``generate`` of this kind can take the tail pass (gram_generate_tail) at
+        some batch size, else (0, 0): beam search on a Trie closure, no item filters, the short cross-attention, a tail inside the
+        call's steps.  Whether a given batch takes it is gram_tail_pass_wanted's answer for that shape."""
+        if fn is None or K <= 1 or filtered or self._max_fused_tokens > _lib.GRAM_MAX_FUSED_LEN or self._closure_trie(fn) is None:
+            return 0, 0
+        _sub, d_tail, steps = self._flat_trie(fn).tail_tables()
+        if not (2 <= d_tail < int(max_length) and 1 <= steps <= _lib.GRAM_TAIL_MAX_STEPS):
+            return 0, 0
+        return d_tail, steps
+
+    def _generate_bytes(self, handle, B: int, N: int, Lp: int, K: int, max_length: int, tail_steps: int) -> int:
+        """workspace of one ``generate``: gram_workspace_bytes, or gram_workspace_bytes_tail where the call would take the tail pass"""
+        lib = _lib.load()
+        if tail_steps > 0 and lib.gram_tail_pass_wanted(handle, B, N, Lp) == 1:
+            return int(lib.gram_workspace_bytes_tail(handle, B, N, Lp, K, max_length, tail_steps))
+        return int(lib.gram_workspace_bytes(handle, B, N, Lp, K, max_length))
+
+    def max_users_per_call(self, N: int, L: int, K: int, max_length: int, limit: int = 4096, headroom: float = 0.9,
+                           prefix_allowed_tokens_fn: Optional[Callable] = None) -> int:
+        """Largest batch B <= limit whose ``generate`` workspace fits the device's free HBM: what the runners size their GPU batches
+        with, whatever ``--eval_batch_size`` the loader was built with (results do not depend on the batch a user is scored in).
+        With ``prefix_allowed_tokens_fn`` (the Trie closure the calls will search) the workspace is the one those calls ask for: where
+        the Trie has a tail and a batch is large enough to take the tail pass, gram_workspace_bytes_tail (the forest's rows, about a
+        tenth more) -- a batch sized without them would never fit the pass and decode step by step.  Memory held by this model's
+        current workspace counts as free (it is re-used or replaced); the handle's token tables (_build_token_tables) are allocated
+        by the time the free memory is read, so they are already subtracted."""
         self._check_fused_len(N, L)
         handle = self._pack()
         lib = _lib.load()
@@ -865,11 +921,12 @@ class GRAM(nn.Module):
             free += self._workspace.numel()
         budget = int(free * headroom)
         lo, hi = 1, max(1, int(limit))
-        if lib.gram_workspace_bytes(handle, hi, N, Lp, K, max_length) <= budget:
+        steps = self._tail_plan(prefix_allowed_tokens_fn, K, max_length)[1]
+        if 0 <= self._generate_bytes(handle, hi, N, Lp, K, max_length, steps) <= budget:
             return hi
-        while lo < hi:  # workspace bytes grow monotonically with B
+        while lo < hi:  # workspace bytes grow monotonically with B (the tail's bytes come in at the size rule's batch and stay)
             mid = (lo + hi + 1) // 2
-            need = lib.gram_workspace_bytes(handle, mid, N, Lp, K, max_length)
+            need = self._generate_bytes(handle, mid, N, Lp, K, max_length, steps)
             if 0 <= need <= budget:
                 lo = mid
             else:
@@ -1163,7 +1220,15 @@ class GRAM(nn.Module):
             items = self._user_item_lists(allowed_items if allow else exclude_items, allow, B, flat, candidates, dev)
         comp, harvest_plan = self._plan(ids, mask, B, N, Lp)
         _ctrie, (t_off, t_tok, t_node) = flat.to_device(dev)
-        ws = self._get_workspace(handle, B, N, Lp, K, int(max_length))
+        # the tail pass (gram_generate_tail; taken by size, GRAM_TAIL_PASS=0 switches it off: gram_tail_pass_wanted): where the Trie has a tail inside this call's
+        # steps, the workspace grows by the forest's rows (gram_workspace_bytes_tail); a device that cannot hold them decodes step by
+        # step -- the same results
+        d_tail, tail_steps = self._tail_plan(prefix_allowed_tokens_fn, K, int(max_length), filtered)
+        tail = tail_steps > 0 and _lib.load().gram_tail_pass_wanted(handle, B, N, Lp) == 1
+        ws = self._tail_workspace(handle, B, N, Lp, K, int(max_length), tail_steps) if tail else None
+        tail = ws is not None
+        if ws is None:
+            ws = self._get_workspace(handle, B, N, Lp, K, int(max_length))
         if K == 1 and nret != 1:
             raise ValueError("num_return_sequences must be 1 for greedy search (num_beams == 1), as in HF generate")
         ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
@@ -1177,7 +1242,8 @@ class GRAM(nn.Module):
             seqs, scores, width = torch.ops.gram.generate_items(*args, leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items,
                                                                 allow)
         else:
-            seqs, scores, width = torch.ops.gram.generate(*args)
+            seqs, scores, width = torch.ops.gram.generate(*args, flat.tail_rows_on(dev) if tail else None, d_tail if tail else 0,
+                                                          tail_steps if tail else 0)
         if harvest_plan is not None:
             self._harvest_from_workspace(harvest_plan, ws, handle, B, N, Lp, K, int(max_length))
         seqs = seqs[:, : int(width[0])]

@@ -63,10 +63,12 @@ def generate(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: 
              trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
              num_return_sequences: int, max_length: int, length_penalty: float, comp_map: Optional[Tensor],
              comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor],
-             n_cached: int, cache_L: int) -> Tuple[Tensor, Tensor, Tensor]:
+             n_cached: int, cache_L: int, trie_sub_rows: Optional[Tensor] = None, trie_d_tail: int = 0,
+             trie_tail_steps: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
     """input_ids i64 (B,N,L), attention_mask u8 (B,N,L), ``handle`` a gram_model_t* as int, ``workspace`` a u8 scratch tensor of
     gram_workspace_bytes; the Trie as its CSR arrays (gram_trie_t); comp_* / cache_* the gram_compaction_t fields (None = off).
-    Returns (sequences i64 (B*nret, max_length), sequences_scores f32 (B*nret) -- empty for greedy search --, width i32 (1,))."""
+    trie_sub_rows i32 (n_nodes,) / trie_d_tail / trie_tail_steps: the Trie's tail tables (gram_trie_tail_t, ``FlatTrie.tail_tables``);
+    given, the call is gram_generate_tail and ``workspace`` must hold gram_workspace_bytes_tail.  Returns (sequences i64 (B*nret, max_length), sequences_scores f32 (B*nret) -- empty for greedy search --, width i32 (1,))."""
     lib = _lib.load()
     B, N, L = input_ids.shape
     dev = input_ids.device
@@ -80,11 +82,21 @@ def generate(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: 
     seqs = torch.empty(B * nret, max_length, dtype=torch.int64, device=dev)
     scores = torch.empty(B * nret if K > 1 else 0, dtype=torch.float32, device=dev)
     width = C.c_int32(0)
+    tail = None
+    if trie_sub_rows is not None and trie_d_tail > 0:
+        _check("trie_sub_rows", trie_sub_rows, torch.int32, (trie_child_off.numel() - 1,), dev)
+        tail = _lib.TrieTail(trie_sub_rows.data_ptr(), int(trie_d_tail), int(trie_tail_steps))
     with torch.cuda.device(dev):
-        rc = lib.gram_generate_ex(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length,
-                                  float(length_penalty), C.byref(trie), C.byref(comp) if comp is not None else None,
-                                  workspace.data_ptr(), workspace.numel(), seqs.data_ptr(), scores.data_ptr() if K > 1 else None,
-                                  C.byref(width), _stream(input_ids))
+        if tail is not None:
+            rc = lib.gram_generate_tail(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length,
+                                        float(length_penalty), C.byref(trie), C.byref(comp) if comp is not None else None,
+                                        C.byref(tail), workspace.data_ptr(), workspace.numel(), seqs.data_ptr(),
+                                        scores.data_ptr() if K > 1 else None, C.byref(width), _stream(input_ids))
+        else:
+            rc = lib.gram_generate_ex(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length,
+                                      float(length_penalty), C.byref(trie), C.byref(comp) if comp is not None else None,
+                                      workspace.data_ptr(), workspace.numel(), seqs.data_ptr(), scores.data_ptr() if K > 1 else None,
+                                      C.byref(width), _stream(input_ids))
     _lib.check(rc, "gram_generate")
     return seqs, scores, torch.tensor([width.value], dtype=torch.int32)
 
@@ -92,7 +104,7 @@ def generate(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: 
 @generate.register_fake
 def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
-      cache_x, n_cached, cache_L):
+      cache_x, n_cached, cache_L, trie_sub_rows=None, trie_d_tail=0, trie_tail_steps=0):
     B = input_ids.shape[0]
     return (input_ids.new_empty(B * num_return_sequences, max_length),
             input_ids.new_empty(B * num_return_sequences if num_beams > 1 else 0, dtype=torch.float32),

@@ -175,7 +175,7 @@ class BaseRunner:
         return n
 
     # ---------------------------------------------------------------- GPU batches, whatever --eval_batch_size is
-    def _gpu_batch_users(self, model, n_slots: int, L: int, K: int, max_length: int) -> int:
+    def _gpu_batch_users(self, model, n_slots: int, L: int, K: int, max_length: int, fn=None) -> int:
         """Users per ``generate`` call.  The reference scores `--eval_batch_size` users per call (default 1,
         arguments.py:84-86): 95 users/s on this path against 3 100 at 4 096 per call.  A user's result does not depend on the batch
         it is scored in (bit for bit: tests/test_gpu_configs.py), so the runner re-batches: `--eval_gpu_batch` / GRAM_EVAL_USERS
@@ -184,7 +184,10 @@ class BaseRunner:
         if explicit > 0:
             return explicit
         if hasattr(model, "max_users_per_call"):
-            return int(model.max_users_per_call(n_slots, L, K, max_length, limit=4096))
+            try:  # (fn: the Trie closure of the calls, so that a batch is sized with the tail pass's forest where it will take it)
+                return int(model.max_users_per_call(n_slots, L, K, max_length, limit=4096, prefix_allowed_tokens_fn=fn))
+            except TypeError:  # a model whose max_users_per_call does not take the closure
+                return int(model.max_users_per_call(n_slots, L, K, max_length, limit=4096))
         return 4096
 
     def _rescore_unfinished(self, model, input_ids, attention_mask, seqs, scores, fn, K, ref_max_length, shape):
@@ -369,7 +372,7 @@ class BaseRunner:
         collator = getattr(testloader, "collate_fn", None)
         n_slots = int(_arg(self.args, "max_his", 20)) + 1
         L = int(getattr(collator, "item_prompt_max_len", 0) or _arg(self.args, "item_prompt_max_len", 128))
-        users_per_call = self._gpu_batch_users(model, n_slots, L, K, max_length)
+        users_per_call = self._gpu_batch_users(model, n_slots, L, K, max_length, fn)
         lap("candidate_strings")
         logging.info(f"scoring {users_per_call} users per generate() call (--eval_batch_size {_arg(self.args, 'eval_batch_size', 1)} "
                      f"is the loader's; results do not depend on the batch)")

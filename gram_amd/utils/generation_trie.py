@@ -378,6 +378,75 @@ class FlatTrie:
         self._decoder_rows[int(start_token)] = out
         return out
 
+    # A forest row costs what a step's row costs (the GEMMs, most of a decode step); what the tail pass saves is bank sweeps and
+    # launches.  1.10 is a choice from the Trie's shape, not from a sweep over factors: on Beauty it admits d = 5 (1.04 rows per level
+    # of height) and refuses d = 4 (1.13), whose subtrees reach 100 rows.  Measured at d = 5 (bench shape): 80.6 forest rows per user
+    # on average, 93 at most, against 100 rows of five full steps -- so the GEMMs shrink too; other factors / depths were not measured.
+    TAIL_ROW_FACTOR = 1.10
+
+    def tail_tables(self, factor: Optional[float] = None):
+        """(sub_rows, d_tail, steps): the tail tables of ``gram_generate_tail`` (include/gram_hip.h ``gram_trie_tail_t``).
+
+        ``sub_rows`` int32 [n_nodes]: the decoder rows of a node's subtree -- the node and its descendants that have children; 0 for
+        a leaf (nothing is predicted after EOS).  Against that stands what stepping through the subtree costs a beam: one row per
+        level that still has a node with children, the subtree's height.  ``d_tail`` is the smallest prefix length d >= 2 (start
+        token counted) such that from d on, at every length, the subtrees hold at most ``factor`` (TAIL_ROW_FACTOR) times their
+        heights in rows, summed over the nodes of that length, and at least two steps are left to replace; 0 when no length
+        qualifies or more than GRAM_TAIL_MAX_STEPS steps would be left: the Trie has no tail and ``generate`` decodes step by step.
+        ``steps`` = the decode steps left at d_tail (the depth of the deepest node with children - d_tail + 1), 0 without a tail.
+        Built once per Trie from the CSR arrays alone (both constructors), one vectorised pass per level."""
+        f = float(self.TAIL_ROW_FACTOR if factor is None else factor)
+        hit = getattr(self, "_tail_tables", None)
+        if hit is not None and hit[0] == f:
+            return hit[1]
+        from .. import _lib
+
+        n = self.n_nodes
+        fan = np.diff(self.child_off).astype(np.int64)
+        child = self.child_node.astype(np.int64)
+        parent = np.zeros(n, dtype=np.int64)
+        parent[child] = np.repeat(np.arange(n, dtype=np.int64), fan)
+        depth = np.zeros(n, dtype=np.int64)
+        levels, frontier = [], np.zeros(1, dtype=np.int64)
+        while frontier.size:
+            levels.append(frontier)
+            counts = fan[frontier]
+            first = self.child_off[frontier].astype(np.int64)
+            edges = np.repeat(first - (np.cumsum(counts) - counts), counts) + np.arange(int(counts.sum()), dtype=np.int64)
+            frontier = child[edges]
+            depth[frontier] = len(levels)
+        inner = (fan > 0) & (np.arange(n) > 0)
+        sub = inner.astype(np.int64)
+        height = inner.astype(np.int64)
+        for lv in reversed(levels[2:]):  # (level 1 hangs on the root, which is no row)
+            np.add.at(sub, parent[lv], sub[lv])
+            np.maximum.at(height, parent[lv], np.where(inner[parent[lv]], height[lv] + 1, 0))
+        sub[~inner] = 0
+        d_tail, steps = 0, 0
+        if inner.any():
+            deepest = int(depth[inner].max())
+            for d in range(deepest, 1, -1):  # from the bottom up: the first length that fails ends the tail
+                at = inner & (depth == d)
+                if not at.any() or sub[at].sum() > f * height[at].sum():
+                    break
+                if deepest - d + 1 >= 2:
+                    d_tail = d
+            if d_tail and deepest - d_tail + 1 > _lib.GRAM_TAIL_MAX_STEPS:
+                d_tail = 0
+            steps = deepest - d_tail + 1 if d_tail else 0
+        out = (sub.astype(np.int32), int(d_tail), int(steps))
+        self._tail_tables = (f, out)
+        return out
+
+    def tail_rows_on(self, device):
+        """Device copy of :meth:`tail_tables`' ``sub_rows``, uploaded once per device."""
+        import torch
+
+        key = ("tail", str(device))
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.tail_tables()[0]).to(device)
+        return self._device[key]
+
     def decoder_rows_on(self, device, start_token: int = 0):
         """(:meth:`decoder_rows`, its seven arrays as device tensors in ``gram_trie_rows_t``'s field order), uploaded once per device."""
         import torch

@@ -601,6 +601,79 @@ int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const u
                         const gram_user_items_t* items_host, void* workspace, int64_t workspace_bytes, int64_t* sequences,
                         float* scores, int32_t* width_host, void* stream);
 
+/* ---- the tail pass: the chain-like lower levels of the Trie decoded in one pass per user forest ---------------------
+ * Once a user's beams stand on prefixes of length d_tail (start token counted), every decoder state the remaining search steps can
+ * ask for belongs to a known forest: the beams' nodes and their descendants that have children.  gram_generate_tail builds that
+ * forest on the device after the search step that reaches d_tail (gram_tail_forest), runs the decoder ONCE over its rows -- the
+ * cross-attention reads a user's bank once per 64 forest rows instead of once per step -- and replays the remaining search steps on
+ * the stored hidden states (gram_tail_rowpos maps each beam to its forest row; no decoder launch in between).  Sequences, scores
+ * and the beam state after every step are gram_generate_ex's bit for bit: every kernel of the pass is row-independent, the
+ * self-attention IS the step-wise kernel (level by level) and the cross-attention is the step-wise kernel's template. */
+#define GRAM_TAIL_MAX_STEPS 16  /* decode steps one pass replaces at most (a forest row walks that many parents at most) */
+#define GRAM_TAIL_ENTRY_ROWS 64 /* forest rows of one cross-attention entry: the four 16-row tiles of the entry kernel        */
+typedef struct {
+  const int32_t* sub_rows; /* device, i32 [n_nodes]: decoder rows of node n's subtree = n and its descendants that have children;
+                              0 for a leaf (FlatTrie.tail_tables)                                                              */
+  int32_t d_tail;          /* switch depth: the pass starts when the beams hold d_tail tokens; 0 = this Trie has no tail       */
+  int32_t steps;           /* decode steps left from there: (depth of the deepest node with children) - d_tail + 1             */
+} gram_trie_tail_t;
+/* The forest of one call (device arrays, carved from the workspace by gram_generate_tail).  Rows are user-major; inside a user
+ * depth-major: the live beams in beam order, then level by level the children that have children, parents in row order, children
+ * in token order. */
+typedef struct {
+  int32_t* tokens;    /* [cap_rows]  decoder input token of the row                                                  */
+  int32_t* pos;       /* [cap_rows]  decoder position of the row                                                     */
+  int32_t* parent;    /* [cap_rows]  forest row of the parent prefix, -1 for a beam's own row                        */
+  int32_t* root;      /* [cap_rows]  beam row b * K + k whose subtree the row belongs to (its cache and anc column)  */
+  int32_t* node;      /* [cap_rows]  Trie node of the row's prefix                                                   */
+  int32_t* user_off;  /* [B + 1]     rows of user b: [user_off[b], user_off[b + 1])                                  */
+  int32_t* ent_off;   /* [B + 1]     cross-attention entries of user b (one per 64 rows)                             */
+  int32_t* ent_users; /* [cap_entries]       user of each entry                                                      */
+  int32_t* ent_rows;  /* [cap_entries][64]   forest rows of each entry, -1 = none                                    */
+  int32_t* rowpos;    /* [B * K]     forest row of each beam in the coming search step, -1 = the beam is not live    */
+  int32_t* counts;    /* [4 + 2 * GRAM_TAIL_MAX_STEPS]  rows, entries, most rows of one user, 0, then the rows of every level of
+                         the even users [GRAM_TAIL_MAX_STEPS] and of the odd users [GRAM_TAIL_MAX_STEPS]                 */
+  /* The self-attention of the pass is the step-wise kernel, run level by level: level l (position t + l) takes its rows gathered
+   * by SLOT -- a row's index among the rows of its level, which is also the cache row the kernel writes its k and v to -- and an
+   * ancestor table of its own: column s holds, for positions < t, what the beam's column of gram_beam_state_t.anc holds, and from
+   * t on the slots of the row's ancestors in the forest.  A level of the forest may hold more rows than the cache has per position
+   * (B * K): the users go in two groups, even and odd, each with its own slots and tables, run one after the other.  (Slots are
+   * handed out per user and level in the order the users' threads arrive: they differ from run to run, the results do not.) */
+  int32_t* slot;       /* [cap_rows]                slot of the row at its level, within its user's group               */
+  int32_t* lvl_rows;   /* [2][n_levels][cap_rows]   forest row of every slot                                            */
+  int32_t* lvl_tokens; /* [2][n_levels][cap_rows]   its token (layer 0 reads the token table by it)                     */
+  int32_t* lvl_anc;    /* [2][n_levels][Tmax][B*K]  the ancestor tables                                                 */
+  int32_t cap_rows, cap_entries, n_levels, pad_;
+} gram_forest_t;
+/* counts and offsets (one workgroup), the rows, slots and entries (one thread per user), the ancestor tables (one thread per row).
+ * A forest of more than cap_rows rows or cap_entries entries writes its counts only: the caller reads them and goes on step by
+ * step (as it does when a group's level holds more than B * K rows: a level's slots are cache rows).  t = position of the beams' rows. */
+int gram_tail_forest(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const gram_trie_tail_t* tail_host,
+                     const gram_forest_t* forest_host, int t, void* stream);
+/* forest.rowpos for the coming search step: the forest row whose node is the beam's, -1 for a beam that is not live. */
+int gram_tail_rowpos(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const gram_forest_t* forest_host, void* stream);
+/* dst row rows[i] = src row i, for i < n: rows of row_bytes bytes (a multiple of 16); an index outside [0, dst_rows) is skipped.  The
+ * tail pass runs its self-attention level by level with the step-wise kernel, on the level's rows gathered by slot, and puts the
+ * results back with this. */
+int gram_scatter_rows(const void* src, const int32_t* rows, void* dst, int n, int row_bytes, int dst_rows, void* stream);
+/* gram_cross_attn_decode_split's live-row form over entries: workgroup row e serves user ent_users[e] and the up to 64 rows
+ * ent_rows[e * 64 ..] of q / out (-1: none).  K is the beam count of the search whose bits are restated (it selects the one- or
+ * two-wave split of the keys, as gram_cross_attn_decode_split does): a row gets the bits that call gives it. */
+int gram_cross_attn_entries_split(const void* q, const void* k_layer, const void* vt_layer, const uint8_t* mask, void* out,
+                                  int n_entries, int K, int H, int S, const int32_t* ent_users, const int32_t* ent_rows, int pieces,
+                                  int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits, void* stream);
+/* Workspace of gram_generate_tail: gram_workspace_bytes plus the forest's decoder rows and tables, carved BEHIND it (nothing of
+ * gram_workspace_bytes's layout moves).  Capacity: 5/4 * B * K * steps rows (a forest of the average Beauty node holds 1.04 rows
+ * per replaced step and beam), about 38 KB per row at T5-base in the two-piece mode. */
+int64_t gram_workspace_bytes_tail(const gram_model_t* m, int B, int N, int L, int K, int max_length, int steps);
+/* gram_generate_ex with the tail pass.  tail_host NULL, d_tail 0, K = 1, a handle with a raised fused limit, a call for which
+ * gram_tail_pass_wanted says 0 or a forest over capacity: exactly gram_generate_ex's launches.  Otherwise workspace_bytes must be
+ * gram_workspace_bytes_tail's. */
+int gram_generate_tail(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
+                       int max_length, float length_penalty, const gram_trie_t* trie_host, const gram_compaction_t* compaction_host,
+                       const gram_trie_tail_t* tail_host, void* workspace, int64_t workspace_bytes, int64_t* sequences,
+                       float* scores, int32_t* width_host, void* stream);
+
 /* The encoder layers alone on P independent passages (T5Stack encoder role, gram_t5_modeling.py:1037-1296, up to
  * but excluding final_layer_norm): x_out f32 [P][L][d_model] is the residual stream the final norm, the position
  * embedding and the bank projection consume.  ids i64 [P][L], mask u8 [P][L].  Workspace as for
@@ -812,6 +885,28 @@ int gram_debug_set_live_rows(int on);
 /* A/B hook: 0 = layer 0's QKV GEMMs run as on a handle without token tables, 1 = the tables are read where the handle has them,
  * -1 = what the GRAM_TOKEN_TABLES environment variable says (default 1).  Results are bit-identical either way.  Process-wide. */
 int gram_debug_set_token_tables(int on);
+/* A/B hook: 0 = gram_generate_tail decodes step by step like gram_generate_ex, 1 = the tail pass wherever the Trie has a tail,
+ * -1 (default) = what the GRAM_TAIL_PASS environment variable says (0: never, 1: wherever the Trie has a tail), and without it by
+ * size: the pass where one layer's bank holds at least 256 MB.  The pass is faster at every batch size measured; the default keeps
+ * small calls on the step-wise train because the suite pins that train there.
+ * Results are bit-identical either way.  Process-wide. */
+int gram_debug_set_tail_pass(int on);
+/* 1 if gram_generate_tail would take the tail pass for a call of this shape on a Trie with a tail (the switch and the size rule
+ * above), 0 if not: what a caller sizes its workspace by.  < 0: GRAM_E_ARG. */
+int gram_tail_pass_wanted(const gram_model_t* m, int B, int N, int L);
+/* TEST hook: the forest may hold at most `rows` rows (0 = what the workspace was carved for), so that the over-capacity fallback is
+ * reachable with small Tries.  Process-wide. */
+int gram_debug_set_tail_capacity(int rows);
+/* TEST hook: a group's level of the forest may hold at most `rows` rows (0 = the cache's B * K rows per position), so that the
+ * level fallback is reachable with small Tries.  Process-wide. */
+int gram_debug_set_tail_level_capacity(int rows);
+/* What the last gram_generate[_ex / _items / _tail] of this process did: out[0] = 1 if the tail pass ran (0: step by step), out[1] = forest rows,
+ * out[2] = cross-attention entries, out[3] = most rows of one user (the three counts are 0 when no forest was built). */
+int gram_debug_tail_last(int32_t* out4);
+/* TEST hook: where gram_generate[_ex / _items / _tail] keeps its beam state inside a workspace carved for (B, N, L, K, max_length):
+ * *out gets the device pointers and sizes (length_penalty is the carve's default), so a test can read the state a call left. */
+int gram_debug_workspace_beam_state(const gram_model_t* m, void* workspace, int B, int N, int L, int K, int max_length,
+                                    gram_beam_state_t* out);
 /* A/B hook (tests/bench_wide_trie.py): which form of the Trie-constrained search step runs.  -1 (default) and 0 = by shape: the
  * one-shot kernel where all K * max_fanout candidates fit on chip, the chunked kernel otherwise; 1 = always the chunked kernel.
  * Results are bit-identical either way.  Process-wide. */

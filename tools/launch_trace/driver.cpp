@@ -11,6 +11,7 @@
 extern char* g_ws;
 extern int64_t g_ws_bytes;
 extern std::vector<int> g_live_script;
+extern std::vector<int> g_tail_script;
 void trace_line(const char* name, int64_t v);
 
 namespace {
@@ -35,6 +36,7 @@ struct Case {
   bool items;                 // gram_generate_items: per-user item filters (gram_user_items_t)
   int max_L;                  // != 0: gram_model_set_max_passage_len first (a long-mode handle: the tiled encoder attention at every L)
   int max_S;                  // != 0: gram_model_set_max_fused_len first (the long cross-attention at every S; the model takes 40 passages)
+  int tail_rows;              // != 0: gram_generate_tail with d_tail = 2 and two steps left; gram_tail_forest reports this many rows
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -91,6 +93,13 @@ const Case kCases[] = {
     {"generate_fused_4704", GENERATE, 2, 1, 2, 21, 224, 4, 4, SOME, false, false, false, false, 0, false, 256, 16384},
     {"tf_fused_4704", TEACHER_FORCED, 2, 1, 2, 21, 224, 3, 4, OFF, false, false, false, false, 0, false, 256, 16384},
     {"score_trie_fused_4704", SCORE_TRIE, 2, 1, 2, 21, 224, 3, 4, OFF, false, false, false, false, 0, false, 256, 16384},
+    // gram_generate_tail (d_tail = 2, two steps left; capacity 5/4 * 8 * 2 = 20 rows): the trains of generate_p1_folded /
+    // generate_p2_tables up to step 1, then the forest, ONE decoder pass over its 11 rows in 2 entries and two search steps; a forest
+    // of 21 rows goes on step by step (generate_p1_folded's train behind the forest's count); a raised fused limit never builds one
+    {"generate_tail_p1", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 11},
+    {"generate_tail_p2_tables", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, true, 0, false, 0, 0, 11},
+    {"generate_tail_over", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 21},
+    {"generate_tail_fused_32", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 16384, 11},
 };
 
 gram_model_t* make_model(int pieces, int fold, int max_passages) {
@@ -149,6 +158,17 @@ int run(const Case& c) {
     g_ws_bytes = gram_workspace_bytes_trie(m, B, N, L, K * T);
     trace_line("gram_workspace_bytes_trie", g_ws_bytes);
   }
+  gram_trie_tail_t tail{nullptr, 2, 2};
+  if (c.tail_rows) {
+    tail.sub_rows = fake<int32_t>();  // (only here: the other cases' fake addresses stay what their goldens recorded)
+    // rows, entries, most rows of a user, 0; then the even users' levels (4 and rows - 7) and, 16 entries on, the odd users' (3 and 0)
+    g_tail_script = {c.tail_rows, (c.tail_rows + 63) / 64 + 1, c.tail_rows - 3, 0, 4, c.tail_rows - 7};
+    g_tail_script.resize(4 + GRAM_TAIL_MAX_STEPS, 0);
+    g_tail_script.push_back(3);
+    gram_debug_set_tail_pass(1);  // (whatever GRAM_TAIL_PASS says in the caller's environment)
+    g_ws_bytes = gram_workspace_bytes_tail(m, B, N, L, K, T, tail.steps);
+    trace_line("gram_workspace_bytes_tail", g_ws_bytes);
+  }
   g_ws = (char*)calloc(g_ws_bytes, 1);  // zeroed, and touched only where a stub writes: a large case costs address space alone
   int32_t width = -1;
   void* io[5] = {fake(), fake(), fake(), fake(), fake()};  // the remaining inputs and outputs of the entry, in its argument order
@@ -159,6 +179,9 @@ int run(const Case& c) {
         return gram_generate_items(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, &items, g_ws, g_ws_bytes,
                                    (int64_t*)io[0], (float*)io[1], &width, st);
       }
+      if (c.tail_rows)
+        return gram_generate_tail(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, &tail, g_ws, g_ws_bytes,
+                                  (int64_t*)io[0], (float*)io[1], &width, st);
       return gram_generate_ex(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, g_ws, g_ws_bytes, (int64_t*)io[0],
                               (float*)io[1], &width, st);
     case ENCODE_FUSED:

@@ -14,6 +14,7 @@
 char* g_ws = nullptr;  // the workspace of the running case (driver.cpp)
 int64_t g_ws_bytes = 0;
 std::vector<int> g_live_script;  // what the next gram_live_rows calls report: {live rows, users} per call
+std::vector<int> g_tail_script;  // what the next gram_tail_forest call reports: {rows, entries, most rows of a user}
 
 namespace {
 void put(int v) { printf(" %d", v); }
@@ -54,6 +55,11 @@ void put(const gram_trie_rows_t* r) {
   fields(r->tokens, r->pos, r->anc, r->row_node, r->node_row, r->node_tok, r->node_leaf, r->Q, r->Tq, r->n_nodes, r->n_leaves);
 }
 void put(const gram_live_rows_t* l) { fields(l->rows, l->rowpos, l->users, l->tokens, l->counts); }
+void put(const gram_trie_tail_t* t) { fields(t->sub_rows, t->d_tail, t->steps); }
+void put(const gram_forest_t* f) {
+  fields(f->tokens, f->pos, f->parent, f->root, f->node, f->user_off, f->ent_off, f->ent_users, f->ent_rows, f->rowpos, f->counts,
+         f->slot, f->lvl_rows, f->lvl_tokens, f->lvl_anc, f->cap_rows, f->cap_entries, f->n_levels);
+}
 template <class... A>
 int rec(const char* name, A... a) {
   fputs(name, stdout);
@@ -212,6 +218,23 @@ int gram_live_rows(const gram_beam_state_t* s, const gram_trie_t* trie, const gr
     if (!g_live_script.empty()) g_live_script.erase(g_live_script.begin());
   }
   REC(s, trie, out, out->counts[0], out->counts[1], st);
+}
+int gram_tail_forest(const gram_beam_state_t* s, const gram_trie_t* trie, const gram_trie_tail_t* tail, const gram_forest_t* f, int t,
+                     void* st) {
+  for (int i = 0; i < 4 + 2 * GRAM_TAIL_MAX_STEPS; ++i) {  // the scripted counts: rows, entries, most rows, 0, rows per (group, level)
+    f->counts[i] = g_tail_script.empty() ? 0 : g_tail_script.front();
+    if (!g_tail_script.empty()) g_tail_script.erase(g_tail_script.begin());
+  }
+  REC(s, trie, tail, f, t, f->counts[0], f->counts[1], st);
+}
+int gram_tail_rowpos(const gram_beam_state_t* s, const gram_trie_t* trie, const gram_forest_t* f, void* st) { REC(s, trie, f, st); }
+int gram_scatter_rows(const void* src, const int32_t* rows, void* dst, int n, int row_bytes, int dst_rows, void* st) {
+  REC(src, rows, dst, n, row_bytes, dst_rows, st);
+}
+int gram_cross_attn_entries_split(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int n_entries, int K, int H,
+                                  int S, const int32_t* ent_users, const int32_t* ent_rows, int pieces, int64_t q_ps, int64_t bank_ps,
+                                  const uint32_t* key_bits, void* st) {
+  REC(q, k, vt, mask, out, n_entries, K, H, S, ent_users, ent_rows, pieces, q_ps, bank_ps, key_bits, st);
 }
 
 hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t st) { return (hipError_t)rec(__func__, dst, value, bytes, (void*)st); }
