@@ -50,9 +50,7 @@ __device__ __forceinline__ f32x4 xa_merge_o(f32x4 o0, f32x4 o1, float w0, float 
 
 // NT = 16-beam tiles; LIVE: live-row step (gram_live_rows_t); S = bf16 pieces; NW = waves per workgroup (1: a wave owns the whole
 // (user, head) and nothing is merged)
-// ENT: the entry form of the tail pass (gram_cross_attn_entries_split) -- the row table is indexed by the workgroup row, not by the
-// user, so that a user may own several workgroup rows
-template <int NT, bool LIVE, int S, int NW, bool ENT = false>
+template <int NT, bool LIVE, int S, int NW>
 __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     const p16* __restrict__ q, const p16* __restrict__ kbank, const p16* __restrict__ vtbank,
     const uint8_t* __restrict__ mask, p16* __restrict__ out, int K, int H, int Sk, const int32_t* __restrict__ users,
@@ -70,7 +68,6 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   // live-row step (users != NULL): workgroup y serves user users[y]; q/out rows are the compact rows rowpos[b*K + beam]
   // (-1 = beam not live: zero query, nothing stored)
   const int h = blockIdx.x, b = LIVE ? users[blockIdx.y] : blockIdx.y;
-  const int rb = ENT ? (int)blockIdx.y : b;  // whose slots of the row table this workgroup serves
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, g = lane >> 4;
@@ -95,7 +92,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   // instructions only
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    const int qrow = xa_row<LIVE>(rb, K, 16 * nt + c, rowpos);
+    const int qrow = xa_row<LIVE>(b, K, 16 * nt + c, rowpos);
 #pragma unroll
     for (int pc = 0; pc < S; ++pc)
 #pragma unroll
@@ -309,7 +306,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
       lt += __shfl_xor(lt, 16, 64);
       lt += __shfl_xor(lt, 32, 64);
       const float inv = 1.f / lt;
-      const int orow = xa_row<LIVE>(rb, K, 16 * nt + c, rowpos);
+      const int orow = xa_row<LIVE>(b, K, 16 * nt + c, rowpos);
       if (orow >= 0) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) xa_store<S>(out, orow, inner, h * 64 + 16 * mt + 4 * g, o[mt][nt] * inv);
@@ -340,9 +337,344 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     xa_merge_w(sm_m[beam], sm_m[NB + beam], sm_l[beam], sm_l[NB + beam], w0, w1, inv2);
     const f32x4 v = xa_merge_o(*reinterpret_cast<const f32x4*>(sm_o + ((size_t)beam) * 64 + d4),
                          *reinterpret_cast<const f32x4*>(sm_o + ((size_t)(NB + beam)) * 64 + d4), w0, w1, inv2);
-    int orow = rb * K + beam;  // (beam < K here; through xa_row() hipcc keeps the comparison and reschedules the merge)
+    int orow = b * K + beam;  // (beam < K here; through xa_row() hipcc keeps the comparison and reschedules the merge)
     if constexpr (LIVE) orow = rowpos[orow];
     if (orow >= 0) xa_store<S>(out, orow, inner, h * 64 + d4, v);
+  }
+}
+
+// The entry form of the tail pass (gram_cross_attn_entries_split): the rows of a user's forest, 64 table slots per entry
+// (gram_forest_t.ent_rows, -1 = none).  One workgroup per (head, run of consecutive entries that name one user): the workgroup of an
+// entry whose predecessor names the same user returns at once, the run's leader serves the run two entries (eight 16-row tiles) at a
+// time and sweeps the user's bank slice once per pair.  2 * NW waves: wave (p, w) owns the valid key steps the step-wise kernel deals
+// to wave w of NW and the live tiles -- tiles with a row in any of their 16 slots -- of ordinal p, p + 2, ... of the pair, at most
+// four; a tile without a row costs nothing.  The two waves (0, w) and (1, w) of a key split consume the same steps and share a ring
+// of two stages: one brings a step's K tiles, the other its V^T tiles, one step ahead, and one workgroup barrier per step hands the
+// stages over (gram_sync(): the chaos build screens it).  The form with a private stage and a counted-wait pipeline per wave, as in
+// cross_attn_kernel, was measured too: its second request for a line is not reliably an L2 hit (13.8 GB per launch from beyond the
+// L2 against 10.7 GB here) and it was 0.4 ms per launch slower (profiles/xattn_entries_bench_ab.txt).
+// A row's arithmetic (S^T, online softmax, O^T, the merge of the two key-split partials) is the step-wise kernel's, instruction for
+// instruction per row, so a row's bits are those of cross_attn_kernel<.., S, NW> whatever tile of whatever entry holds it.
+constexpr int XA_RUN_MERGE = 4 * (4 * 64 * 16 + 2 * 64 * 4);  // LDS per half for the merge: O, m, l of wave (p, 1) (aliases the stages)
+template <int S, int NW>
+__global__ __launch_bounds__(2 * NW * 64, 2) void cross_attn_runs_kernel(
+    const p16* __restrict__ q, const p16* __restrict__ kbank, const p16* __restrict__ vtbank, const uint8_t* __restrict__ mask,
+    p16* __restrict__ out, int n_entries, int H, int Sk, const int32_t* __restrict__ ent_users, const int32_t* __restrict__ ent_rows,
+    long q_pstride, long bank_pstride, const uint32_t* __restrict__ key_bits) {
+  using T = SplitTab<S>;
+  static_assert(NW == 1 || NW == 2, "the merge is written for two waves");
+  constexpr int ER = GRAM_TAIL_ENTRY_ROWS;        // table slots per entry
+  constexpr int MT = 4;                           // tiles per wave at most: half of a pair's eight
+  static_assert(ER == 64, "a pair of entries is eight 16-row tiles");
+  constexpr int PSTR = 2 * XA_TILE;               // piece stride inside the stage: K tile | V^T tile
+  constexpr int STAGE = S * PSTR;                 // per wave
+  constexpr int MERGE = XA_RUN_MERGE;
+  static_assert(MERGE == MT * (4 * 64 * 16 + 2 * 64 * 4), "O, m, l of up to MT tiles, one slot per lane");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int h = blockIdx.x, lead = blockIdx.y;
+  const int b = ent_users[lead];
+  if (lead > 0 && ent_users[lead - 1] == b) return;  // served by the run's leader
+  int run_end = lead + 1;
+  while (run_end < n_entries && ent_users[run_end] == b) ++run_end;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave = wv % NW, half = wv / NW;       // key split | which of the pair's live tiles
+  const int c = lane & 15, g = lane >> 4;
+  const int inner = H * 64;
+  const char* kb = reinterpret_cast<const char*>(kbank + ((size_t)b * H + h) * Sk * 64);
+  const char* vt = reinterpret_cast<const char*>(vtbank + ((size_t)b * H + h) * 64 * Sk);
+  const uint8_t* mk = mask + (size_t)b * Sk;
+
+  // the valid 32-key steps and their dealing to the waves of a key split: cross_attn_kernel's
+  const int nsteps = Sk >> 5;
+  uint32_t kb0 = 0, kb1 = 0;
+  if (key_bits) {
+    if (lane < nsteps) kb0 = key_bits[(size_t)b * 128 + lane];
+    if (lane + 64 < nsteps) kb1 = key_bits[(size_t)b * 128 + 64 + lane];
+  } else {
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const int st = lane + 64 * hf;
+      uint32_t bits = 0;
+      if (st < nsteps) {
+        const uint4* p = reinterpret_cast<const uint4*>(mk + 32 * st);
+        const uint4 a = p[0], c2 = p[1];
+        const uint32_t w8[8] = {a.x, a.y, a.z, a.w, c2.x, c2.y, c2.z, c2.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bits |= ((w8[i] >> (8 * j)) & 0xffu) ? (1u << (4 * i + j)) : 0u;
+      }
+      if (hf == 0) kb0 = bits; else kb1 = bits;
+    }
+  }
+  unsigned long long v0 = __ballot(kb0 != 0u), v1 = __ballot(kb1 != 0u);
+  if ((v0 | v1) == 0ull) {  // no valid key at all: every step is kept (uniform softmax over all S keys)
+    v0 = nsteps >= 64 ? ~0ull : ((1ull << nsteps) - 1ull);
+    v1 = nsteps > 64 ? ((nsteps >= 128 ? ~0ull : ((1ull << (nsteps - 64)) - 1ull))) : 0ull;
+  }
+  v0 = __builtin_amdgcn_readfirstlane((unsigned)v0) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(v0 >> 32)) << 32);
+  v1 = __builtin_amdgcn_readfirstlane((unsigned)v1) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(v1 >> 32)) << 32);
+  int ord = 0;  // ordinal of the next valid step (wave-uniform scalar state)
+  auto next = [&](int s) -> int {
+    for (s = s + 1; s < nsteps; ++s) {
+      const unsigned long long bit = (s < 64 ? (v0 >> s) : (v1 >> (s - 64))) & 1ull;
+      if (bit) {
+        const bool mine = ord == wave;
+        ord = ord + 1 == NW ? 0 : ord + 1;
+        if (mine) return s;
+      }
+    }
+    return nsteps;
+  };
+
+  // per-lane byte offsets of this lane's 16 B in each of the 4 + 4 DMA instructions of a (step, piece)
+  uint32_t koff[4], voff[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int kr = 8 * i + (lane >> 3);
+    koff[i] = (uint32_t)(kr * 128 + (((lane & 7) ^ ksw(kr)) << 4));
+    const int d = 16 * i + (lane >> 2);
+    voff[i] = (uint32_t)(d * 64 + (((lane & 3) ^ vsw(d)) << 4));
+  }
+  // a key split's ring of two stages, shared by its two waves: wave (0, w) brings a step's K tiles, wave (1, w) its V^T tiles
+  const uint32_t stage0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * 2 * STAGE;
+  const int nvalid = __popcll(v0) + __popcll(v1);
+  const int trips = (nvalid + NW - 1) / NW;  // key steps of wave (., 0): every wave of the workgroup meets this many barriers per sweep
+  auto issue_k = [&](int step, int buf) {
+    const uint32_t dst = stage0 + buf * STAGE;
+#pragma unroll
+    for (int pc = 0; pc < S; ++pc) {
+      const char* kbase = kb + (size_t)pc * bank_pstride * 2 + (size_t)step * (32 * 128);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) dma16_nt(dst + pc * PSTR + i * 1024, koff[i], kbase);
+    }
+  };
+  auto issue_v = [&](int step, int buf) {
+    const uint32_t dst = stage0 + buf * STAGE;
+#pragma unroll
+    for (int pc = 0; pc < S; ++pc) {
+      const char* vbase = vt + (size_t)pc * bank_pstride * 2 + (size_t)step * 4096;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) dma16(dst + pc * PSTR + XA_TILE + i * 1024, voff[i], vbase);
+    }
+  };
+  const int krow = 8 * (c >> 2) + (c & 3);  // + 4t: key row of S^T tile t this lane feeds
+
+  f32x4 o[4][MT];
+  float m[MT], l[MT];
+  // one sweep of the slice for this wave's NL live tiles `tiles` (four bits each) of the pair whose table slots start at `rows`:
+  // cross_attn_kernel's arithmetic with NT = NL, step for step
+  auto sweep = [&](auto nl_c, const int32_t* __restrict__ rows, int tiles) __attribute__((always_inline)) {
+    constexpr int NL = decltype(nl_c)::value;
+    constexpr int NA = NL > 0 ? NL : 1;  // (NL = 0: this half of the pair holds no live tile; the wave brings its tiles all the same)
+    // the first step's tiles are requested ahead of the query fragments: both are in flight together
+    ord = 0;
+    int cur = next(-1);
+    if (cur < nsteps) {
+      if (half == 0) issue_k(cur, 0);
+      else issue_v(cur, 0);
+    }
+    p16x8 qf[S][NA][2];
+#pragma unroll
+    for (int nt = 0; nt < NL; ++nt) {
+      const int qrow = rows[16 * ((tiles >> (4 * nt)) & 7) + c];
+#pragma unroll
+      for (int pc = 0; pc < S; ++pc)
+#pragma unroll
+        for (int kd = 0; kd < 2; ++kd)
+          qf[pc][nt][kd] = qrow >= 0 ? ld_global_b128(q + pc * q_pstride + (size_t)qrow * inner + h * 64 + 32 * kd + 8 * g) : zero_bf16x8();
+    }
+    p16x8 kf[S][2][2], vf[S][4];
+    auto read_k = [&](int buf) {
+      const char* stg = smem + (wave * 2 + buf) * STAGE;
+#pragma unroll
+      for (int pc = 0; pc < S; ++pc)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int kd = 0; kd < 2; ++kd) {
+            const int r = krow + 4 * t;
+            kf[pc][t][kd] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + r * 128 + (((g + 4 * kd) ^ ksw(r)) << 4));
+          }
+    };
+    auto read_v = [&](int buf) {
+      const char* stg = smem + (wave * 2 + buf) * STAGE;
+#pragma unroll
+      for (int pc = 0; pc < S; ++pc)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+          const int d = 16 * mt + c;
+          vf[pc][mt] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + XA_TILE + d * 64 + ((g ^ vsw(d)) << 4));
+        }
+    };
+    p16x8 pf[S][NA];
+    auto math_qk = [&](int step) {
+      const uint32_t kword = step < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)kb0, step) : (uint32_t)__builtin_amdgcn_readlane((int)kb1, step - 64);
+      const uint32_t kbits = kword >> (8 * g);
+#pragma unroll
+      for (int nt = 0; nt < NL; ++nt) {
+        f32x4 s[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int pr = 0; pr < T::NP; ++pr) {
+            a = mfma16(kf[T::A[pr]][t][0], qf[T::B[pr]][nt][0], a);
+            a = mfma16(kf[T::A[pr]][t][1], qf[T::B[pr]][nt][1], a);
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) a[j] = ((kbits >> (4 * t + j)) & 1u) ? a[j] : GRAM_FMIN;
+          s[t] = a;
+        }
+        float tm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
+                         fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
+        tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
+        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+        const float mn = fmaxf(m[nt], tm);
+        const float alpha = __expf(m[nt] - mn);
+        m[nt] = mn;
+        float ps = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float e = __expf(s[t][j] - mn);
+            ps += e;
+#pragma unroll
+            for (int pc = 0; pc < S; ++pc) {
+              const p16 eb = (p16)e;
+              pf[pc][nt][4 * t + j] = eb;
+              e -= (float)eb;
+            }
+          }
+        l[nt] = xa_l_update(l[nt], alpha, ps);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) o[mt][nt] *= alpha;
+      }
+    };
+    auto math_pv = [&]() {
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NL; ++nt)
+#pragma unroll
+          for (int pr = 0; pr < T::NP; ++pr) o[mt][nt] = mfma16(vf[T::A[pr]][mt], pf[T::B[pr]][nt], o[mt][nt]);
+    };
+    wait_vm<0>();
+#pragma unroll
+    for (int nt = 0; nt < NL; ++nt)
+#pragma unroll
+      for (int pc = 0; pc < S; ++pc)
+#pragma unroll
+        for (int kd = 0; kd < 2; ++kd) asm volatile("" : "+v"(qf[pc][nt][kd]));
+    // A step's tiles are requested one step ahead, into the other stage of the ring.  One workgroup barrier per step: behind it the
+    // step's tiles have landed (each partner has waited for its own) and every wave has the last step's fragments in registers, so
+    // that stage is free for the next step's tiles.  A wave that has run out of steps -- the second key split may own one step fewer
+    // -- goes on meeting the barriers.
+    for (int it = 0; it < trips; ++it) {
+      const int buf = it & 1;
+      wait_vm<0>();
+      gram_sync();
+      const int nxt = cur < nsteps ? next(cur) : nsteps;
+      if (nxt < nsteps) {
+        if (half == 0) issue_k(nxt, buf ^ 1);
+        else issue_v(nxt, buf ^ 1);
+      }
+      if constexpr (NL > 0) {
+        if (cur < nsteps) {
+          read_k(buf);
+          math_qk(cur);
+          read_v(buf);
+          math_pv();
+        }
+      }
+      cur = nxt;
+    }
+  };
+
+  for (int e0 = lead; e0 < run_end; e0 += 2) {
+    const int32_t* rows = ent_rows + (size_t)e0 * ER;
+    const int ntiles = e0 + 1 < run_end ? 2 * (ER / 16) : ER / 16;
+    // the pair's live tiles, dealt alternately to the two halves (wave-uniform: a ballot per tile)
+    int nl = 0, tiles = 0, seen = 0;
+#pragma unroll
+    for (int t = 0; t < 2 * (ER / 16); ++t) {
+      const int r = t < ntiles ? rows[16 * t + c] : -1;
+      if (__ballot(r >= 0) != 0ull) {
+        if ((seen & 1) == half) {
+          tiles |= t << (4 * nl);
+          ++nl;
+        }
+        ++seen;
+      }
+    }
+    if (seen == 0) continue;  // (the same for every wave of the workgroup)
+    nl = __builtin_amdgcn_readfirstlane(nl);
+    tiles = __builtin_amdgcn_readfirstlane(tiles);
+#pragma unroll
+    for (int nt = 0; nt < MT; ++nt) {
+      m[nt] = GRAM_FMIN;
+      l[nt] = 0.f;
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) o[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    if (e0 != lead) gram_sync();  // the last pair's stages and merge buffers have been read
+    switch (nl) {
+      case 1: sweep(std::integral_constant<int, 1>{}, rows, tiles); break;
+      case 2: sweep(std::integral_constant<int, 2>{}, rows, tiles); break;
+      case 3: sweep(std::integral_constant<int, 3>{}, rows, tiles); break;
+      case 4: sweep(std::integral_constant<int, 4>{}, rows, tiles); break;
+      default: sweep(std::integral_constant<int, 0>{}, rows, tiles); break;
+    }
+    float* mg_o = reinterpret_cast<float*>(smem + half * MERGE);  // [MT][4][64 lanes] f32x4
+    float* mg_m = mg_o + MT * 4 * 64 * 4;                         // [MT][64 lanes]
+    float* mg_l = mg_m + MT * 64;
+    if constexpr (NW == 2) gram_sync();  // every wave is past its loop: the stages are dead
+#pragma unroll
+    for (int nt = 0; nt < MT; ++nt) {
+      if (nt < nl) {
+        float lt = l[nt];
+        lt += __shfl_xor(lt, 16, 64);
+        lt += __shfl_xor(lt, 32, 64);
+        l[nt] = lt;
+        if constexpr (NW == 2) {
+          if (wave == 1) {
+            mg_m[nt * 64 + lane] = m[nt];
+            mg_l[nt * 64 + lane] = lt;
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) *reinterpret_cast<f32x4*>(mg_o + ((nt * 4 + mt) * 64 + lane) * 4) = o[mt][nt];
+          }
+        }
+      }
+    }
+    if constexpr (NW == 2) gram_sync();
+    if (wave == 0) {
+#pragma unroll
+      for (int nt = 0; nt < MT; ++nt) {
+        if (nt < nl) {
+          const int orow = rows[16 * ((tiles >> (4 * nt)) & 7) + c];
+          if constexpr (NW == 2) {
+            float w0, w1, inv2;
+            xa_merge_w(m[nt], mg_m[nt * 64 + lane], l[nt], mg_l[nt * 64 + lane], w0, w1, inv2);
+            if (orow >= 0) {
+#pragma unroll
+              for (int mt = 0; mt < 4; ++mt)
+                xa_store<S>(out, orow, inner, h * 64 + 16 * mt + 4 * g,
+                            xa_merge_o(o[mt][nt], *reinterpret_cast<const f32x4*>(mg_o + ((nt * 4 + mt) * 64 + lane) * 4), w0, w1, inv2));
+            }
+          } else {
+            const float inv = 1.f / l[nt];
+            if (orow >= 0) {
+#pragma unroll
+              for (int mt = 0; mt < 4; ++mt) xa_store<S>(out, orow, inner, h * 64 + 16 * mt + 4 * g, o[mt][nt] * inv);
+            }
+          }
+        }
+      }
+    }
   }
 }
 
@@ -398,25 +730,23 @@ int launch_cross_nt(const XaLaunch& a) {
   }
 }
 
-// The entry form of the tail pass: four row tiles per entry whatever the entry holds (a forest's rows per user are not known on the
-// host); NW is what launch_cross picks for the search's K beams, because the split of the keys over the waves is part of a row's bits.
+// The entry form of the tail pass: one workgroup per entry is launched (the runs of a user's entries are not known on the host) and
+// the leader of each run does the run's work; NW is what launch_cross picks for the search's K beams, because the split of the keys
+// over the waves is part of a row's bits.
 template <int S, int NW>
 int launch_cross_entries(const XaLaunch& a) {
-  constexpr int NT = 4, NB = NT * 16;
-  static_assert(NB == GRAM_TAIL_ENTRY_ROWS, "an entry's row table (gram_forest_t.ent_rows) is indexed by the kernel's padded row count");
-  constexpr int stages = NW * S * 2 * XA_TILE, merge = NW == 1 ? 0 : (2 * NW * NB + NW * NB * 64) * 4;
+  constexpr int stages = NW * 2 * S * 2 * XA_TILE, merge = NW == 1 ? 0 : 2 * XA_RUN_MERGE;  // a ring of two stages per key split
   constexpr int smem = stages > merge ? stages : merge;
   static_assert(smem <= 160 * 1024, "the stages do not fit the LDS");
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_kernel<NT, true, S, NW, true>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cross_attn_runs_kernel<S, NW>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
-  hipLaunchKernelGGL((cross_attn_kernel<NT, true, S, NW, true>), dim3(a.H, a.B), dim3(NW * 64), smem, a.st, (const p16*)a.q,
-                     (const p16*)a.k, (const p16*)a.vt, a.mask, (p16*)a.out, NB, a.H, a.Sk, a.users, a.rowpos, a.q_ps, a.bank_ps,
-                     a.key_bits);
+  hipLaunchKernelGGL((cross_attn_runs_kernel<S, NW>), dim3(a.H, a.B), dim3(2 * NW * 64), smem, a.st, (const p16*)a.q, (const p16*)a.k,
+                     (const p16*)a.vt, a.mask, (p16*)a.out, a.B, a.H, a.Sk, a.users, a.rowpos, a.q_ps, a.bank_ps, a.key_bits);
   GRAM_CHECK_LAUNCH();
   return 0;
 }
