@@ -55,7 +55,6 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
     const p16* __restrict__ q, const p16* __restrict__ kbank, const p16* __restrict__ vtbank,
     const uint8_t* __restrict__ mask, p16* __restrict__ out, int K, int H, int Sk, const int32_t* __restrict__ users,
     const int32_t* __restrict__ rowpos, long q_pstride, long bank_pstride, const uint32_t* __restrict__ key_bits) {
-  using T = SplitTab<S>;
   constexpr int NB = NT * 16;                     // padded beams
   static_assert(NW == 1 || NW == 2, "the merge is written for two waves");
   constexpr int PSTR = 2 * XA_TILE;               // piece stride inside the stage: K tile | V^T tile
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
 
   // query fragments (lane: beam 16 nt + c, dims 32 kd + 8 g ..+7 of the head; zeros for a beam that has no row): requested first, in
   // parallel with the key bits, and retired with them by the wait in front of the loop -- the counted waits of the loop must see DMA
-  // instructions only
+  // instructions only.  (The load and, below, its fence are spelled out in each kernel: as shared functions they cost this one registers)
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int qrow = xa_row<LIVE>(b, K, 16 * nt + c, rowpos);
@@ -106,35 +105,11 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   const int nsteps = Sk >> 5;
   // this lane's two words of key bits (steps lane and lane + 64), either precomputed once per generate (gram_mask_key_bits) or
   // packed here from the mask bytes; every wave holds all of them, so a step's word is one v_readlane away
-  uint32_t kb0 = 0, kb1 = 0;
-  if (key_bits) {
-    if (lane < nsteps) kb0 = key_bits[(size_t)b * 128 + lane];
-    if (lane + 64 < nsteps) kb1 = key_bits[(size_t)b * 128 + 64 + lane];
-  } else {
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int st = lane + 64 * half;
-      uint32_t bits = 0;
-      if (st < nsteps) {
-        const uint4* p = reinterpret_cast<const uint4*>(mk + 32 * st);
-        const uint4 a = p[0], c2 = p[1];
-        const uint32_t w8[8] = {a.x, a.y, a.z, a.w, c2.x, c2.y, c2.z, c2.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bits |= ((w8[i] >> (8 * j)) & 0xffu) ? (1u << (4 * i + j)) : 0u;
-      }
-      if (half == 0) kb0 = bits; else kb1 = bits;
-    }
-  }
-  unsigned long long v0 = __ballot(kb0 != 0u), v1 = __ballot(kb1 != 0u);
-  if ((v0 | v1) == 0ull) {
-    v0 = nsteps >= 64 ? ~0ull : ((1ull << nsteps) - 1ull);
-    v1 = nsteps > 64 ? ((nsteps >= 128 ? ~0ull : ((1ull << (nsteps - 64)) - 1ull))) : 0ull;
-  }
-  v0 = __builtin_amdgcn_readfirstlane((unsigned)v0) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(v0 >> 32)) << 32);
-  v1 = __builtin_amdgcn_readfirstlane((unsigned)v1) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(v1 >> 32)) << 32);
+  uint32_t kb0, kb1;
+  unsigned long long v0, v1;
+  xa_key_steps(key_bits, mk, b, nsteps, lane, kb0, kb1, v0, v1);
   int ord = 0;  // ordinal of the next valid step (wave-uniform scalar state)
+  // (the dealing is spelled out here and in cross_attn_runs_kernel: as a shared function it costs their instantiations one to three SGPRs)
   auto next = [&](int s) -> int {
     for (s = s + 1; s < nsteps; ++s) {
       const unsigned long long bit = (s < 64 ? (v0 >> s) : (v1 >> (s - 64))) & 1ull;
@@ -148,117 +123,27 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
   };
 
   // per-lane byte offsets of this lane's 16 B in each of the 4 + 4 DMA instructions of a (step, piece)
+  // (spelled out in each kernel: computed by shared functions, the bf16 build's <1, ., 2, 2> takes three VGPRs more)
   uint32_t koff[4], voff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int kr = 8 * i + (lane >> 3);  // key row of the tile; the lane lands at position lane & 7 and fetches chunk pos ^ ksw
     koff[i] = (uint32_t)(kr * 128 + (((lane & 7) ^ ksw(kr)) << 4));
     const int d = 16 * i + (lane >> 2);  // V^T row; position lane & 3
-    voff[i] = (uint32_t)(d * 64 + (((lane & 3) ^ vsw(d)) << 4));  // (the bank's V^T is blocked by 32 keys: a step's tile is [64 d][64 B], contiguous)
+    voff[i] = (uint32_t)(d * 64 + (((lane & 3) ^ vsw(d)) << 4));
   }
   const uint32_t stage0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * STAGE;
-  // 4 * S DMA instructions each: this step's K tiles (streaming hint: measured) / V^T tiles of every piece -> the stage
-  auto issue_k = [&](int step) {
-    const uint32_t dst = stage0;  // (a copy local to the lambda, here and in read_k / read_v: hipcc orders the address arithmetic differently without)
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) {
-      const char* kbase = kb + (size_t)pc * bank_pstride * 2 + (size_t)step * (32 * 128);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dma16_nt(dst + pc * PSTR + i * 1024, koff[i], kbase);
-    }
-  };
-  auto issue_v = [&](int step) {
-    const uint32_t dst = stage0;  // (local copy: see issue_k)
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) {
-      const char* vbase = vt + (size_t)pc * bank_pstride * 2 + (size_t)step * 4096;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dma16(dst + pc * PSTR + XA_TILE + i * 1024, voff[i], vbase);
-    }
-  };
-  const int krow = 8 * (c >> 2) + (c & 3);  // + 4t: key row of S^T tile t this lane feeds
-  // the step's K / V^T fragments, pulled out of the stage into registers: the arithmetic works on registers only, so a half of the
-  // stage is re-filled as soon as its reads have returned
-  p16x8 kf[S][2][2], vf[S][4];
-  auto read_k = [&]() {
-    const char* stg = smem + wave * STAGE;  // (local to the lambda: see issue_k)
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc)
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int kd = 0; kd < 2; ++kd) {
-          const int r = krow + 4 * t;
-          kf[pc][t][kd] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + r * 128 + (((g + 4 * kd) ^ ksw(r)) << 4));
-        }
-  };
-  auto read_v = [&]() {
-    const char* stg = smem + wave * STAGE;  // (local to the lambda: see issue_k)
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const int d = 16 * mt + c;
-        vf[pc][mt] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + XA_TILE + d * 64 + ((g ^ vsw(d)) << 4));
-      }
-  };
+  auto issue_k = [&](int step) { xa_issue_k<S, PSTR>(stage0, kb, bank_pstride, step, koff); };
+  auto issue_v = [&](int step) { xa_issue_v<S, PSTR>(stage0, vt, bank_pstride, step, voff); };
+  p16x8 kf[S][2][2], vf[S][4];  // the step's K / V^T fragments
+  auto read_k = [&]() { xa_read_k<S, PSTR>(smem + wave * STAGE, c, g, kf); };
+  auto read_v = [&]() { xa_read_v<S, PSTR>(smem + wave * STAGE, c, g, vf); };
   p16x8 pf[S][NT];  // exp(S^T - max) of the step, as pieces: the B operand of O^T += V^T P^T
-  auto math_qk = [&](int step) {
-    const uint32_t kword = step < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)kb0, step) : (uint32_t)__builtin_amdgcn_readlane((int)kb1, step - 64);
-    const uint32_t kbits = kword >> (8 * g);  // this lane's keys 8g + 4t + j
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      f32x4 s[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int pr = 0; pr < T::NP; ++pr) {
-          a = mfma16(kf[T::A[pr]][t][0], qf[T::B[pr]][nt][0], a);
-          a = mfma16(kf[T::A[pr]][t][1], qf[T::B[pr]][nt][1], a);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = ((kbits >> (4 * t + j)) & 1u) ? a[j] : GRAM_FMIN;
-        s[t] = a;
-      }
-      float tm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
-                       fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-      tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-      const float mn = fmaxf(m[nt], tm);
-      const float alpha = __expf(m[nt] - mn);
-      m[nt] = mn;
-      float ps = 0.f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float e = __expf(s[t][j] - mn);
-          ps += e;
-#pragma unroll
-          for (int pc = 0; pc < S; ++pc) {
-            const p16 eb = (p16)e;
-            pf[pc][nt][4 * t + j] = eb;
-            e -= (float)eb;
-          }
-        }
-      l[nt] = xa_l_update(l[nt], alpha, ps);
-      // (One round-1 build of this kernel returned wrong values in dims 48-63; the cause was not this scaling -- whose packed
-      // multiply was blamed at the time -- but accumulators read by the loop's back-edge copies 2-7 wait states after their
-      // MFMA, through branches the compiler's hazard padding did not cover: DESIGN.md §4.3.  tools/check_isa_hazards.py
-      // checks every build for that, across the control-flow graph.)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) o[mt][nt] *= alpha;
-    }
-  };
-  auto math_pv = [&]() {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int pr = 0; pr < T::NP; ++pr) o[mt][nt] = mfma16(vf[T::A[pr]][mt], pf[T::B[pr]][nt], o[mt][nt]);
-  };
+
+  // the shared 32-key step (xattn_tile.h) on this kernel's registers.  (Through lambdas: called from the loop directly, hipcc promotes
+  // the arrays they capture to registers before it unrolls, and reschedules whole kernels.)
+  auto step_qk = [&](int step) { xa_step_qk<NT>(xa_kword(kb0, kb1, step), g, kf, qf, pf, m, l, o); };
+  auto step_pv = [&]() { xa_step_pv<NT>(vf, pf, o); };
 
   // Everything the first DMAs depend on (the key bits) is in; ordinary loads, the query fragments among them, are retired so that the
   // counted waits below see DMA instructions only.
@@ -286,7 +171,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the K fragments are in registers before their tiles are re-filled
       issue_k(nxt);
     }
-    math_qk(cur);
+    step_qk(cur);
     if (nxt < nsteps) wait_vm<4 * S>();  // (newest: the next step's K tiles)
     else wait_vm<0>();
     read_v();
@@ -294,7 +179,7 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       issue_v(nxt);
     }
-    math_pv();
+    step_pv();
     cur = nxt;
   }
 
@@ -353,15 +238,15 @@ __global__ __launch_bounds__(NW * 64) void cross_attn_kernel(
 // stages over (gram_sync(): the chaos build screens it).  The form with a private stage and a counted-wait pipeline per wave, as in
 // cross_attn_kernel, was measured too: its second request for a line is not reliably an L2 hit (13.8 GB per launch from beyond the
 // L2 against 10.7 GB here) and it was 0.4 ms per launch slower (profiles/xattn_entries_bench_ab.txt).
-// A row's arithmetic (S^T, online softmax, O^T, the merge of the two key-split partials) is the step-wise kernel's, instruction for
-// instruction per row, so a row's bits are those of cross_attn_kernel<.., S, NW> whatever tile of whatever entry holds it.
+// A row's arithmetic is the step-wise kernel's: both call the one 32-key step of xattn_tile.h (xa_step_qk, xa_step_pv) and the one
+// merge of the two key-split partials (xa_merge_w, xa_merge_o), and deal the valid steps to the waves alike, so a row's bits are those
+// of cross_attn_kernel<.., S, NW> whatever tile of whatever entry holds it.
 constexpr int XA_RUN_MERGE = 4 * (4 * 64 * 16 + 2 * 64 * 4);  // LDS per half for the merge: O, m, l of wave (p, 1) (aliases the stages)
 template <int S, int NW>
 __global__ __launch_bounds__(2 * NW * 64, 2) void cross_attn_runs_kernel(
     const p16* __restrict__ q, const p16* __restrict__ kbank, const p16* __restrict__ vtbank, const uint8_t* __restrict__ mask,
     p16* __restrict__ out, int n_entries, int H, int Sk, const int32_t* __restrict__ ent_users, const int32_t* __restrict__ ent_rows,
     long q_pstride, long bank_pstride, const uint32_t* __restrict__ key_bits) {
-  using T = SplitTab<S>;
   static_assert(NW == 1 || NW == 2, "the merge is written for two waves");
   constexpr int ER = GRAM_TAIL_ENTRY_ROWS;        // table slots per entry
   constexpr int MT = 4;                           // tiles per wave at most: half of a pair's eight
@@ -387,36 +272,11 @@ __global__ __launch_bounds__(2 * NW * 64, 2) void cross_attn_runs_kernel(
   const char* vt = reinterpret_cast<const char*>(vtbank + ((size_t)b * H + h) * 64 * Sk);
   const uint8_t* mk = mask + (size_t)b * Sk;
 
-  // the valid 32-key steps and their dealing to the waves of a key split: cross_attn_kernel's
+  // the valid 32-key steps (xa_key_steps) and their dealing to the waves of a key split, as in cross_attn_kernel
   const int nsteps = Sk >> 5;
-  uint32_t kb0 = 0, kb1 = 0;
-  if (key_bits) {
-    if (lane < nsteps) kb0 = key_bits[(size_t)b * 128 + lane];
-    if (lane + 64 < nsteps) kb1 = key_bits[(size_t)b * 128 + 64 + lane];
-  } else {
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int st = lane + 64 * hf;
-      uint32_t bits = 0;
-      if (st < nsteps) {
-        const uint4* p = reinterpret_cast<const uint4*>(mk + 32 * st);
-        const uint4 a = p[0], c2 = p[1];
-        const uint32_t w8[8] = {a.x, a.y, a.z, a.w, c2.x, c2.y, c2.z, c2.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bits |= ((w8[i] >> (8 * j)) & 0xffu) ? (1u << (4 * i + j)) : 0u;
-      }
-      if (hf == 0) kb0 = bits; else kb1 = bits;
-    }
-  }
-  unsigned long long v0 = __ballot(kb0 != 0u), v1 = __ballot(kb1 != 0u);
-  if ((v0 | v1) == 0ull) {  // no valid key at all: every step is kept (uniform softmax over all S keys)
-    v0 = nsteps >= 64 ? ~0ull : ((1ull << nsteps) - 1ull);
-    v1 = nsteps > 64 ? ((nsteps >= 128 ? ~0ull : ((1ull << (nsteps - 64)) - 1ull))) : 0ull;
-  }
-  v0 = __builtin_amdgcn_readfirstlane((unsigned)v0) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(v0 >> 32)) << 32);
-  v1 = __builtin_amdgcn_readfirstlane((unsigned)v1) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(v1 >> 32)) << 32);
+  uint32_t kb0, kb1;
+  unsigned long long v0, v1;
+  xa_key_steps(key_bits, mk, b, nsteps, lane, kb0, kb1, v0, v1);
   int ord = 0;  // ordinal of the next valid step (wave-uniform scalar state)
   auto next = [&](int s) -> int {
     for (s = s + 1; s < nsteps; ++s) {
@@ -443,30 +303,13 @@ __global__ __launch_bounds__(2 * NW * 64, 2) void cross_attn_runs_kernel(
   const uint32_t stage0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * 2 * STAGE;
   const int nvalid = __popcll(v0) + __popcll(v1);
   const int trips = (nvalid + NW - 1) / NW;  // key steps of wave (., 0): every wave of the workgroup meets this many barriers per sweep
-  auto issue_k = [&](int step, int buf) {
-    const uint32_t dst = stage0 + buf * STAGE;
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) {
-      const char* kbase = kb + (size_t)pc * bank_pstride * 2 + (size_t)step * (32 * 128);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dma16_nt(dst + pc * PSTR + i * 1024, koff[i], kbase);
-    }
-  };
-  auto issue_v = [&](int step, int buf) {
-    const uint32_t dst = stage0 + buf * STAGE;
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) {
-      const char* vbase = vt + (size_t)pc * bank_pstride * 2 + (size_t)step * 4096;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dma16(dst + pc * PSTR + XA_TILE + i * 1024, voff[i], vbase);
-    }
-  };
-  const int krow = 8 * (c >> 2) + (c & 3);  // + 4t: key row of S^T tile t this lane feeds
+  auto issue_k = [&](int step, int buf) { xa_issue_k<S, PSTR>(stage0 + buf * STAGE, kb, bank_pstride, step, koff); };
+  auto issue_v = [&](int step, int buf) { xa_issue_v<S, PSTR>(stage0 + buf * STAGE, vt, bank_pstride, step, voff); };
 
   f32x4 o[4][MT];
   float m[MT], l[MT];
   // one sweep of the slice for this wave's NL live tiles `tiles` (four bits each) of the pair whose table slots start at `rows`:
-  // cross_attn_kernel's arithmetic with NT = NL, step for step
+  // the shared step with NT = NL
   auto sweep = [&](auto nl_c, const int32_t* __restrict__ rows, int tiles) __attribute__((always_inline)) {
     constexpr int NL = decltype(nl_c)::value;
     constexpr int NA = NL > 0 ? NL : 1;  // (NL = 0: this half of the pair holds no live tile; the wave brings its tiles all the same)
@@ -488,81 +331,12 @@ __global__ __launch_bounds__(2 * NW * 64, 2) void cross_attn_runs_kernel(
           qf[pc][nt][kd] = qrow >= 0 ? ld_global_b128(q + pc * q_pstride + (size_t)qrow * inner + h * 64 + 32 * kd + 8 * g) : zero_bf16x8();
     }
     p16x8 kf[S][2][2], vf[S][4];
-    auto read_k = [&](int buf) {
-      const char* stg = smem + (wave * 2 + buf) * STAGE;
-#pragma unroll
-      for (int pc = 0; pc < S; ++pc)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int kd = 0; kd < 2; ++kd) {
-            const int r = krow + 4 * t;
-            kf[pc][t][kd] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + r * 128 + (((g + 4 * kd) ^ ksw(r)) << 4));
-          }
-    };
-    auto read_v = [&](int buf) {
-      const char* stg = smem + (wave * 2 + buf) * STAGE;
-#pragma unroll
-      for (int pc = 0; pc < S; ++pc)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          const int d = 16 * mt + c;
-          vf[pc][mt] = *reinterpret_cast<const p16x8*>(stg + pc * PSTR + XA_TILE + d * 64 + ((g ^ vsw(d)) << 4));
-        }
-    };
+    auto read_k = [&](int buf) { xa_read_k<S, PSTR>(smem + (wave * 2 + buf) * STAGE, c, g, kf); };
+    auto read_v = [&](int buf) { xa_read_v<S, PSTR>(smem + (wave * 2 + buf) * STAGE, c, g, vf); };
     p16x8 pf[S][NA];
-    auto math_qk = [&](int step) {
-      const uint32_t kword = step < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)kb0, step) : (uint32_t)__builtin_amdgcn_readlane((int)kb1, step - 64);
-      const uint32_t kbits = kword >> (8 * g);
-#pragma unroll
-      for (int nt = 0; nt < NL; ++nt) {
-        f32x4 s[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int pr = 0; pr < T::NP; ++pr) {
-            a = mfma16(kf[T::A[pr]][t][0], qf[T::B[pr]][nt][0], a);
-            a = mfma16(kf[T::A[pr]][t][1], qf[T::B[pr]][nt][1], a);
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) a[j] = ((kbits >> (4 * t + j)) & 1u) ? a[j] : GRAM_FMIN;
-          s[t] = a;
-        }
-        float tm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
-                         fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-        tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-        const float mn = fmaxf(m[nt], tm);
-        const float alpha = __expf(m[nt] - mn);
-        m[nt] = mn;
-        float ps = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float e = __expf(s[t][j] - mn);
-            ps += e;
-#pragma unroll
-            for (int pc = 0; pc < S; ++pc) {
-              const p16 eb = (p16)e;
-              pf[pc][nt][4 * t + j] = eb;
-              e -= (float)eb;
-            }
-          }
-        l[nt] = xa_l_update(l[nt], alpha, ps);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) o[mt][nt] *= alpha;
-      }
-    };
-    auto math_pv = [&]() {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NL; ++nt)
-#pragma unroll
-          for (int pr = 0; pr < T::NP; ++pr) o[mt][nt] = mfma16(vf[T::A[pr]][mt], pf[T::B[pr]][nt], o[mt][nt]);
-    };
+    // (through lambdas: see cross_attn_kernel)
+    auto step_qk = [&](int step) { xa_step_qk<NL>(xa_kword(kb0, kb1, step), g, kf, qf, pf, m, l, o); };
+    auto step_pv = [&]() { xa_step_pv<NL>(vf, pf, o); };
     wait_vm<0>();
 #pragma unroll
     for (int nt = 0; nt < NL; ++nt)
@@ -586,9 +360,9 @@ __global__ __launch_bounds__(2 * NW * 64, 2) void cross_attn_runs_kernel(
       if constexpr (NL > 0) {
         if (cur < nsteps) {
           read_k(buf);
-          math_qk(cur);
+          step_qk(cur);
           read_v(buf);
-          math_pv();
+          step_pv();
         }
       }
       cur = nxt;
@@ -756,15 +530,7 @@ int launch_cross_entries(const XaLaunch& a) {
 __global__ __launch_bounds__(128) void mask_key_bits_kernel(const uint8_t* __restrict__ mask, uint32_t* __restrict__ bits, int Sk) {
   const int b = blockIdx.x, st = threadIdx.x;
   uint32_t w = 0;
-  if (st < (Sk >> 5)) {
-    const uint4* p = reinterpret_cast<const uint4*>(mask + (size_t)b * Sk + 32 * st);
-    const uint4 a = p[0], c2 = p[1];
-    const uint32_t w8[8] = {a.x, a.y, a.z, a.w, c2.x, c2.y, c2.z, c2.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w |= ((w8[i] >> (8 * j)) & 0xffu) ? (1u << (4 * i + j)) : 0u;
-  }
+  if (st < (Sk >> 5)) w = xa_pack32(mask + (size_t)b * Sk + 32 * st);
   bits[(size_t)b * 128 + st] = w;
 }
 

@@ -2,8 +2,8 @@
 // (gram_model_set_max_fused_len; dec_attn.hip's cross_attn_kernel holds a user's key bits in two words per lane: <= 4096 keys).
 //
 // Split-key: a user's VALID 32-key steps, counted in key order, are cut into segments of 128; one workgroup of two waves per
-// (head, user, segment) runs dec_attn.hip's step loop over its segment -- the same 32-key K / V^T tiles by LDS-DMA (xattn_tile.h),
-// the same half-stage refill, the same three-product MFMA order, wave w owning the steps of ordinal parity w -- and merges the two
+// (head, user, segment) runs the 32-key step of xattn_tile.h (xa_step_qk, xa_step_pv) over its segment -- cross_attn_kernel's K / V^T
+// tiles by LDS-DMA, its half-stage refill, its three-product MFMA order, wave w owning the steps of ordinal parity w -- and merges the two
 // waves' partial softmaxes (m, l, O[64]) UNNORMALISED.  A user whose valid steps fit one segment is normalised and stored by that
 // workgroup; otherwise the segment leaves its partial in fp32 scratch and cross_attn_long_merge_kernel folds a row's partials in
 // ascending segment order, normalises, splits into pieces and stores.  No atomics; every sum has one fixed order.
@@ -68,7 +68,6 @@ __global__ __launch_bounds__(128) void cross_attn_long_kernel(
     const p16* __restrict__ q, const p16* __restrict__ kbank, const p16* __restrict__ vtbank, p16* __restrict__ out, int K, int H,
     int Sk, const int32_t* __restrict__ users, const int32_t* __restrict__ rowpos, long q_pstride, long bank_pstride,
     const uint32_t* __restrict__ key_bits, float* __restrict__ scratch) {
-  using T = SplitTab<S>;
   constexpr int NW = 2;
   constexpr int NB = NT * 16;        // padded beams
   constexpr int PSTR = 2 * XA_TILE;  // piece stride inside the stage: K tile | V^T tile
@@ -245,57 +244,9 @@ __global__ __launch_bounds__(128) void cross_attn_long_kernel(
       }
   };
   p16x8 pf[S][NT];  // exp(S^T - max) of the step, as pieces: the B operand of O^T += V^T P^T
-  auto math_qk = [&](uint32_t kword) {
-    const uint32_t kbits = kword >> (8 * g);  // this lane's keys 8g + 4t + j
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      f32x4 s[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int pr = 0; pr < T::NP; ++pr) {
-          a = mfma16(kf[T::A[pr]][t][0], qf[T::B[pr]][nt][0], a);
-          a = mfma16(kf[T::A[pr]][t][1], qf[T::B[pr]][nt][1], a);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = ((kbits >> (4 * t + j)) & 1u) ? a[j] : GRAM_FMIN;
-        s[t] = a;
-      }
-      float tm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
-                       fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-      tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-      const float mn = fmaxf(m[nt], tm);
-      const float alpha = __expf(m[nt] - mn);
-      m[nt] = mn;
-      float ps = 0.f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float e = __expf(s[t][j] - mn);
-          ps += e;
-#pragma unroll
-          for (int pc = 0; pc < S; ++pc) {
-            const p16 eb = (p16)e;
-            pf[pc][nt][4 * t + j] = eb;
-            e -= (float)eb;
-          }
-        }
-      l[nt] = xa_l_update(l[nt], alpha, ps);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) o[mt][nt] *= alpha;
-    }
-  };
-  auto math_pv = [&]() {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int pr = 0; pr < T::NP; ++pr) o[mt][nt] = mfma16(vf[T::A[pr]][mt], pf[T::B[pr]][nt], o[mt][nt]);
-  };
+  // the shared 32-key step on this kernel's registers (through lambdas: see cross_attn_kernel, dec_attn.hip)
+  auto step_qk = [&](uint32_t kword) { xa_step_qk<NT>(kword, g, kf, qf, pf, m, l, o); };
+  auto step_pv = [&]() { xa_step_pv<NT>(vf, pf, o); };
 
   // ordinary loads (the key bits, the query fragments) are retired so that the counted waits below see DMA instructions only
   wait_vm<0>();
@@ -305,7 +256,8 @@ __global__ __launch_bounds__(128) void cross_attn_long_kernel(
     for (int pc = 0; pc < S; ++pc)
 #pragma unroll
       for (int kd = 0; kd < 2; ++kd) asm volatile("" : "+v"(qf[pc][nt][kd]));
-  // one stage per wave, consumed and re-filled in halves: dec_attn.hip's loop
+  // one stage per wave, consumed and re-filled in halves, as in cross_attn_kernel; the arithmetic of a step is xattn_tile.h's.  (The DMA,
+  // the fragment reads and the query load stay spelled out: through the shared functions this kernel did not time inside the parent's spread.)
   int cur = next();
   if (cur < nsteps) {
     issue_k(cur);
@@ -320,7 +272,7 @@ __global__ __launch_bounds__(128) void cross_attn_long_kernel(
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the K fragments are in registers before their tiles are re-filled
       issue_k(nxt);
     }
-    math_qk(kword);
+    step_qk(kword);
     if (nxt < nsteps) wait_vm<4 * S>();  // (newest: the next step's K tiles)
     else wait_vm<0>();
     read_v();
@@ -329,7 +281,7 @@ __global__ __launch_bounds__(128) void cross_attn_long_kernel(
       issue_v(nxt);
     }
     if (any && kword != 0xffffffffu) mask_v(kword);
-    math_pv();
+    step_pv();
     cur = nxt;
   }
 
@@ -412,15 +364,7 @@ __global__ __launch_bounds__(256) void cross_attn_long_merge_kernel(const float*
 __global__ __launch_bounds__(512) void mask_key_bits_long_kernel(const uint8_t* __restrict__ mask, uint32_t* __restrict__ bits, int Sk) {
   const int b = blockIdx.x, st = threadIdx.x;
   uint32_t w = 0;
-  if (st < (Sk >> 5)) {
-    const uint4* p = reinterpret_cast<const uint4*>(mask + (size_t)b * Sk + 32 * st);
-    const uint4 a = p[0], c2 = p[1];
-    const uint32_t w8[8] = {a.x, a.y, a.z, a.w, c2.x, c2.y, c2.z, c2.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w |= ((w8[i] >> (8 * j)) & 0xffu) ? (1u << (4 * i + j)) : 0u;
-  }
+  if (st < (Sk >> 5)) w = xa_pack32(mask + (size_t)b * Sk + 32 * st);
   bits[(size_t)b * XL_STRIDE + st] = w;
   const int cnt = __syncthreads_count(w != 0u);
   if (st < XL_STRIDE - XL_WORDS) bits[(size_t)b * XL_STRIDE + XL_WORDS + st] = st == 0 ? (uint32_t)cnt : 0u;

@@ -3,8 +3,10 @@
 //
 //     probs[b][h][i][s] = softmax_s(q[b*Q + i] . k[b][h][s] + (mask[b][s] ? 0 : finfo.min)),  f32 [B][H][Q][S]
 //
-// A sibling of cross_attn_kernel (dec_attn.hip) without V: the same operand pieces, the same three-product order (SplitTab), the same
-// K tiles through LDS-DMA with the same swizzle (ksw) and the same key bits, so the numbers describe the attention the decoder applied.
+// A sibling of cross_attn_kernel (dec_attn.hip) without V: the same operand pieces, the scores and the online (max, sum) of xattn_tile.h
+// (xa_scores in the three-product order, xa_row_max, xa_l_update), the same K tiles through LDS-DMA with the same swizzle (ksw) and the
+// same key bits, so the numbers describe the attention the decoder applied.  The key-step setup, the DMA and the fragment reads stay
+// spelled out here: through the shared functions this kernel's schedule changes, and it did not time inside the parent's spread.
 // A row's normaliser (max, sum) is only known after the last key, so the bank's K is swept TWICE: sweep 1 keeps (m, l) per row,
 // sweep 2 recomputes the scores -- the same MFMAs on the same data: the same bits -- and stores exp(s - m) * (1 / l).  Nothing the
 // kernel writes is read back.
@@ -15,17 +17,10 @@
 // outputs are written as zeros.  A user without a valid key keeps every step: scores all finfo.min, probabilities uniform 1 / S.
 #include "common.h"
 #include "prof.h"
+#include "xattn_tile.h"
 
 namespace {
 
-// LDS-DMA through inline asm, streaming hint (dec_attn.hip's dma16_nt: the builtin makes hipcc wait lgkmcnt(0) in front of every DMA)
-__device__ __forceinline__ void xp_dma16(uint32_t lds_addr /*wave-uniform*/, uint32_t voff, const char* base /*uniform*/) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory");
-}
-// K tile [32 keys][128 B]: 16-B chunk ch of key row r sits at position ch ^ ksw(r) (dec_attn.hip: conflict-free fragment reads)
-__device__ __forceinline__ int xp_ksw(int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); }
-
-constexpr int XP_TILE = 4096;  // the K tile of a 32-key step, per piece
 constexpr int XP_NT = 2;       // 16-row MFMA tiles per wave: 32 query rows per workgroup
 constexpr int XP_ROWS = XP_NT * 16;
 
@@ -34,9 +29,8 @@ __global__ __launch_bounds__(64) void cross_attn_probs_kernel(const p16* __restr
                                                               const uint8_t* __restrict__ mask, float* __restrict__ probs, int Q, int H,
                                                               int Sk, long q_pstride, long bank_pstride,
                                                               const uint32_t* __restrict__ key_bits) {
-  using T = SplitTab<S>;
   constexpr int NT = XP_NT;
-  __shared__ __attribute__((aligned(16))) char smem[S * XP_TILE];  // the one stage: this step's K tile of every piece
+  __shared__ __attribute__((aligned(16))) char smem[S * XA_TILE];  // the one stage: this step's K tile of every piece
 
   const int h = blockIdx.x, b = blockIdx.y, row0 = blockIdx.z * XP_ROWS;
   const int lane = threadIdx.x;
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(64) void cross_attn_probs_kernel(const p16* __restr
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int kr = 8 * i + (lane >> 3);  // key row of the tile; the lane lands at position lane & 7 and fetches chunk pos ^ ksw
-    koff[i] = (uint32_t)(kr * 128 + (((lane & 7) ^ xp_ksw(kr)) << 4));
+    koff[i] = (uint32_t)(kr * 128 + (((lane & 7) ^ ksw(kr)) << 4));
   }
   const uint32_t stage0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   auto issue_k = [&](int step) {
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(64) void cross_attn_probs_kernel(const p16* __restr
     for (int pc = 0; pc < S; ++pc) {
       const char* kbase = kb + (size_t)pc * bank_pstride * 2 + (size_t)step * (32 * 128);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) xp_dma16(stage0 + pc * XP_TILE + i * 1024, koff[i], kbase);
+      for (int i = 0; i < 4; ++i) dma16_nt(stage0 + pc * XA_TILE + i * 1024, koff[i], kbase);
     }
   };
   const int krow = 8 * (c >> 2) + (c & 3);  // + 4t: key row of S^T tile t this lane feeds
@@ -131,25 +125,14 @@ __global__ __launch_bounds__(64) void cross_attn_probs_kernel(const p16* __restr
 #pragma unroll
         for (int kd = 0; kd < 2; ++kd) {
           const int r = krow + 4 * t;
-          kf[pc][t][kd] = *reinterpret_cast<const p16x8*>(smem + pc * XP_TILE + r * 128 + (((g + 4 * kd) ^ xp_ksw(r)) << 4));
+          kf[pc][t][kd] = *reinterpret_cast<const p16x8*>(smem + pc * XA_TILE + r * 128 + (((g + 4 * kd) ^ ksw(r)) << 4));
         }
   };
-  // S^T = K Q^T of the step for row tile nt: lane (c, g) holds row 16 nt + c, keys 8g + 4t + j; masked keys = finfo.min
+  // S^T = K Q^T of the step for row tile nt (xa_scores): lane (c, g) holds row 16 nt + c, keys 8g + 4t + j; masked keys = finfo.min
   auto scores = [&](int step, int nt, f32x4 (&s)[2]) {
-    const uint32_t kword = step < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)kb0, step) : (uint32_t)__builtin_amdgcn_readlane((int)kb1, step - 64);
-    const uint32_t kbits = kword >> (8 * g);
+    const uint32_t kbits = xa_kword(kb0, kb1, step) >> (8 * g);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int pr = 0; pr < T::NP; ++pr) {
-        a = mfma16(kf[T::A[pr]][t][0], qf[T::B[pr]][nt][0], a);
-        a = mfma16(kf[T::A[pr]][t][1], qf[T::B[pr]][nt][1], a);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[j] = ((kbits >> (4 * t + j)) & 1u) ? a[j] : GRAM_FMIN;
-      s[t] = a;
-    }
+    for (int t = 0; t < 2; ++t) s[t] = xa_scores(kf, qf, nt, t, kbits);
   };
 
   // ordinary loads (query fragments, key bits) are retired here: the waits of the sweeps see DMA instructions and stores only
@@ -191,18 +174,14 @@ __global__ __launch_bounds__(64) void cross_attn_probs_kernel(const p16* __restr
     for (int nt = 0; nt < NT; ++nt) {
       f32x4 s[2];
       scores(step, nt, s);
-      float tm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])), fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-      tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-      const float mn = fmaxf(m[nt], tm);
-      const float alpha = __expf(m[nt] - mn);
-      m[nt] = mn;
+      float alpha;
+      const float mn = xa_row_max(s, m[nt], alpha);
       float ps = 0.f;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int j = 0; j < 4; ++j) ps += __expf(s[t][j] - mn);
-      l[nt] = __builtin_fmaf(l[nt], alpha, ps);
+      l[nt] = xa_l_update(l[nt], alpha, ps);
     }
   });
   float inv[NT];
