@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ ta
 
 // embed_tokens for the folded-norm path: x (f32) + xb = bf16(x) + the row's sum of squares in ss[row][0]
 // embed_tokens for the folded-norm path: x (f32), its 16-bit copy xb and the row's 64-column partial sums of squares ss[row][d/64]
-// (nblk == d / 64; fewer: the row's total in ss[row][0] and zeros, the layout of round 1 -- no row factor then).
+// (nblk * 64 == d; any other nblk, or a d that is no multiple of 64: the row's total in ss[row][0] and zeros -- no row factor then).
 // xs_out != NULL: the copy is x * xs, xs the power-of-two factor of the row itself (row_xscale), written to xs_out[row]
 // xb == NULL: no copy is written (its first consumer reads a token table instead of running the layer-0 QKV GEMM on it)
 template <typename IdT>
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void embed_ex_kernel(const float* __restrict__
   const f32x4* src = reinterpret_cast<const f32x4*>(table + (size_t)ids[row] * d);
   f32x4* dst = reinterpret_cast<f32x4*>(x + (size_t)row * d);
   p16* dstb = xb + (size_t)row * d * pieces;
-  const bool blocks = nblk == d / 64;  // (d % 64 == 0 then: checked by the launcher)
+  const bool blocks = nblk * 64 == d;  // whole 64-column blocks only: any other (d, nblk) is the row-total form
   f32x4 v[4];  // d <= 1024
   float total = 0.f, minblk = INFINITY;
 #pragma unroll
@@ -146,7 +146,8 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
       s *= __expf(m - vm);
       m = vm;
     }
-    s += __expf(v[0] - m) + __expf(v[1] - m) + __expf(v[2] - m) + __expf(v[3] - m);
+    // (nothing but -inf so far: the terms would be exp(-inf + inf) = NaN, and the NaN would outlive the `* 0` below)
+    if (m > -INFINITY) s += __expf(v[0] - m) + __expf(v[1] - m) + __expf(v[2] - m) + __expf(v[3] - m);
   }
   float wm = wave_max(m);
   s *= (m == -INFINITY) ? 0.f : __expf(m - wm);

@@ -118,8 +118,8 @@ int gram_row_rscale(const float* ss, float* rs, int M, int nblk, int d, float ep
 /* The same with the row factors of the 16-bit copy (gram_norm_fusion_t): rs[m] = rsqrt(..) / xs_in[m] (xs_in NULL = 1) and, when
  * xs_out is given, xs_out[m] = the factor for the next producer (see xs_out above).  xs_out may not alias xs_in. */
 int gram_row_rscale_xs(const float* ss, float* rs, const float* xs_in, float* xs_out, int M, int nblk, int d, float eps, void* stream);
-/* embed_tokens for the folded path: x (f32), xb = bf16(x), ss[m][b] = the sum of squares of 64-column block b when nblk == d / 64
- * (any other nblk: the row's total in ss[m][0], zeros behind it). */
+/* embed_tokens for the folded path: x (f32), xb = bf16(x), ss[m][b] = the sum of squares of 64-column block b when nblk * 64 == d
+ * (any other nblk, or a d that is no multiple of 64: the row's total in ss[m][0], zeros behind it). */
 int gram_embed_ex(const float* table, const void* ids, int ids_are_i64, float* x, void* xb, float* ss, int nblk, int rows,
                   int d, void* stream);
 
@@ -279,7 +279,8 @@ int gram_cross_attn_decode(const void* q, const void* k_layer, const void* vt_la
 int gram_dec_self_attn(const void* qkv, void* kcache, void* vcache, const int32_t* anc,
                        const float* bias, void* out, int R, int H, int t, int Tmax, void* stream);
 
-/* lse[r] = log(sum_v exp(logits[r][v]))   (the normaliser of HF's log_softmax in beam_search). */
+/* lse[r] = log(sum_v exp(logits[r][v]))   (the normaliser of HF's log_softmax in beam_search).
+ * A logit of -inf adds nothing; a row of -inf throughout gives -inf. */
 int gram_row_lse(const float* logits, float* lse, int R, int V, void* stream);
 
 /* Flat Trie in HBM (CSR), built from generation_trie.py:5-68's nested dict by
