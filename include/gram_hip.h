@@ -648,10 +648,19 @@ typedef struct {
 } gram_forest_t;
 /* counts and offsets (one workgroup), the rows, slots and entries (one thread per user), the ancestor tables (one thread per row).
  * A forest of more than cap_rows rows or cap_entries entries writes its counts only: the caller reads them and goes on step by
- * step (as it does when a group's level holds more than B * K rows: a level's slots are cache rows).  t = position of the beams' rows. */
+ * step (as it does when a group's level holds more than B * K rows: a level's slots are cache rows).  t = position of the beams' rows.
+ * A user holds the rows tail->sub_rows promises for its live beams (at most cap_rows + 1 are counted per user).  A table that
+ * promises more rows than the Trie holds below those beams sets st->error[0] = 3 -- a soft flag, as every beam-state error -- and
+ * the rows promised and not found become harmless copies of a start row behind the user's real rows: pad token, pos t, parent -1,
+ * root b * K, node -1, slots of level 0 like any row's; no beam's gram_tail_rowpos points at one.
+ * What is written: counts [4 + 2 * GRAM_TAIL_MAX_STEPS], user_off and ent_off [B + 1] always; for a forest that fits, the row arrays
+ * and slot [counts[0]], ent_users and ent_rows [counts[1]], per (group, level < n_levels) the first counts[4 + ...] cells of lvl_rows
+ * and lvl_tokens, and of lvl_anc the columns of the slots < B * K: the positions < t and those of the row's ancestors (< Tmax), not
+ * the row's own.  A row at level >= n_levels gets slot -1 and no table cell.  rowpos is gram_tail_rowpos's.  Nothing else is touched. */
 int gram_tail_forest(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const gram_trie_tail_t* tail_host,
                      const gram_forest_t* forest_host, int t, void* stream);
-/* forest.rowpos for the coming search step: the forest row whose node is the beam's, -1 for a beam that is not live. */
+/* forest.rowpos for the coming search step: the forest row whose node is the beam's (the first of its user's rows), -1 for a beam
+ * that is not live.  A live beam whose node none of its user's rows holds sets st->error[0] = 3 and gets row 0. */
 int gram_tail_rowpos(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const gram_forest_t* forest_host, void* stream);
 /* dst row rows[i] = src row i, for i < n: rows of row_bytes bytes (a multiple of 16); an index outside [0, dst_rows) is skipped.  The
  * tail pass runs its self-attention level by level with the step-wise kernel, on the level's rows gathered by slot, and puts the

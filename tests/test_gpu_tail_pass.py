@@ -3,7 +3,9 @@
 Everything here is a comparison of raw bits (torch.equal).  Whole calls: sequences, scores and every array of the beam state after
 every replayed step -- a call with max_length cut to t + 2 ends right behind the search step of position t, and the test hook
 gram_debug_workspace_beam_state says where the workspace keeps the state.  The pass is forced with gram_debug_set_tail_pass(1): by
-default calls this small decode step by step (gram_tail_pass_wanted).  Kernels: the entry cross-attention against
+default calls this small decode step by step (gram_tail_pass_wanted) -- but for the calls of 2049 users, which the size rule itself
+sends through the pass, and which reach the row counts of the persistent GEMM.  Kernels: the forest's tables against
+tests/tail_oracle.py (more of that in tests/test_gpu_tail_forest.py); the entry cross-attention against
 gram_cross_attn_decode_split on groups of K rows, on forests of up to 65 rows per user; the scatter of the level results.  (The
 pass's self-attention is the step-wise kernel itself.)"""
 import ctypes as C
@@ -11,7 +13,7 @@ import ctypes as C
 import pytest
 import torch
 
-from tests.test_tail_pass_host import BRANCHY, BUSHY, CHAIN, RAGGED
+from tests.test_tail_pass_host import BRANCHY, BUSHY, CHAIN, RAGGED, WIDE
 
 pytestmark = pytest.mark.gpu
 SENT = 0x5A5A  # 16-bit sentinel pattern (a finite number in IEEE half and in bfloat16)
@@ -41,9 +43,9 @@ def _bits(t):
     return t.view(torch.int16)
 
 
-def _model(G, pieces):
+def _model(G, pieces, heads=2):
     from tests.test_gpu_token_tables import _model as tiny
-    return tiny(G, pieces)
+    return tiny(G, pieces, heads)
 
 
 _FNS = {}
@@ -94,18 +96,25 @@ def _inputs(B, N, L, pad_passage, seed):
     return mk(torch.Generator().manual_seed(seed), B, N, L, 256, pad_passage)
 
 
-def _compare(G, m, ids, mask, cands, K, want_tail, live=-1, **kw):
-    """tail pass on against off at every cut of max_length behind a replayed step (and the full call)"""
+def _compare(G, m, ids, mask, cands, K, want_tail, live=-1, cuts=None, on=1, **kw):
+    """tail pass on against off at every cut of max_length behind a replayed step (and the full call), or at the given cuts.
+    on = None: the "on" runs come first and nobody touches the switch before them, so that the size rule decides
+    (gram_tail_pass_wanted)."""
     from gram_amd.utils.generation_trie import FlatTrie, Trie
     lib = G.lib()
     d_tail = FlatTrie(Trie(cands)).tail_tables()[1]
     full = max(len(c) for c in cands)
-    cuts = range(max(d_tail, 2) + 1, full + 1) if want_tail else [full]
-    ran = []
+    if cuts is None:
+        cuts = range(max(d_tail, 2) + 1, full + 1) if want_tail else [full]
+    ran, by_size = [], {}
+    if on is None:
+        lib.gram_debug_set_live_rows(live)
+        by_size = {T: _run(G, m, ids, mask, cands, K, T, **kw) for T in cuts}
     for T in cuts:
         lib.gram_debug_set_live_rows(live)
-        lib.gram_debug_set_tail_pass(1)
-        seq_on, sc_on, st_on, last = _run(G, m, ids, mask, cands, K, T, **kw)
+        if on is not None:
+            lib.gram_debug_set_tail_pass(on)
+        seq_on, sc_on, st_on, last = by_size[T] if on is None else _run(G, m, ids, mask, cands, K, T, **kw)
         lib.gram_debug_set_tail_pass(0)
         seq_off, sc_off, st_off, last_off = _run(G, m, ids, mask, cands, K, T, **kw)
         ran.append(last[0])
@@ -186,23 +195,50 @@ def test_a_level_over_the_cache_rows_goes_on_step_by_step(G, pieces):
     _compare(G, m, ids, mask, RAGGED, 4, want_tail=True)
 
 
+@pytest.mark.parametrize("pieces,heads", [(2, 2), (1, 4)])  # one layer's bank: 4 * B * heads * (N * L = 128) * 64 * pieces bytes
+@pytest.mark.parametrize("cands,K,live", [(RAGGED, 20, 1), (BRANCHY, 4, 0)], ids=["ragged-K20-live", "branchy-K4-live-off"])
+def test_the_size_rule_takes_the_pass_at_256_MB_of_bank_and_the_call_stays_bit_identical(G, cands, K, live, pieces, heads):
+    """No switch and no environment variable for the "on" run: gram_tail_pass_wanted decides (generate.hip, tail_wanted).  2047 users
+    hold one byte less than 256 MB of bank per layer, 2049 more.  At K = 20 the step's 40 980 rows and the forest's rows put every
+    GEMM of the pass and the lm_head on the persistent ping-pong kernel, with an M tail; each level's cache rows serve both user
+    groups in turn."""
+    from gram_amd.utils.generation_trie import FlatTrie, Trie
+    m, lib = _model(G, pieces, heads), G.lib()
+    N, L, handle = 2, 64, m._pack()
+    d_tail, full = FlatTrie(Trie(cands)).tail_tables()[1], max(len(c) for c in cands)
+    assert lib.gram_tail_pass_wanted(handle, 2047, N, L) == 0 and lib.gram_tail_pass_wanted(handle, 2049, N, L) == 1
+    ids, mask = _inputs(2049, N, L, False, 2049 + K)
+    lib.gram_debug_set_live_rows(live)
+    _seq, _sc, state, last = _run(G, m, ids[:2047], mask[:2047], cands, K, full)
+    assert last == [0, 0, 0, 0] and int(state["error"].view(torch.int32)[0]) == 0  # (no forest was built)
+    last = _compare(G, m, ids, mask, cands, K, want_tail=True, live=live, cuts=[d_tail + 2, full], on=None)
+    assert last[0] == 1 and last[1] >= 2049 * K  # (every beam is live at d_tail)
+    if K == 20:
+        assert last[1] > 32768  # (the forest's GEMMs take the ping-pong kernel as the step's do)
+    print(f"\nB=2049 K={K} pieces={pieces} heads={heads}: forest rows {last[1]}, entries {last[2]}, most rows of one user {last[3]}")
+
+
+@pytest.mark.parametrize("pieces", [2, 1])
+@pytest.mark.parametrize("B,K,by_size", [(3, 20, False), (3, 40, False), (17, 20, False), (2049, 20, True)],
+                         ids=["B3-K20-two-entries", "B3-K40-three-entries", "B17-K20", "B2049-K20-by-size"])
+def test_a_forest_of_more_than_64_rows_per_user_is_bit_identical_to_stepping(G, B, K, by_size, pieces):
+    """WIDE gives every beam four steps and 4 to 6 rows: 20 beams hold 80 to 120 forest rows -- two cross-attention entries per user,
+    one full and one partial, as on the Beauty Trie -- and 40 beams three."""
+    m = _model(G, pieces, 4 // pieces if by_size else 2)
+    ids, mask = _inputs(B, 2, 64, False, 300 * B + K)
+    if by_size:
+        assert G.lib().gram_tail_pass_wanted(m._pack(), B, 2, 64) == 1
+        last = _compare(G, m, ids, mask, WIDE, K, want_tail=True, cuts=[max(len(c) for c in WIDE)], on=None)
+        print(f"\nB={B} K={K} pieces={pieces}: forest rows {last[1]}, entries {last[2]}, most rows of one user {last[3]}")
+    else:
+        last = _compare(G, m, ids, mask, WIDE, K, want_tail=True)
+    if K == 20:
+        assert 65 <= last[3] <= 128 and last[2] >= B + 1
+    else:
+        assert last[3] > 128 and last[2] >= 2 * B + 1
+
+
 # ------------------------------------------------------------------------------------ 2. the forest and its self-attention
-def _forest_buffers(G, B, K, Tmax, cap, n_levels):
-    from gram_amd import _lib
-    i32 = dict(dtype=torch.int32, device=G.DEV)
-    ents = cap // _lib.GRAM_TAIL_ENTRY_ROWS + B
-    R = B * K
-    t = dict(tokens=torch.full((cap,), -7, **i32), pos=torch.full((cap,), -7, **i32), parent=torch.full((cap,), -7, **i32),
-             root=torch.full((cap,), -7, **i32), node=torch.full((cap,), -7, **i32), user_off=torch.full((B + 1,), -7, **i32),
-             ent_off=torch.full((B + 1,), -7, **i32), ent_users=torch.full((ents,), -7, **i32),
-             ent_rows=torch.full((ents, _lib.GRAM_TAIL_ENTRY_ROWS), -7, **i32), rowpos=torch.full((R,), -7, **i32),
-             counts=torch.full((4 + 2 * _lib.GRAM_TAIL_MAX_STEPS,), -7, **i32), slot=torch.full((cap,), -7, **i32),
-             lvl_rows=torch.full((2, n_levels, cap), -7, **i32), lvl_tokens=torch.full((2, n_levels, cap), -7, **i32),
-             lvl_anc=torch.full((2, n_levels, Tmax, R), -7, **i32))
-    f = _lib.Forest(**{k: v.data_ptr() for k, v in t.items()}, cap_rows=cap, cap_entries=ents, n_levels=n_levels, pad_=0)
-    return f, t
-
-
 @pytest.mark.parametrize("pieces", [2, 1])
 @pytest.mark.parametrize("table", [False, True])
 def test_forest_tables_and_level_self_attention_equal_a_plain_enumeration_and_the_stepwise_kernel(G, table, pieces):
@@ -211,9 +247,9 @@ def test_forest_tables_and_level_self_attention_equal_a_plain_enumeration_and_th
     self-attention -- gram_dec_self_attn[_rows]_split per group and level on the rows gathered by slot, with the forest's own
     ancestor tables, the second group on the first's cache rows, gram_scatter_rows -- against the same kernel run level by level
     with a plain ancestor table in which every forest row owns a cache row (at most 64 rows), bit for bit."""
-    import numpy as np
     from gram_amd import _lib
     from gram_amd.utils.generation_trie import FlatTrie, Trie
+    from tests import tail_oracle
     flat = FlatTrie(Trie(BRANCHY))
     sub, d_tail, steps = flat.tail_tables()
     assert (d_tail, steps) == (3, 3)
@@ -233,28 +269,17 @@ def test_forest_tables_and_level_self_attention_equal_a_plain_enumeration_and_th
     keep["tokens"].copy_(torch.tensor([[p[-1] if p else 0 for p in row] for row in prefixes], dtype=torch.int32).flatten())
     keep["done"].copy_(torch.tensor([0, 0, 0, 1], dtype=torch.int32))  # (user 3 is finished: no rows)
     keep["anc"].copy_(torch.randint(0, R, (Tmax, R), generator=g).to(torch.int32))
-    f, ft = _forest_buffers(G, B, K, Tmax, cap, steps)
+    state = dict(node=keep["node"].cpu().numpy(), tokens=keep["tokens"].cpu().numpy(), done=keep["done"].cpu().numpy(),
+                 anc=keep["anc"].cpu().numpy())
+    f, ft, whole, layout = tail_oracle.forest_buffers(dev, B, K, Tmax, cap, steps)
     _lib.check(G.lib().gram_tail_forest(C.byref(st), C.byref(ctrie), C.byref(tail), C.byref(f), t, G.stream()), "gram_tail_forest")
     torch.cuda.synchronize()
-    # ---- the plain enumeration
-    fan = np.diff(flat.child_off)
-    rows, user_off = [], [0]  # (token, pos, parent, root, node)
-    for b in range(B):
-        base = len(rows)
-        if b != 3:
-            for k in range(K):
-                n = node[b][k]
-                if n >= 0 and fan[n] > 0:
-                    rows.append((prefixes[b][k][-1], t, -1, b * K + k, n))
-            head = base
-            while head < len(rows):
-                _tok, pos, _par, root, n = rows[head]
-                for e in range(int(flat.child_off[n]), int(flat.child_off[n + 1])):
-                    c = int(flat.child_node[e])
-                    if fan[c] > 0:
-                        rows.append((int(flat.child_tok[e]), pos + 1, head, root, c))
-                head += 1
-        user_off.append(len(rows))
+    # ---- the plain enumeration (tests/tail_oracle.py): every cell of every table and the guard bands, then the tables one by one
+    E = tail_oracle.enumerate_forest(flat, sub, state, B, K, t, cap, f.cap_entries, steps)
+    tail_oracle.check_forest(E, whole, layout, state["anc"], Tmax)
+    rows = list(zip(*(getattr(E, name).tolist() for name in tail_oracle.ROW_ARRAYS)))  # (token, pos, parent, root, node)
+    user_off = E.user_off.tolist()
+    assert user_off[4] == user_off[3] and all(r[4] >= 0 for r in rows)  # (the finished user owns no row; no row is a copy)
     n = len(rows)
     assert 20 <= n <= cap and any(r[1] > t and sum(1 for q in rows if q[2] == i) > 1 for i, r in enumerate(rows))  # (a fork below d_tail)
     counts = ft["counts"].cpu().tolist()
