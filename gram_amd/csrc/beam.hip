@@ -18,6 +18,8 @@
 // One workgroup per user; users are independent, so this shards trivially.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "prof.h"
 #include "sparse_dot.h"
@@ -138,6 +140,16 @@ struct StepArgs {
 // ---- per-user item filters (gram_user_items_t).  FILT is a compile-time property of the step kernels: the unfiltered instantiations
 // carry none of this.  The alive test below is the ONE definition that the key builders (dense_window, sparse_window, shared0_keys),
 // flag_nonfinite_keys (through the zero key), step_finish (the ranked walk and the filler loop) and the greedy step all share.
+// A step kernel's filter is its trailing parameter pack UI: nothing (unfiltered: the parameter list and the code of a kernel without
+// the pack) or one gram_user_items_t (FILT).
+template <typename... UI>
+constexpr bool filtered() {
+  static_assert(sizeof...(UI) == 0 || (sizeof...(UI) == 1 && (std::is_same_v<UI, gram_user_items_t> && ...)),
+                "a step kernel's trailing pack is empty or one gram_user_items_t");
+  return sizeof...(UI) != 0;
+}
+__device__ __forceinline__ const gram_user_items_t* items_ptr() { return nullptr; }
+__device__ __forceinline__ const gram_user_items_t* items_ptr(const gram_user_items_t& u) { return &u; }
 
 // first index in r[0, n) whose value is >= v
 __device__ __forceinline__ int rank_lower_bound(const int32_t* __restrict__ r, int n, int v) {
@@ -223,7 +235,7 @@ __device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, in
 // K keys of each.  The caller puts a barrier behind it.
 // FILT: a candidate whose child node is not alive for the user gets the zero key ("nothing", below every real key) and no dot product;
 // the shared step-0 row computes every child's logit and leaves the test to shared0_keys.
-template <int NTHR, bool FILT = false>
+template <int NTHR, bool FILT>
 __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, float* s_log, int b, int tid,
                                               int c0, int n, bool shared0) {
   const gram_beam_state_t& st = a.st;
@@ -286,7 +298,7 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
 // step 0's shared row: the keys of beams [k0, k0 + kg) x children [j0, j0 + nj) of the shared node, from the nj logits that
 // sparse_window left in s_log: kw[(k - k0) * nj + (j - j0)].  (k0 = j0 = 0, kg = K, nj = the node's fan-out: the user's whole list
 // in its flat-index order)
-template <int NTHR, bool FILT = false>
+template <int NTHR, bool FILT>
 __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared& sh, unsigned long long* kw, const float* s_log, int b,
                                              int tid, int j0, int nj, int k0, int kg) {
   const gram_beam_state_t& st = a.st;
@@ -304,7 +316,7 @@ __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared
 }
 
 // DENSE mode, gather: log_softmax at the allowed tokens + running beam score.  Candidates [c0, c0 + n) -> kw[0, n); kw[n, npad) = 0
-template <int NTHR, bool FILT = false>
+template <int NTHR, bool FILT>
 __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, int b, int tid, int c0, int n,
                                              int npad) {
   const gram_beam_state_t& st = a.st;
@@ -333,7 +345,7 @@ __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared
 // all its candidates into -inf / NaN -- either way the search would go on and return an ordinary-looking ranking without them.
 // -inf candidates are legitimate (HF's -inf refills of finished beams).  Every candidate's key passes through here before the
 // selection can drop it.  FILT: the zero key of a dead candidate is no score (a real key's low word is never 0) and is passed over.
-template <int NTHR, bool FILT = false>
+template <int NTHR, bool FILT>
 __device__ __forceinline__ void flag_nonfinite_keys(const StepArgs& a, const unsigned long long* kw, int n, int tid) {
   for (int i = tid; i < n; i += NTHR) {
     if constexpr (FILT)
@@ -404,7 +416,7 @@ __device__ __forceinline__ void top_p_select(unsigned long long* keys, int NC, i
 // all).  BeamSearchScorer.process on one thread, then the sequences / ancestor table / per-row state are advanced through
 // new_seq [K][Tmax] / new_anc [Tmax][K] (LDS).  FILT: the zero keys of dead candidates sort last, so the ranking ends at the first
 // one, and a filler token is any token that is not an ALIVE child of beam 0's node.
-template <int NTHR, bool FILT = false>
+template <int NTHR, bool FILT>
 __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int* new_seq, int* new_anc,
                                             int b, int tid) {
   const gram_beam_state_t& st = a.st;
@@ -527,13 +539,15 @@ constexpr int kOneShotMaxKeys = 16384;  // K * max_fanout the one-shot kernel ta
 
 // ONE-SHOT form: all of a user's candidates in LDS at once (K * max_fanout <= 16 384 and the LDS sum below within the CU's 160 KB).
 // NTHR threads per workgroup (= per user): 256 for batches that fill the chip with workgroups; 1 024 for small batches, where one user's
-// sparse logits (a trip computes NTHR / 4 candidates' dot products, each on its 8 lanes) and sort stages are the step's latency
-template <int NTHR>
+// sparse logits (a trip computes NTHR / 4 candidates' dot products, each on its 8 lanes) and sort stages are the step's latency.
+// UI: the per-user item filter (filtered(), above)
+template <int NTHR, typename... UI>
 __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
                                                         const float* __restrict__ lse, int V, int cur_len, int nc_max, int rows_per_user,
                                                         const p16* __restrict__ hd, const p16* __restrict__ emb, int d,
                                                         const int32_t* __restrict__ rowpos, int pieces,
-                                                        const float* __restrict__ emb32, const float* __restrict__ pre) {
+                                                        const float* __restrict__ emb32, const float* __restrict__ pre, UI... ui) {
+  constexpr bool FILT = filtered<UI...>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nc_max]
   float* s_log = reinterpret_cast<float*>(keys + nc_max);                   // [max_fanout, rounded up to 4] shared step-0 logits
@@ -541,7 +555,7 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
   int* new_seq = reinterpret_cast<int*>(smem + (size_t)nc_max * 8 + ((size_t)tr.max_fanout * 4 + 15) / 16 * 16);
   int* new_anc = new_seq + st.K * st.Tmax;
   __shared__ StepShared sh;
-  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max};
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max, items_ptr(ui...)};
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int K = st.K;
@@ -552,74 +566,26 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
   if (!isdone && logits == nullptr) {
     for (int ci = C + tid; ci < NC; ci += NTHR) keys[ci] = 0ull;
     const bool shared0 = rows_per_user == 1;
-    sparse_window<NTHR>(a, sh, keys, s_log, b, tid, 0, shared0 ? sh.pre[1] : C, shared0);
+    sparse_window<NTHR, FILT>(a, sh, keys, s_log, b, tid, 0, shared0 ? sh.pre[1] : C, shared0);
     if (shared0) {
       gram_sync();
-      shared0_keys<NTHR>(a, sh, keys, s_log, b, tid, 0, sh.pre[1], 0, K);
+      shared0_keys<NTHR, FILT>(a, sh, keys, s_log, b, tid, 0, sh.pre[1], 0, K);
     }
     gram_sync();
   }
   if (!isdone && logits != nullptr) {
-    dense_window<NTHR>(a, sh, keys, b, tid, 0, C, NC);
+    dense_window<NTHR, FILT>(a, sh, keys, b, tid, 0, C, NC);
     gram_sync();
   }
   if (!isdone) {
-    flag_nonfinite_keys<NTHR>(a, keys, C, tid);
+    flag_nonfinite_keys<NTHR, FILT>(a, keys, C, tid);
     flag_nonfinite_lse(a, sh, b, tid);
     int P = 64;
     while (P < 2 * K) P <<= 1;
     top_p_select<NTHR, kOneShotMaxKeys>(keys, NC, P, tid);
   }
-  step_finish<NTHR>(a, sh, keys, new_seq, new_anc, b, tid);
+  step_finish<NTHR, FILT>(a, sh, keys, new_seq, new_anc, b, tid);
 }
-// ... with per-user item filters (gram_user_items_t).  beam_step_kernel's text with the filtered (FILT = true) forms of the pieces; the
-// unfiltered kernel above keeps its own text, and with it its code object, instruction for instruction.
-template <int NTHR>
-__global__ __launch_bounds__(NTHR) void beam_step_items_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
-                                                              const float* __restrict__ lse, int V, int cur_len, int nc_max,
-                                                              int rows_per_user, const p16* __restrict__ hd, const p16* __restrict__ emb,
-                                                              int d, const int32_t* __restrict__ rowpos, int pieces,
-                                                              const float* __restrict__ emb32, const float* __restrict__ pre,
-                                                              gram_user_items_t ui) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nc_max]
-  float* s_log = reinterpret_cast<float*>(keys + nc_max);                   // [max_fanout, rounded up to 4] shared step-0 logits
-  // [K][Tmax] + [Tmax][K]: the advanced sequences / ancestor table on their way back to HBM (sized by the call, not by the maxima)
-  int* new_seq = reinterpret_cast<int*>(smem + (size_t)nc_max * 8 + ((size_t)tr.max_fanout * 4 + 15) / 16 * 16);
-  int* new_anc = new_seq + st.K * st.Tmax;
-  __shared__ StepShared sh;
-  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max, &ui};
-
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int K = st.K;
-  step_setup(a, sh, b, tid, nc_max);
-  const int C = sh.C, NC = sh.NC;
-  const bool isdone = sh.isdone != 0;
-
-  if (!isdone && logits == nullptr) {
-    for (int ci = C + tid; ci < NC; ci += NTHR) keys[ci] = 0ull;
-    const bool shared0 = rows_per_user == 1;
-    sparse_window<NTHR, true>(a, sh, keys, s_log, b, tid, 0, shared0 ? sh.pre[1] : C, shared0);
-    if (shared0) {
-      gram_sync();
-      shared0_keys<NTHR, true>(a, sh, keys, s_log, b, tid, 0, sh.pre[1], 0, K);
-    }
-    gram_sync();
-  }
-  if (!isdone && logits != nullptr) {
-    dense_window<NTHR, true>(a, sh, keys, b, tid, 0, C, NC);
-    gram_sync();
-  }
-  if (!isdone) {
-    flag_nonfinite_keys<NTHR, true>(a, keys, C, tid);
-    flag_nonfinite_lse(a, sh, b, tid);
-    int P = 64;
-    while (P < 2 * K) P <<= 1;
-    top_p_select<NTHR, kOneShotMaxKeys>(keys, NC, P, tid);
-  }
-  step_finish<NTHR, true>(a, sh, keys, new_seq, new_anc, b, tid);
-}
-
 // CHUNKED form: any fan-out.  The candidates stream through a fixed key array: keys[0, P) carry the best P keys so far (descending;
 // zero keys -- below every real key, whose low word is never 0 -- while fewer have been seen), keys[P, P + n) take the next n <= cap
 // candidates, the same top-P selection runs over the power of two >= P + n, and so on until the list is exhausted.  The keys are
@@ -640,19 +606,21 @@ __global__ __launch_bounds__(NTHR) void beam_step_items_kernel(gram_beam_state_t
 constexpr int kChunkKeys = 4096;
 constexpr int kChunkLog = 2048;
 
-template <int NTHR>
+// (UI: as in beam_step_kernel)
+template <int NTHR, typename... UI>
 __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
                                                                 const float* __restrict__ lse, int V, int cur_len, int cap,
                                                                 int rows_per_user, const p16* __restrict__ hd,
                                                                 const p16* __restrict__ emb, int d, const int32_t* __restrict__ rowpos,
-                                                                int pieces, const float* __restrict__ emb32) {
+                                                                int pieces, const float* __restrict__ emb32, UI... ui) {
+  constexpr bool FILT = filtered<UI...>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [kChunkKeys]
   float* s_log = reinterpret_cast<float*>(keys + kChunkKeys);              // [kChunkLog]
   int* new_seq = reinterpret_cast<int*>(s_log + kChunkLog);                // [K][Tmax] + [Tmax][K], as in the one-shot kernel
   int* new_anc = new_seq + st.K * st.Tmax;
   __shared__ StepShared sh;
-  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0};
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0, items_ptr(ui...)};
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int K = st.K;
@@ -674,19 +642,19 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
       while (na < P + n) na <<= 1;
       for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
       gram_sync();
-      flag_nonfinite_keys<NTHR>(a, kw, n, tid);
+      flag_nonfinite_keys<NTHR, FILT>(a, kw, n, tid);
       top_p_select<NTHR, kChunkKeys>(keys, na, P, tid);
     };
     if (logits != nullptr) {
       for (int c0 = 0; c0 < C; c0 += cap) {
         const int n = C - c0 < cap ? C - c0 : cap;
-        dense_window<NTHR>(a, sh, kw, b, tid, c0, n, n);
+        dense_window<NTHR, FILT>(a, sh, kw, b, tid, c0, n, n);
         merge(n);
       }
     } else if (rows_per_user != 1) {
       for (int c0 = 0; c0 < C; c0 += cap) {
         const int n = C - c0 < cap ? C - c0 : cap;
-        sparse_window<NTHR>(a, sh, kw, s_log, b, tid, c0, n, false);
+        sparse_window<NTHR, FILT>(a, sh, kw, s_log, b, tid, c0, n, false);
         merge(n);
       }
     } else {
@@ -694,89 +662,19 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
       const int njmax = cap < kChunkLog ? cap : kChunkLog;
       for (int j0 = 0; j0 < cnt0; j0 += njmax) {
         const int nj = cnt0 - j0 < njmax ? cnt0 - j0 : njmax;
-        sparse_window<NTHR>(a, sh, kw, s_log, b, tid, j0, nj, true);
+        sparse_window<NTHR, FILT>(a, sh, kw, s_log, b, tid, j0, nj, true);
         gram_sync();
         const int kgmax = cap / nj;  // >= 1
         for (int k0 = 0; k0 < K; k0 += kgmax) {
           const int kg = K - k0 < kgmax ? K - k0 : kgmax;
-          shared0_keys<NTHR>(a, sh, kw, s_log, b, tid, j0, nj, k0, kg);
+          shared0_keys<NTHR, FILT>(a, sh, kw, s_log, b, tid, j0, nj, k0, kg);
           merge(kg * nj);
         }
       }
     }
   }
-  step_finish<NTHR>(a, sh, keys, new_seq, new_anc, b, tid);
+  step_finish<NTHR, FILT>(a, sh, keys, new_seq, new_anc, b, tid);
 }
-// ... with per-user item filters: beam_step_chunked_kernel's text with the filtered forms of the pieces (see beam_step_items_kernel)
-template <int NTHR>
-__global__ __launch_bounds__(NTHR) void beam_step_chunked_items_kernel(gram_beam_state_t st, gram_trie_t tr,
-                                                                      const float* __restrict__ logits, const float* __restrict__ lse,
-                                                                      int V, int cur_len, int cap, int rows_per_user,
-                                                                      const p16* __restrict__ hd, const p16* __restrict__ emb, int d,
-                                                                      const int32_t* __restrict__ rowpos, int pieces,
-                                                                      const float* __restrict__ emb32, gram_user_items_t ui) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [kChunkKeys]
-  float* s_log = reinterpret_cast<float*>(keys + kChunkKeys);              // [kChunkLog]
-  int* new_seq = reinterpret_cast<int*>(s_log + kChunkLog);                // [K][Tmax] + [Tmax][K], as in the one-shot kernel
-  int* new_anc = new_seq + st.K * st.Tmax;
-  __shared__ StepShared sh;
-  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0, &ui};
-
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int K = st.K;
-  step_setup(a, sh, b, tid, 0);
-  const int C = sh.C;
-  const bool isdone = sh.isdone != 0;
-
-  if (!isdone) {
-    flag_nonfinite_lse(a, sh, b, tid);
-    int P = 64;
-    while (P < 2 * K) P <<= 1;
-    if (cap > kChunkKeys - P) cap = kChunkKeys - P;  // (the launcher's job; a wrong value must not reach past the array)
-    if (cap < 1) cap = 1;
-    unsigned long long* kw = keys + P;
-    for (int i = tid; i < P; i += NTHR) keys[i] = 0ull;  // nothing carried yet
-    // kw[0, n) hold fresh keys (all threads behind a barrier or not: one follows the padding)
-    auto merge = [&](int n) {
-      int na = 2 * P;  // the power of two >= P + n
-      while (na < P + n) na <<= 1;
-      for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
-      gram_sync();
-      flag_nonfinite_keys<NTHR, true>(a, kw, n, tid);
-      top_p_select<NTHR, kChunkKeys>(keys, na, P, tid);
-    };
-    if (logits != nullptr) {
-      for (int c0 = 0; c0 < C; c0 += cap) {
-        const int n = C - c0 < cap ? C - c0 : cap;
-        dense_window<NTHR, true>(a, sh, kw, b, tid, c0, n, n);
-        merge(n);
-      }
-    } else if (rows_per_user != 1) {
-      for (int c0 = 0; c0 < C; c0 += cap) {
-        const int n = C - c0 < cap ? C - c0 : cap;
-        sparse_window<NTHR, true>(a, sh, kw, s_log, b, tid, c0, n, false);
-        merge(n);
-      }
-    } else {
-      const int cnt0 = sh.pre[1];
-      const int njmax = cap < kChunkLog ? cap : kChunkLog;
-      for (int j0 = 0; j0 < cnt0; j0 += njmax) {
-        const int nj = cnt0 - j0 < njmax ? cnt0 - j0 : njmax;
-        sparse_window<NTHR, true>(a, sh, kw, s_log, b, tid, j0, nj, true);
-        gram_sync();
-        const int kgmax = cap / nj;  // >= 1
-        for (int k0 = 0; k0 < K; k0 += kgmax) {
-          const int kg = K - k0 < kgmax ? K - k0 : kgmax;
-          shared0_keys<NTHR, true>(a, sh, kw, s_log, b, tid, j0, nj, k0, kg);
-          merge(kg * nj);
-        }
-      }
-    }
-  }
-  step_finish<NTHR, true>(a, sh, keys, new_seq, new_anc, b, tid);
-}
-
 // The sparse logits of a search step, computed by MANY workgroups (a handful of users: beam_step_kernel's one workgroup per user pulls
 // up to K * fan-out fp32 lm_head rows -- 15 MB at K = 20, fan-out 255 -- through ONE CU, 70 us on average and up to 290 us of a one-user
 // step).  Workgroup (chunk, user) recomputes the user's candidate list exactly as beam_step_kernel does (beams in order, each beam's
@@ -933,7 +831,9 @@ __global__ void beam_finalize_kernel(gram_beam_state_t st, int nret, int max_len
 // Trie children (first maximum wins, like torch.argmax on the -inf-masked row; no children -> index 0),
 // finished users emit pad.  done[b] doubles as HF's (1 - unfinished_sequences); n_hyps[b] records the
 // sequence length at which the user finished (0 = still running) for the final width.
-__global__ void greedy_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits, int V, int cur_len) {
+// UI (filtered(), above): the argmax runs over the children that are alive for the user (node_alive).
+template <typename... UI>
+__global__ void greedy_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits, int V, int cur_len, UI... ui) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= st.B) return;
   const int T = st.Tmax;
@@ -946,6 +846,8 @@ __global__ void greedy_step_kernel(gram_beam_state_t st, gram_trie_t tr, const f
       float best = -INFINITY;
       bool any = false;
       for (int e = lo; e < hi; ++e) {
+        if constexpr (filtered<UI...>())
+          if (!node_alive(*items_ptr(ui...), b, tr.child_node[e])) continue;
         const int c = tr.child_tok[e];
         const float v = logits[(size_t)b * V + c];
         // children are sorted by token: strict > keeps the first maximum; a -inf logit at a lower index than
@@ -967,44 +869,6 @@ __global__ void greedy_step_kernel(gram_beam_state_t st, gram_trie_t tr, const f
   st.tokens[b] = tok;
   st.node[b] = next_node;
 }
-// greedy_step_kernel with per-user item filters: the argmax runs over the children that are alive for the user (node_alive)
-__global__ void greedy_step_items_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits, int V, int cur_len,
-                                         gram_user_items_t ui) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= st.B) return;
-  const int T = st.Tmax;
-  int tok = st.pad, next_node = -1;
-  if (!st.done[b]) {
-    const int nd = st.node[b];
-    tok = 0;  // argmax of an all -inf row
-    if (nd >= 0) {
-      const int lo = tr.child_off[nd], hi = tr.child_off[nd + 1];
-      float best = -INFINITY;
-      bool any = false;
-      for (int e = lo; e < hi; ++e) {
-        if (!node_alive(ui, b, tr.child_node[e])) continue;
-        const int c = tr.child_tok[e];
-        const float v = logits[(size_t)b * V + c];
-        // children are sorted by token: strict > keeps the first maximum; a -inf logit at a lower index than
-        // an allowed -inf one cannot happen for finite model outputs, NaN is never selected over a number
-        if (!any || v > best) {
-          best = v;
-          tok = c;
-          next_node = tr.child_node[e];
-          any = true;
-        }
-      }
-    }
-    if (tok == st.eos) {
-      st.done[b] = 1;
-      st.n_hyps[b] = cur_len + 1;
-    }
-  }
-  st.seq[(size_t)b * T + cur_len] = tok;
-  st.tokens[b] = tok;
-  st.node[b] = next_node;
-}
-
 // A call's per-user item lists -> sorted distinct leaf ranks (gram_user_items_prepare).  One workgroup per user: the list's entries
 // become leaf ranks (padding and out-of-range indices become INT32_MAX, above every rank), a bitonic sort in LDS puts them in
 // ascending order, and every thread compacts its slice of the sorted array behind an exclusive scan of the slices' distinct counts.
@@ -1335,7 +1199,24 @@ static int check_items(const gram_user_items_t* it) {
   return 0;
 }
 
-// items != nullptr: the step's form with per-user item filters (the *_items kernels); nullptr: exactly the launches of before
+// One search step, one workgroup per user: the 1 024-thread instantiation of a form when `wide`, its 256-thread one otherwise.  Both
+// are allowed `smem` bytes of dynamic LDS first; the high-water mark is the pair's own (a static of this template's instantiation).
+template <auto kStep256, auto kStep1024, typename... Args>
+static int launch_step_pair(bool wide, int B, size_t smem, hipStream_t stream, const Args&... args) {
+  static size_t attr_bytes = 0;
+  if (smem > attr_bytes) {
+    for (const void* f : {reinterpret_cast<const void*>(kStep256), reinterpret_cast<const void*>(kStep1024)})
+      if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); e != hipSuccess) return (int)e;
+    attr_bytes = smem;
+  }
+  if (wide) hipLaunchKernelGGL(kStep1024, dim3(B), dim3(1024), smem, stream, args...);
+  else hipLaunchKernelGGL(kStep256, dim3(B), dim3(256), smem, stream, args...);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+// items != nullptr: the step's form with per-user item filters (the <NTHR, gram_user_items_t> instantiations of the step kernels);
+// nullptr: exactly the launches of before
 static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                             int cur_len, int rows_per_user, const void* hd, const void* emb, int d, const int32_t* rowpos,
                             void* stream, int pieces = 1, const float* emb32 = nullptr, const gram_user_items_t* items = nullptr) {
@@ -1355,6 +1236,7 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
   // few users: one workgroup per user leaves the chip empty and the step is that workgroup's latency -> 1 024 threads per user
   // (same per-candidate arithmetic, same total order of the keys: identical results; GRAM_BEAM_WIDE_MAXB: A/B hook, 0 = never)
   static const int wide_max_b = getenv("GRAM_BEAM_WIDE_MAXB") ? atoi(getenv("GRAM_BEAM_WIDE_MAXB")) : 128;
+  const bool wide = st->B <= wide_max_b;
   if (chunked) {
     // 32-bit scalar state of the kernel: the flat index k * V + tok < K * V, and the candidate count and its prefix sums <= K * V
     // (a node has at most V children)
@@ -1364,54 +1246,12 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
     int cap = kChunkKeys - P;
     if (g_beam_chunk_cap > 0 && g_beam_chunk_cap < cap) cap = g_beam_chunk_cap;
     const size_t smem = (size_t)kChunkKeys * 8 + (size_t)kChunkLog * 4 + seq_bytes;  // <= 40 KB + 64 KB
-    static size_t attr_bytes = 0;
-    if (smem > attr_bytes) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_kernel<256>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem);
-      if (e != hipSuccess) return (int)e;
-      attr_bytes = smem;
-    }
-    if (items) {
-      static size_t items_attr_bytes = 0;
-      if (smem > items_attr_bytes) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_items_kernel<256>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e == hipSuccess)
-          e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_chunked_items_kernel<1024>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-        items_attr_bytes = smem;
-      }
-      if (st->B <= wide_max_b)
-        hipLaunchKernelGGL(beam_step_chunked_items_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse,
-                           V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, *items);
-      else
-        hipLaunchKernelGGL(beam_step_chunked_items_kernel<256>, dim3(st->B), dim3(256), smem, (hipStream_t)stream, *st, *tr, logits, lse,
-                           V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, *items);
-      GRAM_CHECK_LAUNCH();
-      return 0;
-    }
-    if (st->B <= wide_max_b)
-      hipLaunchKernelGGL(beam_step_chunked_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse, V,
-                         cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32);
-    else
-      hipLaunchKernelGGL(beam_step_chunked_kernel<256>, dim3(st->B), dim3(256), smem, (hipStream_t)stream, *st, *tr, logits, lse, V,
-                         cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32);
-    GRAM_CHECK_LAUNCH();
-    return 0;
-  }
-  const size_t smem = smem_one;
-  static size_t attr_bytes = 0;
-  if (smem > attr_bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)smem);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_bytes = smem;
+    auto launch = [&](auto... ui) {
+      return launch_step_pair<beam_step_chunked_kernel<256, decltype(ui)...>, beam_step_chunked_kernel<1024, decltype(ui)...>>(
+          wide, st->B, smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d,
+          rowpos, pieces, emb32, ui...);
+    };
+    return items ? launch(*items) : launch();
   }
   // a handful of users: the sparse logits by their own kernel over many CUs (sparse_logits_kernel), the search step reads them
   // (gram_beam_state_t.cand_logits: caller-provided scratch; GRAM_BEAM_PRE_MAXB: A/B hook, 0 = never)
@@ -1424,35 +1264,12 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
     GRAM_CHECK_LAUNCH();
     pre = st->cand_logits;
   }
-  const int nc_arg = nc;
-  if (items) {
-    static size_t items_attr_bytes = 0;
-    if (smem > items_attr_bytes) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_items_kernel<256>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_items_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem);
-      if (e != hipSuccess) return (int)e;
-      items_attr_bytes = smem;
-    }
-    if (st->B <= wide_max_b)
-      hipLaunchKernelGGL(beam_step_items_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len,
-                         nc_arg, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, pre, *items);
-    else
-      hipLaunchKernelGGL(beam_step_items_kernel<256>, dim3(st->B), dim3(256), smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len,
-                         nc_arg, rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, pre, *items);
-    GRAM_CHECK_LAUNCH();
-    return 0;
-  }
-  if (st->B <= wide_max_b)
-    hipLaunchKernelGGL(beam_step_kernel<1024>, dim3(st->B), dim3(1024), smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nc_arg,
-                       rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, pre);
-  else
-    hipLaunchKernelGGL(beam_step_kernel<256>, dim3(st->B), dim3(256), smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nc_arg,
-                       rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, pre);
-  GRAM_CHECK_LAUNCH();
-  return 0;
+  auto launch = [&](auto... ui) {
+    return launch_step_pair<beam_step_kernel<256, decltype(ui)...>, beam_step_kernel<1024, decltype(ui)...>>(
+        wide, st->B, smem_one, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nc, rows_per_user, (const p16*)hd, (const p16*)emb, d,
+        rowpos, pieces, emb32, pre, ui...);
+  };
+  return items ? launch(*items) : launch();
 }
 
 extern "C" int gram_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
@@ -1562,26 +1379,28 @@ extern "C" int gram_tail_rowpos(const gram_beam_state_t* st, const gram_trie_t* 
   return 0;
 }
 
-extern "C" int gram_greedy_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, int V, int cur_len,
-                               void* stream) {
+// what the two greedy entry points share: the state checks and the launch.  ui: nothing, or the lists (checked by the caller)
+template <typename... UI>
+static int launch_greedy_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, int V, int cur_len, void* stream,
+                              const UI&... ui) {
   if (int e = check_state(st)) return e;
   if (!tr || st->K != 1 || cur_len < 1 || cur_len >= st->Tmax || V < 2) return GRAM_E_ARG;
   gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
-  hipLaunchKernelGGL(greedy_step_kernel, dim3((st->B + 127) / 128), dim3(128), 0, (hipStream_t)stream, *st, *tr, logits, V, cur_len);
+  hipLaunchKernelGGL(greedy_step_kernel<UI...>, dim3((st->B + 127) / 128), dim3(128), 0, (hipStream_t)stream, *st, *tr, logits, V, cur_len,
+                     ui...);
   GRAM_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int gram_greedy_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, int V, int cur_len,
+                               void* stream) {
+  return launch_greedy_step(st, tr, logits, V, cur_len, stream);
 }
 
 extern "C" int gram_greedy_step_items(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, int V, int cur_len,
                                       const gram_user_items_t* items, void* stream) {
   if (int e = check_items(items)) return e;
-  if (int e = check_state(st)) return e;
-  if (!tr || st->K != 1 || cur_len < 1 || cur_len >= st->Tmax || V < 2) return GRAM_E_ARG;
-  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
-  hipLaunchKernelGGL(greedy_step_items_kernel, dim3((st->B + 127) / 128), dim3(128), 0, (hipStream_t)stream, *st, *tr, logits, V, cur_len,
-                     *items);
-  GRAM_CHECK_LAUNCH();
-  return 0;
+  return launch_greedy_step(st, tr, logits, V, cur_len, stream, *items);
 }
 
 extern "C" int gram_greedy_finalize(const gram_beam_state_t* st, int max_length, int64_t* sequences, int32_t* out_width,

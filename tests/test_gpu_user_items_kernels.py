@@ -2,12 +2,14 @@
 at every launch form.  tests/test_gpu_user_items.py covers them through whole generate() calls on a tiny model; here the shapes
 are chosen so that every instantiation runs.  launch_beam_step picks the form from B and the Trie alone:
 
-    B <= 16 and a state with cand_logits ("scratch")   sparse_logits_kernel, then beam_step_items_kernel<1024> reading its logits
-    B <= 128 (17 .. 128, or <= 16 without scratch)     beam_step_items_kernel<1024>, dot products in the kernel: the dead flag
-                                                       parked in bit 63 of the key slot, dot(act && !dead)
-    B >= 129                                           beam_step_items_kernel<256>
-    K * max_fanout > 16 384 or too much LDS            beam_step_chunked_items_kernel<1024> (B <= 128) / <256> (B >= 129); the
-                                                       same two under gram_debug_set_beam_chunked(1) on any shape ("forced")
+    B <= 16 and a state with cand_logits ("scratch")   sparse_logits_kernel, then beam_step_kernel<1024, gram_user_items_t> reading
+                                                       its logits
+    B <= 128 (17 .. 128, or <= 16 without scratch)     beam_step_kernel<1024, gram_user_items_t>, dot products in the kernel: the
+                                                       dead flag parked in bit 63 of the key slot, dot(act && !dead)
+    B >= 129                                           beam_step_kernel<256, gram_user_items_t>
+    K * max_fanout > 16 384 or too much LDS            beam_step_chunked_kernel<1024, gram_user_items_t> (B <= 128) / <256, ...>
+                                                       (B >= 129); the same two under gram_debug_set_beam_chunked(1) on any shape
+                                                       ("forced")
     rowpos != NULL                                     the live-row form of whichever kernel the shape selects
 
 Each of them runs below with exclude and with allow lists, on one-piece (gram_beam_step_sparse_items) and two-piece
@@ -528,9 +530,9 @@ SEARCH_CASES = [
     ("grid16", 8, 64, 1, True),                # P = 128, lists of thousands of ranks: 12-level searches; user 3 keeps 3 of 4 096
     ("grid16", 8, 64, 2, True),
     ("grid16", 129, 20, 2, False),             # <256> with long lists
-    ("second300", 2, 64, 1, False),            # chunked by its shape: beam_step_chunked_items_kernel<1024>
+    ("second300", 2, 64, 1, False),            # chunked by its shape: beam_step_chunked_kernel<1024, gram_user_items_t>
     ("second300", 2, 64, 2, False),
-    ("root900", 129, 20, 2, False),            # beam_step_chunked_items_kernel<256>: step 0's shared row over several chunk rounds
+    ("root900", 129, 20, 2, False),            # beam_step_chunked_kernel<256, gram_user_items_t>: step 0's shared row over several chunk rounds
     ("beauty", 2, 20, 2, True),                # real fan-out 255; 4 096 exclusions per user
 ]
 
@@ -575,7 +577,7 @@ def _candidate_counts(case, snaps):
 @gpu
 @pytest.mark.parametrize("name,B,K,pieces,scratch", [c for c in SEARCH_CASES if c[:3] in (("ragged", 8, 4), ("grid16", 8, 64)) and c[4]])
 def test_filtered_search_forced_chunked_matches_one_shot(G, name, B, K, pieces, scratch):
-    """beam_step_chunked_items_kernel forced onto shapes the one-shot kernel takes, at chunk capacities on and around the search's
+    """beam_step_chunked_kernel<..., gram_user_items_t> forced onto shapes the one-shot kernel takes, at chunk capacities on and around the search's
     own candidate counts: the bits of the one-shot filtered run after every step, node and error included"""
     from tests.test_gpu_wide_trie import _boundary_caps
     w = _world(G, name, B, K, pieces, scratch)
