@@ -20,13 +20,16 @@
 // (2) dec_self_attn_kernel: causal self-attention of the newest token over <= 32 cached
 //     positions with beam-parent indirection (anc table) instead of the reference's
 //     torch.cat + index_select of the whole cache (gram_t5_modeling.py:536-540,
-//     gram_t5.py:320-348); unidirectional relative bias, last query row (:586-593).
+//     gram_t5.py:320-348); unidirectional relative bias, last query row (:586-593).  The arithmetic of a row is self_attn_row.h's,
+//     the one text that tf_attn.hip's and tree_attn.hip's self-attention kernels call too: a cached decode step and the same
+//     prefix in a teacher-forced sequence or in the Trie pass give the same bits by construction.
 //
 // Both kernels take their bf16 operands as 1 or 2 pieces (GRAM_MAX_PIECES; gram_split_t in gram_hip.h).
 #include <type_traits>
 
 #include "common.h"
 #include "prof.h"
+#include "self_attn_row.h"
 #include "xattn_tile.h"
 
 namespace {
@@ -550,41 +553,26 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const p16* __restric
   const int r = rows ? rows[rc] : rc;
   const int inner = H * 64, h = i >> 4;
   const p16* row = qkv + (size_t)(qkv_rows ? qkv_rows[rc] : rc) * 3 * inner + 4 * i;
-  // values as the fp32 sum of their pieces (exact for two pieces, one rounding for three); the pieces themselves go to the cache
-  float qf[4] = {0.f, 0.f, 0.f, 0.f}, kn[4] = {0.f, 0.f, 0.f, 0.f}, vn[4] = {0.f, 0.f, 0.f, 0.f};
+  // the new position's pieces go to the cache as they are
+  p16x4 q4[S], k4[S], v4[S];
 #pragma unroll
-  for (int pc = S - 1; pc >= 0; --pc) {  // smallest piece first
-    const p16x4 q4 = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps);
-    const p16x4 k4 = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps + inner);
-    const p16x4 v4 = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps + 2 * inner);
-    *reinterpret_cast<p16x4*>(kcache + pc * cache_ps + ((size_t)t * R + r) * inner + 4 * i) = k4;
-    *reinterpret_cast<p16x4*>(vcache + pc * cache_ps + ((size_t)t * R + r) * inner + 4 * i) = v4;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      qf[e] += (float)q4[e];
-      kn[e] += (float)k4[e];
-      vn[e] += (float)v4[e];
-    }
+  for (int pc = 0; pc < S; ++pc) {
+    q4[pc] = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps);
+    k4[pc] = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps + inner);
+    v4[pc] = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps + 2 * inner);
+    *reinterpret_cast<p16x4*>(kcache + pc * cache_ps + ((size_t)t * R + r) * inner + 4 * i) = k4[pc];
+    *reinterpret_cast<p16x4*>(vcache + pc * cache_ps + ((size_t)t * R + r) * inner + 4 * i) = v4[pc];
   }
-  float m = -INFINITY, l = 0.f, acc[4] = {0.f, 0.f, 0.f, 0.f};
-  auto attend = [&](int j, const float (&kj)[4], const float (&vj)[4]) {  // online softmax over the positions, in order
-    float s = qf[0] * kj[0] + qf[1] * kj[1] + qf[2] * kj[2] + qf[3] * kj[3];
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    s += __shfl_xor(s, 8, 64);
-    s += bias[h * GRAM_MAX_DEC_LEN + (t - j)];
-    const float mn = fmaxf(m, s);
-    const float alpha = __expf(m - mn);
-    const float p = __expf(s - mn);
-    m = mn;
-    l = l * alpha + p;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = acc[e] * alpha + p * vj[e];
+  float qf[4], kn[4], vn[4], m = -INFINITY, l = 0.f, acc[4] = {0.f, 0.f, 0.f, 0.f};
+  sa_sum<S>(q4, qf);
+  sa_sum<S>(k4, kn);
+  sa_sum<S>(v4, vn);
+  auto attend = [&](int j, const float (&kj)[4], const float (&vj)[4]) {  // position j, in order
+    sa_step(qf, kj, vj, bias[h * GRAM_MAX_DEC_LEN + (t - j)], m, l, acc);
   };
   // Cached positions in batches of U: the U ancestor indices go out together, then the 2 * S * U row loads they address -- two
   // round trips per batch.  (One position per loop trip was ancestor load -> row loads -> arithmetic, strictly in sequence:
-  // 2 t dependent round trips per block, 7 us per block at the bench shape.)  The arithmetic and its order are unchanged.
+  // 2 t dependent round trips per block, 7 us per block at the bench shape.)  The positions are still taken in order.
   constexpr int U = 8;
   for (int j0 = 0; j0 < t; j0 += U) {
     int a[U];
@@ -603,33 +591,15 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const p16* __restric
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (j0 + u < t) {
-        float kj[4] = {0.f, 0.f, 0.f, 0.f}, vj[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int pc = S - 1; pc >= 0; --pc)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            kj[e] += (float)kk[u][pc][e];
-            vj[e] += (float)vv[u][pc][e];
-          }
+        float kj[4], vj[4];
+        sa_sum<S>(kk[u], kj);
+        sa_sum<S>(vv[u], vj);
         attend(j0 + u, kj, vj);
       }
     }
   }
   attend(t, kn, vn);
-  const float inv = 1.f / l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) acc[e] *= inv;
-#pragma unroll
-  for (int pc = 0; pc < S; ++pc) {
-    p16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      o[e] = (p16)acc[e];
-      acc[e] -= (float)o[e];
-    }
-    // (S == 2: interleaved rows [2 * inner], the O GEMM's A operand)
-    *reinterpret_cast<p16x4*>(out + (size_t)rc * inner * S + (S == 2 ? inter_off(4 * i, pc) : 4 * i)) = o;
-  }
+  sa_store<S>(out + (size_t)rc * inner * S, 4 * i, l, acc);
 }
 
 }  // namespace

@@ -7,9 +7,9 @@
 //     q|k|v straight from the QKV GEMM's planar output: no cache, no ancestor table.  One workgroup per (sequence, head); the
 //     sequence's keys and values (fp32 sums of their pieces) sit in LDS, 16 lanes per query, 4 dims per lane.
 //     VALU, not MFMA: the ids of the "split" / "t5_token" types are ~10 tokens, so a 16x16 tile would be mostly padding, and the
-//     kernel is bound by reading the q|k|v rows once (T * 64 * 2 flops per key against 3 * 128 B per row and piece).  It also keeps
-//     the arithmetic of dec_attn.hip's stepped kernel -- the same online softmax over positions 0..t in order, the same lane sums --
-//     so a teacher-forced position and a cached decode step compute the same expression.
+//     kernel is bound by reading the q|k|v rows once (T * 64 * 2 flops per key against 3 * 128 B per row and piece).  The
+//     arithmetic of a row is self_attn_row.h's, the one text that dec_attn.hip's stepped kernel and tree_attn.hip's kernel call
+//     too: a teacher-forced position and a cached decode step over the same prefix give the same bits by construction.
 // (2) the cross-attention of Q = C * T query rows per user over that user's bank: dec_attn.hip's cross_attn_kernel takes <= 64 rows
 //     per user, so Q <= 64 calls it directly (K = Q) and Q > 64 calls its live-row form once per group of <= 64 rows, with offset
 //     q / out pointers and a row table that maps (user, row of the group) to b * Q + row.  Each group re-reads the bank.
@@ -17,6 +17,7 @@
 //     function, the same bits as a beam-search logit), seq_logp = the sum over the sequence in position order (no float atomics).
 #include "common.h"
 #include "prof.h"
+#include "self_attn_row.h"
 #include "sparse_dot.h"
 
 namespace {
@@ -24,74 +25,25 @@ namespace {
 template <int S>
 __global__ __launch_bounds__(256) void dec_self_attn_tf_kernel(const p16* __restrict__ qkv, const float* __restrict__ bias,
                                                                p16* __restrict__ out, int T, int H, long qkv_ps) {
-  __shared__ float ks[GRAM_MAX_DEC_LEN][64], vs[GRAM_MAX_DEC_LEN][64];
+  __shared__ float ks[GRAM_MAX_DEC_LEN][16][4], vs[GRAM_MAX_DEC_LEN][16][4];  // [position][lane of the 16][dim]
   const int sq = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
   const int inner = H * 64, l16 = tid & 15, grp = tid >> 4, ngrp = blockDim.x >> 4;
   const size_t row0 = (size_t)sq * T;
-  // keys and values of the sequence as the fp32 sum of their pieces, smallest first (dec_self_attn_kernel's order)
+  // keys and values of the sequence, summed over their pieces once
   for (int idx = tid; idx < T * 16; idx += blockDim.x) {
-    const int j = idx >> 4, c4 = (idx & 15) * 4;
-    const p16* row = qkv + (row0 + j) * 3 * inner + h * 64 + c4;
-    float kj[4] = {0.f, 0.f, 0.f, 0.f}, vj[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int pc = S - 1; pc >= 0; --pc) {
-      const p16x4 k4 = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps + inner);
-      const p16x4 v4 = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps + 2 * inner);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        kj[e] += (float)k4[e];
-        vj[e] += (float)v4[e];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      ks[j][c4 + e] = kj[e];
-      vs[j][c4 + e] = vj[e];
-    }
+    const int j = idx >> 4, c = idx & 15;
+    const p16* row = qkv + (row0 + j) * 3 * inner + h * 64 + 4 * c;
+    sa_load<S>(row + inner, qkv_ps, ks[j][c]);
+    sa_load<S>(row + 2 * inner, qkv_ps, vs[j][c]);
   }
   __syncthreads();
   // every 16-lane group walks its queries t = grp, grp + ngrp, ... (the loop bound is uniform per group: the lane sums stay whole)
   for (int t = grp; t < T; t += ngrp) {
-    const p16* row = qkv + (row0 + t) * 3 * inner + h * 64 + 4 * l16;
-    float qf[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int pc = S - 1; pc >= 0; --pc) {
-      const p16x4 q4 = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) qf[e] += (float)q4[e];
-    }
-    float m = -INFINITY, l = 0.f, acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j <= t; ++j) {  // causal: positions 0..t, in order
-      const float* kj = &ks[j][4 * l16];
-      const float* vj = &vs[j][4 * l16];
-      float s = qf[0] * kj[0] + qf[1] * kj[1] + qf[2] * kj[2] + qf[3] * kj[3];
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
-      s += bias[h * GRAM_MAX_DEC_LEN + (t - j)];
-      const float mn = fmaxf(m, s);
-      const float alpha = __expf(m - mn);
-      const float p = __expf(s - mn);
-      m = mn;
-      l = l * alpha + p;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = acc[e] * alpha + p * vj[e];
-    }
-    const float inv = 1.f / l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] *= inv;
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) {
-      p16x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] = (p16)acc[e];
-        acc[e] -= (float)o[e];
-      }
-      const int n = h * 64 + 4 * l16;  // (S == 2: interleaved rows [2 * inner], the O GEMM's A operand)
-      *reinterpret_cast<p16x4*>(out + (row0 + t) * inner * S + (S == 2 ? inter_off(n, pc) : n)) = o;
-    }
+    float qf[4], m = -INFINITY, l = 0.f, acc[4] = {0.f, 0.f, 0.f, 0.f};
+    sa_load<S>(qkv + (row0 + t) * 3 * inner + h * 64 + 4 * l16, qkv_ps, qf);
+    for (int j = 0; j <= t; ++j)  // causal: positions 0..t, in order
+      sa_step(qf, ks[j][l16], vs[j][l16], bias[h * GRAM_MAX_DEC_LEN + (t - j)], m, l, acc);
+    sa_store<S>(out + (row0 + t) * inner * S, h * 64 + 4 * l16, l, acc);
   }
 }
 

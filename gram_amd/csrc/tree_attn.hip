@@ -3,41 +3,28 @@
 //
 // (1) dec_self_attn_tree_kernel: causal self-attention where row i attends to the rows anc[i][0..pos[i]] of its user -- its
 //     ancestors in the Trie and itself (T5Attention.forward self branch with the causal mask and the unidirectional relative bias of
-//     layer 0, gram_t5_modeling.py:586-593, on the prefix the row stands for; gram_t5.py:181-263).  The arithmetic restates
-//     tf_attn.hip's dec_self_attn_tf_kernel expression for expression and rounding for rounding (see the kernel) -- K/V/Q as the
-//     fp32 sum of their pieces, smallest first; 16 lanes per query, 4 dims per lane, the shfl_xor 1, 2, 4, 8 lane sum; bias by
-//     distance added after the sum; the online softmax over positions 0..t in order; the same piece split of the output -- so a tree
-//     row and the same prefix in a teacher-forced sequence give the same bits.  16 queries per workgroup; the ancestors' K/V rows are
-//     read through L2 (neighbouring rows are siblings and cousins: the four queries of a wave mostly ask for the same lines).  No
-//     LDS, no barrier.
+//     layer 0, gram_t5_modeling.py:586-593, on the prefix the row stands for; gram_t5.py:181-263).  The arithmetic of a row is
+//     self_attn_row.h's, the one text that tf_attn.hip's dec_self_attn_tf_kernel and dec_attn.hip's stepped kernel call too, so a
+//     tree row, the same prefix in a teacher-forced sequence and the same prefix in a cached decode step give the same bits by
+//     construction.  16 queries per workgroup; the ancestors' K/V rows are read through L2 (neighbouring rows are siblings and
+//     cousins: the four queries of a wave mostly ask for the same lines).  No LDS, no barrier.
 // (2) trie_row_edge_kernel / trie_leaf_kernel: log p of every edge below a row from the final hidden rows (sparse_dot.h: the dot
 //     product of label_logprob_kernel and of the search step, the same bits), then per leaf the sum of the edge terms along its path in
 //     position order, starting from 0.f -- label_logprob_kernel's sum.  One writer per output element: no float atomics.
 // (3) trie_repeat_tokens_kernel: the Q decoder input tokens of the row table repeated for every user.
 #include "common.h"
 #include "prof.h"
+#include "self_attn_row.h"
 #include "sparse_dot.h"
 
 namespace {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// x as an fp32 value in a register: what is computed into it is rounded to fp32 before anything converts it further (the compiler
-// otherwise folds a product and its conversion to 16 bits into one mixed-precision instruction, which rounds once)
-__device__ __forceinline__ float in_f32(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
 
 template <int S>
 __global__ __launch_bounds__(256) void dec_self_attn_tree_kernel(const p16* __restrict__ qkv, const int32_t* __restrict__ pos,
                                                                  const int32_t* __restrict__ anc, const float* __restrict__ bias,
                                                                  p16* __restrict__ out, int Q, int Tq, int H, long qkv_ps, int nblk) {
-  // The expression below is dec_self_attn_tf_kernel's with the roundings written out.  That kernel leaves the choice between a
-  // fused multiply-add and a product followed by a sum to the compiler, which fuses l * alpha + p, acc * alpha + (p * v) and the
-  // second piece's acc * inv - o, and nothing else; the same source here came out fused for two of the four accumulators only.  So
-  // contraction is off in this kernel and every fused operation is an fmaf: the bits do not depend on how the loop is scheduled.
-  // That kernel also rounds acc * inv (and the second piece's difference) to fp32 and then to 16 bits: in_f32 keeps the two roundings.
-#pragma clang fp contract(off)
   const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk, h = blockIdx.y, tid = threadIdx.x;
   const int inner = H * 64, l16 = tid & 15, grp = tid >> 4;
   const int i = blk * 16 + grp;
@@ -47,56 +34,17 @@ __global__ __launch_bounds__(256) void dec_self_attn_tree_kernel(const p16* __re
   const int t = clampi(pos[i], 0, Tq - 1);
   const int32_t* ai = anc + (size_t)i * Tq;
   const p16* row = qkv + (row0 + i) * 3 * inner + h * 64 + 4 * l16;
-  float qf[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int pc = S - 1; pc >= 0; --pc) {
-    const p16x4 q4 = *reinterpret_cast<const p16x4*>(row + pc * qkv_ps);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) qf[e] += (float)q4[e];
-  }
-  float m = -INFINITY, l = 0.f, acc[4] = {0.f, 0.f, 0.f, 0.f};
+  float qf[4], m = -INFINITY, l = 0.f, acc[4] = {0.f, 0.f, 0.f, 0.f};
+  sa_load<S>(row, qkv_ps, qf);
   for (int j = 0; j <= t; ++j) {  // the ancestor at position j, in order; j == t: the row itself
     const int a = clampi(ai[j], 0, Q - 1);
     const p16* arow = qkv + (row0 + a) * 3 * inner + h * 64 + 4 * l16;
-    // keys and values as the fp32 sum of their pieces, smallest first (dec_self_attn_tf_kernel's order)
-    float kj[4] = {0.f, 0.f, 0.f, 0.f}, vj[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int pc = S - 1; pc >= 0; --pc) {
-      const p16x4 k4 = *reinterpret_cast<const p16x4*>(arow + pc * qkv_ps + inner);
-      const p16x4 v4 = *reinterpret_cast<const p16x4*>(arow + pc * qkv_ps + 2 * inner);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        kj[e] += (float)k4[e];
-        vj[e] += (float)v4[e];
-      }
-    }
-    float s = qf[0] * kj[0] + qf[1] * kj[1] + qf[2] * kj[2] + qf[3] * kj[3];  // four products, three additions: nothing fused
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    s += __shfl_xor(s, 8, 64);
-    s += bias[h * GRAM_MAX_DEC_LEN + (t - j)];
-    const float mn = fmaxf(m, s);
-    const float alpha = __expf(m - mn);
-    const float p = __expf(s - mn);
-    m = mn;
-    l = fmaf(l, alpha, p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = fmaf(acc[e], alpha, p * vj[e]);
+    float kj[4], vj[4];
+    sa_load<S>(arow + inner, qkv_ps, kj);
+    sa_load<S>(arow + 2 * inner, qkv_ps, vj);
+    sa_step(qf, kj, vj, bias[h * GRAM_MAX_DEC_LEN + (t - j)], m, l, acc);
   }
-  const float inv = 1.f / l;
-  const int n = h * 64 + 4 * l16;  // (S == 2: interleaved rows [2 * inner], the O GEMM's A operand)
-  p16* orow = out + (row0 + i) * inner * S;
-  p16x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = (p16)in_f32(acc[e] * inv);
-  *reinterpret_cast<p16x4*>(orow + (S == 2 ? inter_off(n, 0) : n)) = o;
-  if (S == 2) {  // the second piece: what the first left of acc * inv, the product unrounded
-    p16x4 o1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o1[e] = (p16)in_f32(fmaf(acc[e], inv, -(float)o[e]));
-    *reinterpret_cast<p16x4*>(orow + inter_off(n, 1)) = o1;
-  }
+  sa_store<S>(out + (row0 + i) * inner * S, h * 64 + 4 * l16, l, acc);
 }
 
 __global__ __launch_bounds__(256) void trie_repeat_tokens_kernel(const int32_t* __restrict__ tokens, int32_t* __restrict__ out, int Q,

@@ -553,6 +553,52 @@ def test_dec_self_attn_one_piece_to_the_last_step(G):
     print(f"\n[dec step, one piece, random data] t=0..{Tmax - 1}: largest error / bound = {worst:.2f}")
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("pieces", [1, 2])
+@pytest.mark.parametrize("R,reorder", [pytest.param(5, False, id="identity"), pytest.param(6, True, id="reordered")])
+def test_stepped_self_attn_bitwise_vs_the_sequence_kernel(G, R, reorder, pieces):
+    """gram_dec_self_attn_split at t = 0..18 against gram_dec_self_attn_tf_split on the same prefixes, bit for bit: both kernels call
+    the one row step of self_attn_row.h.  T = 19 is two full batches of 8 cached positions and a remainder of 3 at the last step, so
+    every slot of the stepped kernel's batch and every remainder is met, t = 0 (no cached position) included; H = 3 is a 48-thread
+    block.  identity: row r of step t is position t of sequence r, one sequence per row.  reordered: random beam parents after every
+    step; for every (t, r) the explicit sequence qkv_j[anc_t[j][r]], j < t, then qkv_t[r], and position t of it is compared -- the
+    ancestor indirection and the shared step together."""
+    H, T = 3, 19
+    inner = H * 64
+    g = torch.Generator().manual_seed(190 + R)
+    x = G.pieces_of((torch.randn(T, R, 3 * inner, generator=g) * 0.5).to(G.DEV), pieces)  # [pieces][step][row][q|k|v]
+    bias = torch.randn(H, DEC_LEN, generator=g).to(G.DEV)
+    kc = torch.zeros(pieces, T, R, inner, dtype=G.DT, device=G.DEV)
+    vc = torch.zeros_like(kc)
+    anc = torch.arange(R, dtype=torch.int32).repeat(T, 1)
+    n_seq = T * R if reorder else R
+    seqs = torch.zeros(pieces, n_seq, T, 3 * inner, dtype=G.DT, device=G.DEV)
+    if not reorder:
+        seqs.copy_(x.transpose(1, 2))
+    outs = []
+    for t in range(T):
+        if reorder:  # the T-padded prefixes of step t's rows, through the table the step reads
+            for j in range(t):
+                seqs[:, t * R: (t + 1) * R, j] = x[:, j, anc[j].long().to(G.DEV)]
+            seqs[:, t * R: (t + 1) * R, t] = x[:, t]
+        qkv = x[:, t].contiguous()
+        out = torch.full((R, pieces * inner), float("nan"), dtype=G.DT, device=G.DEV)
+        anc_d = anc.to(G.DEV)
+        _lib.check(G.lib().gram_dec_self_attn_split(G.p(qkv), G.p(kc), G.p(vc), G.p(anc_d), G.p(bias), G.p(out), R, R, None, H, t, T,
+                                                    pieces, qkv[0].numel(), kc[0].numel(), G.stream()), "dec_attn")
+        outs.append(out)
+        if reorder:
+            anc = _anc_advance(anc, t, torch.randint(0, R, (R,), generator=g))
+    want = torch.full((n_seq * T, pieces * inner), float("nan"), dtype=G.DT, device=G.DEV)
+    _lib.check(G.lib().gram_dec_self_attn_tf_split(G.p(seqs), G.p(bias), G.p(want), n_seq, T, H, pieces, seqs[0].numel(), G.stream()),
+               "tf_attn")
+    want = want.view(n_seq, T, pieces * inner)
+    assert not bool(torch.isnan(want.float()).any())
+    for t in range(T):
+        rows = want[t * R: (t + 1) * R, t] if reorder else want[:, t]
+        assert torch.equal(outs[t].view(torch.int16), rows.contiguous().view(torch.int16)), t
+
+
 # ------------------------------------------------------------------------------------------------ no GPU: the probes can see it
 def test_probes_reject_single_slot_errors():
     """Every probe's fp64 reference passes its own comparator, meets the weight floors, and the comparator -- at the WIDEST bound any
