@@ -100,6 +100,11 @@ class XattnOut(C.Structure):
     _fields_ = [("probs", vp), ("layer_probs", vp), ("token_scores", vp), ("passage_scores", vp)]
 
 
+class XattnScores(C.Structure):
+    """gram_xattn_scores_t: the score outputs of gram_teacher_forced_scores (device pointers; passage_scores None = not wanted)"""
+    _fields_ = [("token_scores", vp), ("passage_scores", vp)]
+
+
 class TrieRows(C.Structure):
     """gram_trie_rows_t: the row tables of a Trie for gram_score_trie (device pointers; FlatTrie.decoder_rows)"""
     _fields_ = [("tokens", vp), ("pos", vp), ("anc", vp), ("row_node", vp), ("node_row", vp), ("node_tok", vp), ("node_leaf", vp),
@@ -242,6 +247,10 @@ SIGNATURES = {
     "gram_xattn_passage_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
     "gram_teacher_forced_ex": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Compaction), vp, vp, C.c_int, C.c_int, vp, i64,
                                          vp, vp, vp, C.POINTER(XattnOut), vp]),
+    # the head-summed token scores over up to 16 384 fused keys (no per-head buffer)
+    "gram_cross_attn_token_scores_split": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, vp, C.c_int, vp]),
+    "gram_teacher_forced_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(Compaction), vp, vp, C.c_int, C.c_int, vp,
+                                             i64, vp, vp, vp, C.POINTER(XattnScores), vp]),
     # every catalogue item in one decoder pass over the Trie
     "gram_dec_self_attn_tree_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp]),
     "gram_trie_repeat_tokens": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),

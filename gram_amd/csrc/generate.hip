@@ -1092,10 +1092,11 @@ Workspace carve_tf(const gram_model* m, void* ws, int B, int N, int L, int C, in
 // whole-sequence one and the cross-attention taking all Q rows of a user; then the lm_head with its LSE partials (logits stored when
 // given) and their combination.  attn != NULL (gram_teacher_forced_ex): every layer's cross-attention is followed by its probabilities
 // (xattn_probs.hip, on the same r.qx and K bank) and their head sum; the passage scores follow the last layer.  These launches only read
-// what the pass computes.  tree != NULL (gram_score_trie): the Q rows of a user are the rows of a Trie, each attending to its ancestors
-// (T is not used).
+// what the pass computes.  sc != NULL (gram_teacher_forced_scores): every layer's cross-attention is followed by the head-summed
+// probabilities (xattn_scores.hip) accumulated into sc->token_scores; no per-head buffer, any S the handle takes.
+// tree != NULL (gram_score_trie): the Q rows of a user are the rows of a Trie, each attending to its ancestors (T is not used).
 int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, const uint8_t* mask, int B, int N, int L, int Q, int T,
-               float* logits, const gram_xattn_out_t* attn, const gram_trie_rows_t* tree, void* st) {
+               float* logits, const gram_xattn_out_t* attn, const gram_xattn_scores_t* sc, const gram_trie_rows_t* tree, void* st) {
   const gram_model_desc_t& c = m->d;
   const int H = c.n_heads, R = B * Q, S = N * L;
   const size_t bank_layer = (size_t)B * H * S * 64;
@@ -1115,6 +1116,9 @@ int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, c
         else
           TRY(gram_cross_attn_rows_split(r.qx, w.bank_k + i * bank_layer, w.bank_vt + i * bank_layer, mask, r.attn, B, Q, H, S, w.pieces,
                                          r.ps_qx, w.ps_bank, w.key_bits, w.rowmap, st));
+        if (sc)
+          TRY(gram_cross_attn_token_scores_split(r.qx, w.bank_k + i * bank_layer, sc->token_scores, B, Q, H, S, w.pieces, r.ps_qx,
+                                                 w.ps_bank, w.key_bits, /*first=*/i == 0, st));
         if (!attn) return 0;
         float* p = attn->probs ? attn->probs + (size_t)i * B * H * Q * S : attn->layer_probs;
         // (the probabilities read the short form's key bits; a handle that carved the long form's lets the kernel pack them from the mask)
@@ -1125,6 +1129,8 @@ int decoder_tf(const gram_model* m, const Workspace& w, const int32_t* tokens, c
       st));
   if (attn && attn->passage_scores)
     TRY(gram_xattn_passage_scores(attn->token_scores, mask, attn->passage_scores, B, Q, N, L, (float)(c.n_dec_layers * H), st));
+  if (sc && sc->passage_scores)
+    TRY(gram_xattn_passage_scores(sc->token_scores, mask, sc->passage_scores, B, Q, N, L, (float)(c.n_dec_layers * H), st));
   TRY(lm_head(m, w, R, logits, w.lse_part, st));
   return gram_lse_combine(w.lse_part, w.lse, R, c.vocab / 64, st);
 }
@@ -1144,10 +1150,12 @@ extern "C" int gram_teacher_forced(const gram_model_t* m, const int64_t* input_i
                                 seq_logp, nullptr, stream);
 }
 
-extern "C" int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
-                                      const gram_compaction_t* comp, const int32_t* dec_ids, const int32_t* labels, int C, int T,
-                                      void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
-                                      const gram_xattn_out_t* attn, void* stream) {
+namespace {
+// the teacher-forced pass with either kind of attention output (at most one of attn, sc); every check before any launch
+int teacher_forced_run(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                       const gram_compaction_t* comp, const int32_t* dec_ids, const int32_t* labels, int C, int T, void* workspace,
+                       int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp, const gram_xattn_out_t* attn,
+                       const gram_xattn_scores_t* sc, void* stream) {
   TRY(check_shapes_tf(m, B, N, L, C, T));
   if (!mask || !dec_ids || !labels || !token_logp || !seq_logp || (!comp && !input_ids)) return GRAM_E_ARG;
   // the attention outputs are the caller's memory: one layer of probabilities at least, and the passage scores are a reduction of the
@@ -1159,9 +1167,31 @@ extern "C" int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* inpu
   if (!workspace || workspace_bytes < w.bytes) return GRAM_E_WORKSPACE;
   const gram_model_desc_t& c = m->d;
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
-  TRY(decoder_tf(m, w, dec_ids, mask, B, N, L, C * T, T, logits, attn, nullptr, stream));
+  TRY(decoder_tf(m, w, dec_ids, mask, B, N, L, C * T, T, logits, attn, sc, nullptr, stream));
   return gram_label_logprob_split(w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, labels, B * C, T, c.vocab, w.pieces,
                                   token_logp, seq_logp, stream);
+}
+}  // namespace
+
+extern "C" int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                                      const gram_compaction_t* comp, const int32_t* dec_ids, const int32_t* labels, int C, int T,
+                                      void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
+                                      const gram_xattn_out_t* attn, void* stream) {
+  return teacher_forced_run(m, input_ids, mask, B, N, L, comp, dec_ids, labels, C, T, workspace, workspace_bytes, logits, token_logp,
+                            seq_logp, attn, nullptr, stream);
+}
+
+// The head-summed scores read the long form's key bits, which only a raised handle's workspace holds (the carve is not changed for
+// this call); the kernel takes 16 heads at most.
+extern "C" int gram_teacher_forced_scores(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                                          const gram_compaction_t* comp, const int32_t* dec_ids, const int32_t* labels, int C, int T,
+                                          void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
+                                          const gram_xattn_scores_t* scores, void* stream) {
+  if (!m || !scores || !scores->token_scores || !m->long_xattn() || m->d.n_heads > 16) return GRAM_E_ARG;
+  if (reinterpret_cast<uintptr_t>(scores->token_scores) & 15) return GRAM_E_ARG;
+  if (B > 65535 || ((int64_t)C * T + 31) / 32 > 65535) return GRAM_E_ARG;  // (the kernel's grid: users, tiles of 32 rows)
+  return teacher_forced_run(m, input_ids, mask, B, N, L, comp, dec_ids, labels, C, T, workspace, workspace_bytes, logits, token_logp,
+                            seq_logp, nullptr, scores, stream);
 }
 
 // ---- every catalogue item in one decoder pass over the Trie (gram_score_trie) ------------------------------------------------------
@@ -1209,7 +1239,7 @@ extern "C" int gram_score_trie(const gram_model_t* m, const int64_t* input_ids, 
   const gram_model_desc_t& c = m->d;
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
   TRY(gram_trie_repeat_tokens(rows->tokens, ts.tokens, B, Q, stream));
-  TRY(decoder_tf(m, w, ts.tokens, mask, B, N, L, Q, 1, nullptr, nullptr, rows, stream));
+  TRY(decoder_tf(m, w, ts.tokens, mask, B, N, L, Q, 1, nullptr, nullptr, nullptr, rows, stream));
   return gram_trie_leaf_logprob_split(w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, rows, B, c.vocab, w.pieces, ts.edge,
                                       leaf_logp, node_logp, stream);
 }

@@ -304,8 +304,8 @@ class GRAM(nn.Module):
         default 4096.  The reference's default history (``--max_his 20``: 21 passages) needs 4704 at 224 tokens per passage and
         10752 at 512.  Above 4096 the decoder's cross-attention is the segmented kernel at EVERY length
         (gram_model_set_max_fused_len), so a user's bits never depend on the batch it was padded with; at 4096 the model launches
-        what it always launched.  The passage cache stays: cached passages do not depend on N * L.  ``cross_attentions`` and
-        ``passage_attention`` stay limited to 4096 fused tokens.  The cross K/V bank is what grows: layers x heads x 64 x (K, V^T) x
+        what it always launched.  The passage cache stays: cached passages do not depend on N * L.  ``cross_attentions``
+        stays limited to 4096 fused tokens; ``passage_attention`` follows the raised limit.  The cross K/V bank is what grows: layers x heads x 64 x (K, V^T) x
         2 B x pieces per fused key and user -- 73.7 KB at T5-base and two pieces, 0.79 GB per user at N * L = 10752; the users per
         call follow from the workspace queries (``max_users_per_call``)."""
         n = int(n)
@@ -582,7 +582,8 @@ class GRAM(nn.Module):
         S = int(input_ids.shape[1]) * ((int(input_ids.shape[2]) + 31) // 32 * 32)
         if S > _lib.GRAM_MAX_FUSED_LEN:
             raise ValueError(f"cross-attention probabilities are limited to {_lib.GRAM_MAX_FUSED_LEN} fused tokens (got N*L = {S}): "
-                             f"cross_attentions / passage_attention do not take the longer contexts set_max_fused_tokens allows")
+                             f"cross_attentions and passage_attention(fused=False) do not take the longer contexts "
+                             f"set_max_fused_tokens allows (passage_attention's default path does)")
         V, H, nl = int(self.config.vocab_size), int(self.config.num_heads), int(self.config.num_decoder_layers)
         N, Q = input_ids.shape[1], dec.shape[1] * dec.shape[2]
 
@@ -624,20 +625,58 @@ class GRAM(nn.Module):
         return tuple(probs[i] for i in range(nl))
 
     @torch.no_grad()
-    def passage_attention(self, input_ids, attention_mask, labels, users_per_call: Optional[int] = None):
+    def _teacher_forced_scores(self, input_ids, attention_mask, dec, lab, users_per_call: Optional[int] = None):
+        """(token_scores (B,C*T,N*Lp), passage_scores (B,C*T,N), Lp) over user chunks of torch.ops.gram.teacher_forced_scores: the
+        heads are summed inside the kernel, so the chunk budget counts the two results only -- no term in H."""
+        if attention_mask.shape != input_ids.shape:
+            raise ValueError("attention_mask must have input_ids' shape (B, N, L)")
+        if self._max_fused_tokens <= _lib.GRAM_MAX_FUSED_LEN:
+            raise ValueError("passage_attention(fused=True) runs on a model whose fused limit was raised: call set_max_fused_tokens(n) "
+                             f"with n > {_lib.GRAM_MAX_FUSED_LEN} first")
+        V = int(self.config.vocab_size)
+        N, Q = input_ids.shape[1], dec.shape[1] * dec.shape[2]
+        outs, Lp = self._tf_chunks(input_ids, attention_mask, dec, lab,
+                                   lambda cid, cmask, handle, ws, cdec, clab, *comp: torch.ops.gram.teacher_forced_scores(
+                                       cid, cmask, handle, ws, cdec, clab, V, *comp),
+                                   extra_bytes=lambda Lp: 4 * Q * (N * Lp + N), users_per_call=users_per_call)
+        tsc, psc = (outs[0][i] if len(outs) == 1 else torch.cat([o[i] for o in outs]) for i in (0, 1))
+        return tsc, psc, Lp
+
+    @torch.no_grad()
+    def passage_attention(self, input_ids, attention_mask, labels, users_per_call: Optional[int] = None,
+                          fused: Optional[bool] = None):
         """Which passages the decoder read, at every position of given sequences: labels (B, C, T) as for ``score_sequences`` (a
         generated sequence as labels gives the attribution of that hypothesis).  Returns ``(token_scores (B, C, T, N, L),
         passage_scores (B, C, T, N))``: the cross-attention weights summed over decoder layers and heads, and per passage their sum
         over its valid keys / (valid keys * layers * heads) -- ``get_crossattention_scores``'s two results at every position; NaN for a
-        passage without a valid key.  Reduced on the device, one layer of probabilities held at a time; a user's result does not
-        depend on the chunk."""
+        passage without a valid key.  A user's result does not depend on the chunk.
+
+        ``fused``: ``False`` reduces one layer of per-head probabilities (B, H, C*T, N*L) at a time on the device and stops at 4096
+        fused tokens; ``True`` sums the heads inside the kernel (gram_teacher_forced_scores) -- no per-head buffer, up to 16 384 fused
+        tokens, on a model raised by ``set_max_fused_tokens``.  ``None`` (default): ``False`` up to 4096 fused tokens, ``True``
+        above.  The two agree within the rounding of the summation order, not bit for bit."""
+        if input_ids.dim() == 3:  # which path, and its refusals, before anything touches a device
+            S = input_ids.shape[1] * ((input_ids.shape[2] + 31) // 32 * 32)
+            if fused is None:
+                fused = S > _lib.GRAM_MAX_FUSED_LEN
+                if fused:
+                    self._check_fused_len(input_ids.shape[1], input_ids.shape[2])  # (a default model: names set_max_fused_tokens)
+            elif fused and self._max_fused_tokens <= _lib.GRAM_MAX_FUSED_LEN:
+                raise ValueError("passage_attention(fused=True) runs on a model whose fused limit was raised: call "
+                                 f"set_max_fused_tokens(n) with n > {_lib.GRAM_MAX_FUSED_LEN} first")
+            elif not fused and S > _lib.GRAM_MAX_FUSED_LEN:
+                raise ValueError(f"cross-attention probabilities are limited to {_lib.GRAM_MAX_FUSED_LEN} fused tokens (got N*L = {S}): "
+                                 f"passage_attention(fused=False) holds one layer of them; fused=None or True takes the longer contexts")
         if self._device().type != "cuda":
             raise NotImplementedError("gram_amd.GRAM.passage_attention runs on a ROCm device (model.to('cuda')); there is no CPU path")
         if input_ids.dim() != 3 or labels.dim() != 3 or labels.shape[0] != input_ids.shape[0]:
             raise ValueError("input_ids must be (B, N, L) and labels (B, C, T)")
         lab = self._check_labels(labels.to(self._device()))
-        _pr, tsc, psc, Lp = self._teacher_forced_attn(input_ids, attention_mask, shift_right(lab), lab, False, True, users_per_call)
         B, N, L = input_ids.shape
+        if fused:
+            tsc, psc, Lp = self._teacher_forced_scores(input_ids, attention_mask, shift_right(lab), lab, users_per_call)
+        else:
+            _pr, tsc, psc, Lp = self._teacher_forced_attn(input_ids, attention_mask, shift_right(lab), lab, False, True, users_per_call)
         _, Cn, T = lab.shape
         return tsc.view(B, Cn, T, N, Lp)[..., :L], psc.view(B, Cn, T, N)
 

@@ -12,6 +12,9 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
                                      ``GRAM.score_sequences``
     torch.ops.gram.teacher_forced_attn  the same pass with its cross-attention probabilities (gram_teacher_forced_ex) --
                                      ``GRAM.cross_attentions`` and ``GRAM.passage_attention``
+    torch.ops.gram.teacher_forced_scores  the same pass with the probabilities summed over heads inside the kernel
+                                     (gram_teacher_forced_scores): up to 16 384 fused keys, no per-head buffer --
+                                     ``GRAM.passage_attention(fused=True)`` and above 4096 keys
     torch.ops.gram.score_trie        every leaf of the Trie scored in one decoder pass over its internal nodes (gram_score_trie) --
                                      ``GRAM.score_all_items``
     torch.ops.gram.linear            nn.Linear without bias: A @ W^T on the 16-bit MFMA (gram_gemm_bf16, 16-bit epilogue)
@@ -290,6 +293,60 @@ def _(input_ids, attention_mask, handle, workspace, decoder_input_ids, labels, v
             decoder_input_ids.new_empty((B, Q, N) if want_scores else (0,), **f))
 
 
+@torch.library.custom_op("gram::teacher_forced_scores", mutates_args=("workspace",), device_types="cuda")
+def teacher_forced_scores(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, decoder_input_ids: Tensor,
+                          labels: Tensor, vocab_size: int, comp_map: Optional[Tensor], comp_ids: Optional[Tensor],
+                          comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor], n_cached: int,
+                          cache_L: int) -> Tuple[Tensor, Tensor]:
+    """The teacher-forced pass of ``teacher_forced`` (same inputs, validated the same way) with the cross-attention scores summed
+    over heads inside the kernel (gram_teacher_forced_scores): no per-head buffer, any N*L the handle takes -- which must have been
+    raised by gram_model_set_max_fused_len (GRAM_E_ARG otherwise).  Returns (token_scores f32 (B, C*T, N*L) = the probabilities
+    summed over layers and heads, passage_scores f32 (B, C*T, N) = per passage the sum over its valid keys / (valid keys *
+    n_dec_layers * n_heads), NaN for a passage without one)."""
+    lib = _lib.load()
+    dev = input_ids.device
+    if input_ids.dim() != 3 or decoder_input_ids.dim() != 3:
+        raise ValueError("teacher_forced_scores: input_ids must be (B, N, L) and decoder_input_ids (B, C, T)")
+    B, N, L = input_ids.shape
+    Bd, Cn, T = decoder_input_ids.shape
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    _check("decoder_input_ids", decoder_input_ids, torch.int32, (B, None, None), dev)
+    _check("labels", labels, torch.int32, (B, Cn, T), dev)
+    if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN or Cn < 1:
+        raise ValueError(f"teacher_forced_scores: need 1 <= T <= {_lib.GRAM_MAX_DEC_LEN} and C >= 1 (got C={Cn}, T={T})")
+    lo_d, hi_d, hi_l = torch.stack([decoder_input_ids.min(), decoder_input_ids.max(), labels.max()]).tolist()
+    if lo_d < 0 or hi_d >= vocab_size or hi_l >= vocab_size:
+        raise ValueError(f"teacher_forced_scores: decoder_input_ids must lie in [0, {vocab_size}) and labels below {vocab_size}")
+    comp = None
+    if comp_map is not None:
+        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
+                               _p(cache_slot))
+    Q, S = Cn * T, N * L
+    f = dict(dtype=torch.float32, device=dev)
+    tsc = torch.empty(B, Q, S, **f)
+    psc = torch.empty(B, Q, N, **f)
+    tok = torch.empty(B, Cn, T, **f)
+    seq = torch.empty(B, Cn, **f)
+    out = _lib.XattnScores(tsc.data_ptr(), psc.data_ptr())
+    with torch.cuda.device(dev):
+        rc = lib.gram_teacher_forced_scores(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
+                                            C.byref(comp) if comp is not None else None, decoder_input_ids.data_ptr(),
+                                            labels.data_ptr(), Cn, T, workspace.data_ptr(), workspace.numel(), None, tok.data_ptr(),
+                                            seq.data_ptr(), C.byref(out), _stream(input_ids))
+    _lib.check(rc, "gram_teacher_forced_scores")
+    return tsc, psc
+
+
+@teacher_forced_scores.register_fake
+def _(input_ids, attention_mask, handle, workspace, decoder_input_ids, labels, vocab_size, comp_map, comp_ids, comp_mask, cache_slot,
+      cache_x, n_cached, cache_L):
+    B, N, L = input_ids.shape
+    _, Cn, T = decoder_input_ids.shape
+    f = dict(dtype=torch.float32)
+    return (decoder_input_ids.new_empty(B, Cn * T, N * L, **f), decoder_input_ids.new_empty(B, Cn * T, N, **f))
+
+
 # ---------------------------------------------------------------------------------------------- every item in one pass over the Trie
 @torch.library.custom_op("gram::score_trie", mutates_args=("workspace",), device_types="cuda")
 def score_trie(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor, trie_child_tok: Tensor,
@@ -549,4 +606,4 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
-__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "score_trie", "linear", "enc_self_attn", "enc_self_attn_long", "cross_attn_decode", "cross_attn_long", "trie_step"]
+__all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "teacher_forced_scores", "score_trie", "linear", "enc_self_attn", "enc_self_attn_long", "cross_attn_decode", "cross_attn_long", "trie_step"]

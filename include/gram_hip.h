@@ -787,6 +787,37 @@ int gram_teacher_forced_ex(const gram_model_t* m, const int64_t* input_ids, cons
                            void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
                            const gram_xattn_out_t* attn_host, void* stream);
 
+/* The token scores without the per-head tensor, over up to GRAM_MAX_LONG_FUSED_LEN fused keys:
+ *   acc[b][i][s] = (first ? 0 : acc[b][i][s]) + the sum over h, in head order, of softmax_s(q[b*Q + i] . k[b][h][s] + masked)[s],
+ * acc f32 [B][Q][S]: gram_cross_attn_probs_split's probabilities (the same operands, product order and online normaliser) summed over
+ * the heads on chip -- what gram_cross_attn_probs_split + gram_xattn_head_sum leave in acc, with nothing of size H * Q * S in
+ * between.  key_bits is required: gram_mask_key_bits_long of the same mask and S (the mask bytes are not read).  S % 32 == 0,
+ * 32 <= S <= GRAM_MAX_LONG_FUSED_LEN, Q >= 1, H <= 16, B <= 65535, pieces 1 or 2.  No atomics, one fixed order for every sum: a row's
+ * valid keys depend on that row, the user's valid 32-key steps in key order (each with its word of bits), `first` and the old value
+ * only -- not on B, Q, the user's place in the batch or where the fully masked steps lie.  Fully masked steps are not fetched: with
+ * `first` their keys are written as 0.0, otherwise left alone; masked keys of a valid step add exactly 0.0 whatever the bank holds; a
+ * user without a valid key gets H / S everywhere.  GRAM_E_ARG before any launch: a NULL or not 16-byte aligned q, k_layer, acc or
+ * key_bits, a size out of range, (two pieces) q_pstride < B*Q*H*64 or bank_pstride < H*S*64, more than 65535 tiles of 32 rows. */
+int gram_cross_attn_token_scores_split(const void* q, const void* k_layer, float* acc, int B, int Q, int H, int S, int pieces,
+                                       int64_t q_pstride, int64_t bank_pstride, const uint32_t* key_bits, int first, void* stream);
+
+/* Score outputs of gram_teacher_forced_scores, caller-owned device memory (Q = C * T rows per user, S = N * L keys). */
+typedef struct {
+  float* token_scores;   /* [B][Q][S]: sum over decoder layers and heads; required                                       */
+  float* passage_scores; /* [B][Q][N]: gram_xattn_passage_scores of it, denom = n_dec_layers * H; or NULL                */
+} gram_xattn_scores_t;
+
+/* gram_teacher_forced with the token (and passage) scores of the pass at every S the handle takes, without a per-head buffer: every
+ * decoder layer's cross-attention is followed by gram_cross_attn_token_scores_split on the same queries and K bank (first = layer 0);
+ * gram_xattn_passage_scores follows the last layer.  Needs a handle raised by gram_model_set_max_fused_len (its workspace holds the
+ * long key bits): a default handle, scores_host == NULL, a NULL or not 16-byte aligned token_scores, more than 16 heads, B > 65535 or
+ * more than 65535 tiles of 32 rows get GRAM_E_ARG before any launch.
+ * The workspace and every other output are those of gram_teacher_forced. */
+int gram_teacher_forced_scores(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L,
+                               const gram_compaction_t* compaction_host, const int32_t* dec_ids, const int32_t* labels, int C, int T,
+                               void* workspace, int64_t workspace_bytes, float* logits, float* token_logp, float* seq_logp,
+                               const gram_xattn_scores_t* scores_host, void* stream);
+
 /* ---- every catalogue item in one decoder pass over the Trie (GRAM.score_all_items) -----------------------------------------
  * The teacher-forced pass above spends one decoder row per (candidate, position); two candidates that share an id prefix share every
  * decoder state along it (a teacher-forced row depends on its prefix only: gram_t5.py:181-263 with the causal self-attention of

@@ -32,7 +32,8 @@ struct Case {
   Live live;
   bool comp, capped, logits;  // a gram_compaction_t with cached passages; every stage capped to one piece; teacher-forced logits stored
   bool tables;                // the handle has token tables: the trace starts with their build (workspace offsets: the build's scratch)
-  int attn;                   // gram_teacher_forced_ex: 1 = every layer's probabilities, 2 = one layer of scratch + token and passage scores
+  int attn;                   // gram_teacher_forced_ex: 1 = every layer's probabilities, 2 = one layer of scratch + token and passage scores;
+                              // 3 = gram_teacher_forced_scores: token and passage scores, the heads summed inside the kernel
   bool items;                 // gram_generate_items: per-user item filters (gram_user_items_t)
   int max_L;                  // != 0: gram_model_set_max_passage_len first (a long-mode handle: the tiled encoder attention at every L)
   int max_S;                  // != 0: gram_model_set_max_fused_len first (the long cross-attention at every S; the model takes 40 passages)
@@ -100,6 +101,10 @@ const Case kCases[] = {
     {"generate_tail_p2_tables", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, true, 0, false, 0, 0, 11},
     {"generate_tail_over", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 21},
     {"generate_tail_fused_32", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 16384, 11},
+    // gram_teacher_forced_scores on a raised handle: the trains of tf_p2 (with the long key bits and cross-attention) and tf_fused_4704
+    // plus, per layer, the head-summed token scores; the passage scores behind the last layer
+    {"tf_scores_fused_96", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4, OFF, false, false, false, false, 3, false, 0, 16384},
+    {"tf_scores_fused_4704", TEACHER_FORCED, 2, 1, 2, 21, 224, 3, 4, OFF, false, false, false, false, 3, false, 256, 16384},
 };
 
 gram_model_t* make_model(int pieces, int fold, int max_passages) {
@@ -191,6 +196,11 @@ int run(const Case& c) {
     case DECODE_STEP:
       return gram_decode_step(m, (int32_t*)io[0], (int32_t*)io[1], mask, B, N, L, K, T, /*t=*/1, g_ws, g_ws_bytes, (float*)io[2], st);
     case TEACHER_FORCED:
+      if (c.attn == 3) {
+        const gram_xattn_scores_t scores{fake<float>(), fake<float>()};
+        return gram_teacher_forced_scores(m, ids, mask, B, N, L, nullptr, (int32_t*)io[0], (int32_t*)io[1], K, T, g_ws, g_ws_bytes, nullptr,
+                                          (float*)io[3], (float*)io[4], &scores, st);
+      }
       if (c.attn) {
         const gram_xattn_out_t attn = c.attn == 1 ? gram_xattn_out_t{fake<float>(), nullptr, nullptr, nullptr}
                                                   : gram_xattn_out_t{nullptr, fake<float>(), fake<float>(), fake<float>()};

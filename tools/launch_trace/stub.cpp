@@ -168,6 +168,10 @@ int gram_cross_attn_probs_split(const void* q, const void* k, const uint8_t* mas
                                 int64_t q_ps, int64_t bank_ps, const uint32_t* key_bits, void* st) {
   REC(q, k, mask, probs, B, Q, H, S, pieces, q_ps, bank_ps, key_bits, st);
 }
+int gram_cross_attn_token_scores_split(const void* q, const void* k, float* acc, int B, int Q, int H, int S, int pieces, int64_t q_ps,
+                                       int64_t bank_ps, const uint32_t* key_bits, int first, void* st) {
+  REC(q, k, acc, B, Q, H, S, pieces, q_ps, bank_ps, key_bits, first, st);
+}
 int gram_xattn_head_sum(const float* probs, float* acc, int B, int Q, int H, int S, int first, void* st) {
   REC(probs, acc, B, Q, H, S, first, st);
 }
