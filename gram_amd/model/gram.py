@@ -551,14 +551,12 @@ class GRAM(nn.Module):
                 raise _lib.GramHipError(f"unsupported problem size B={nb} N={N} L={Lp} {size} (N <= max_item_num+1, L <= {self._max_passage_len}, "
                                         f"N*L <= {self._max_fused_tokens}, T <= {_lib.GRAM_MAX_DEC_LEN})")
             ws = self._ensure_workspace(need)
-            ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
             if trie_rows is not None:
                 cdec = clab = None
             else:
                 # (a chunk's slice of dec / lab starts wherever the rows before it end: a copy is 16-byte aligned, as the ops require)
                 cdec, clab = (dec[b0:b1], lab[b0:b1]) if dec[b0:b1].data_ptr() % 16 == 0 else (dec[b0:b1].clone(), lab[b0:b1].clone())
-            outs.append(call(cid, cmask, int(handle), ws, cdec, clab, ct["comp_map"], ct["comp_ids"], ct["comp_mask"], ct["cache_slot"],
-                             ct["cache_x"], int(ct["n_cached"]), int(ct["cache_L"])))
+            outs.append(call(cid, cmask, int(handle), ws, cdec, clab, *self._comp_args(comp)))
         return outs, Lp
 
     def _teacher_forced(self, input_ids, attention_mask, dec, lab, want_logits: bool, users_per_call: Optional[int] = None):
@@ -1122,6 +1120,14 @@ class GRAM(nn.Module):
         """gram_compaction_t for this batch as (struct, keep-alive list, tensors), or None when the encoder simply runs on all B*N passages."""
         return self._plan(ids, mask, B, N, Lp)[0]
 
+    @staticmethod
+    def _comp_args(comp) -> tuple:
+        """The seven comp_* / cache_* arguments of the whole-path ops (gram_amd/ops.py) from ``_plan``'s compaction, or None for off."""
+        if not comp:
+            return None, None, None, None, None, 0, 0
+        t = comp[2]
+        return t["comp_map"], t["comp_ids"], t["comp_mask"], t["cache_slot"], t["cache_x"], int(t["n_cached"]), int(t["cache_L"])
+
     def _plan(self, ids, mask, B, N, Lp):
         """(gram_compaction_t for this batch -- or None when the encoder simply runs on all B*N passages --, harvest plan or None).
 
@@ -1270,12 +1276,10 @@ class GRAM(nn.Module):
             ws = self._get_workspace(handle, B, N, Lp, K, int(max_length))
         if K == 1 and nret != 1:
             raise ValueError("num_return_sequences must be 1 for greedy search (num_beams == 1), as in HF generate")
-        ct = comp[2] if comp else dict(comp_map=None, comp_ids=None, comp_mask=None, cache_slot=None, cache_x=None, n_cached=0, cache_L=0)
         # the whole path is ONE PyTorch-ROCm custom op over the C ABI (gram_amd/ops.py -> gram_generate_ex / gram_generate_items)
         from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
         args = (ids, mask, int(handle), ws, t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len), K, nret, int(max_length),
-                float(length_penalty), ct["comp_map"], ct["comp_ids"], ct["comp_mask"], ct["cache_slot"], ct["cache_x"],
-                int(ct["n_cached"]), int(ct["cache_L"]))
+                float(length_penalty), *self._comp_args(comp))
         if filtered:
             leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
             seqs, scores, width = torch.ops.gram.generate_items(*args, leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items,

@@ -23,6 +23,11 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
     torch.ops.gram.cross_attn_decode the fusion read of one decoder layer and step over the beam-shared bank
     torch.ops.gram.cross_attn_long   the same over up to 16 384 fused keys (gram_cross_attn_long_split)
     torch.ops.gram.trie_step         one Trie-constrained beam-search step on dense logits (gram_row_lse + gram_beam_step)
+
+Every op keeps its full explicit signature (``torch.library`` derives the schema from it).  What several ops do with the same
+arguments is stated once, in the private helpers below the ``_check`` they are built on: ``_compaction`` / ``_trie`` build the
+gram_compaction_t / gram_trie_t of a call, ``_tf_inputs`` is the validation of the three teacher-forced ops, ``_search`` the
+outputs and the C call of the two ``generate`` ops, ``_enc_self_attn`` / ``_cross_attn_inputs`` the short and long attention forms.
 """
 from __future__ import annotations
 
@@ -44,6 +49,11 @@ def _p(t: Optional[Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _ref(struct):
+    """``byref`` of a ctypes struct, None (a null pointer) for None"""
+    return None if struct is None else C.byref(struct)
+
+
 def _check(name: str, t: Tensor, dtype, shape=None, device=None, contiguous: bool = True) -> None:
     """Everything the C ABI assumes about a tensor before its data_ptr() is taken: a wrong dtype, a transposed or sliced view or
     a shape that does not match the kernel's indexing would otherwise be silent garbage or an out-of-bounds device read."""
@@ -60,7 +70,46 @@ def _check(name: str, t: Tensor, dtype, shape=None, device=None, contiguous: boo
             raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple('*' if e is None else e for e in shape)}")
 
 
+def _compaction(comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor],
+                cache_x: Optional[Tensor], n_cached: int, cache_L: int) -> Optional[_lib.Compaction]:
+    """The gram_compaction_t of the comp_* / cache_* arguments every whole-path op takes; None (compaction off) without a comp_map."""
+    if comp_map is None:
+        return None
+    return _lib.Compaction(n_active=comp_map.numel(), passage_map=comp_map.data_ptr(), ids=_p(comp_ids), mask=_p(comp_mask),
+                           n_cached=n_cached, cache_L=cache_L, cache_x=_p(cache_x), cache_slot=_p(cache_slot))
+
+
+def _trie(child_off: Tensor, child_tok: Tensor, child_node: Tensor, max_fanout: int, min_seq_len: int) -> _lib.Trie:
+    """The gram_trie_t of a Trie's three CSR arrays"""
+    return _lib.Trie(child_off.data_ptr(), child_tok.data_ptr(), child_node.data_ptr(), child_off.numel() - 1, child_tok.numel(),
+                     max_fanout, min_seq_len)
+
+
 # ---------------------------------------------------------------------------------------------- generate
+def _search(fn, what: str, input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie: _lib.Trie,
+            comp: Optional[_lib.Compaction], num_beams: int, num_return_sequences: int, max_length: int, length_penalty: float,
+            *extra) -> Tuple[Tensor, Tensor, Tensor]:
+    """The outputs of a search, its C call ``fn`` (gram_generate_ex, or gram_generate_tail / gram_generate_items with their one
+    further struct in ``extra``) and the ops' return value.  The caller has made input_ids' device the current one."""
+    B, N, L = input_ids.shape
+    K, nret = num_beams, num_return_sequences
+    seqs = torch.empty(B * nret, max_length, dtype=torch.int64, device=input_ids.device)
+    scores = torch.empty(B * nret if K > 1 else 0, dtype=torch.float32, device=input_ids.device)
+    width = C.c_int32(0)
+    rc = fn(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length, float(length_penalty), C.byref(trie),
+            _ref(comp), *extra, workspace.data_ptr(), workspace.numel(), seqs.data_ptr(), scores.data_ptr() if K > 1 else None,
+            C.byref(width), _stream(input_ids))
+    _lib.check(rc, what)
+    return seqs, scores, torch.tensor([width.value], dtype=torch.int32)
+
+
+def _search_fake(input_ids, num_beams, num_return_sequences, max_length):
+    B = input_ids.shape[0]
+    return (input_ids.new_empty(B * num_return_sequences, max_length),
+            input_ids.new_empty(B * num_return_sequences if num_beams > 1 else 0, dtype=torch.float32),
+            torch.empty(1, dtype=torch.int32))
+
+
 @torch.library.custom_op("gram::generate", mutates_args=("workspace",), device_types="cuda")
 def generate(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
              trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
@@ -73,45 +122,24 @@ def generate(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: 
     trie_sub_rows i32 (n_nodes,) / trie_d_tail / trie_tail_steps: the Trie's tail tables (gram_trie_tail_t, ``FlatTrie.tail_tables``);
     given, the call is gram_generate_tail and ``workspace`` must hold gram_workspace_bytes_tail.  Returns (sequences i64 (B*nret, max_length), sequences_scores f32 (B*nret) -- empty for greedy search --, width i32 (1,))."""
     lib = _lib.load()
-    B, N, L = input_ids.shape
     dev = input_ids.device
-    K, nret = num_beams, num_return_sequences
-    trie = _lib.Trie(trie_child_off.data_ptr(), trie_child_tok.data_ptr(), trie_child_node.data_ptr(), trie_child_off.numel() - 1,
-                     trie_child_tok.numel(), trie_max_fanout, trie_min_seq_len)
-    comp = None
-    if comp_map is not None:
-        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
-                               _p(cache_slot))
-    seqs = torch.empty(B * nret, max_length, dtype=torch.int64, device=dev)
-    scores = torch.empty(B * nret if K > 1 else 0, dtype=torch.float32, device=dev)
-    width = C.c_int32(0)
-    tail = None
+    # (unlike generate_items, this op does not validate its tensors: ``GRAM.generate`` prepares them, and this is the benchmarked path)
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
+    fn, tail = lib.gram_generate_ex, ()
     if trie_sub_rows is not None and trie_d_tail > 0:
         _check("trie_sub_rows", trie_sub_rows, torch.int32, (trie_child_off.numel() - 1,), dev)
-        tail = _lib.TrieTail(trie_sub_rows.data_ptr(), int(trie_d_tail), int(trie_tail_steps))
+        fn, tail = lib.gram_generate_tail, (C.byref(_lib.TrieTail(trie_sub_rows.data_ptr(), int(trie_d_tail), int(trie_tail_steps))),)
     with torch.cuda.device(dev):
-        if tail is not None:
-            rc = lib.gram_generate_tail(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length,
-                                        float(length_penalty), C.byref(trie), C.byref(comp) if comp is not None else None,
-                                        C.byref(tail), workspace.data_ptr(), workspace.numel(), seqs.data_ptr(),
-                                        scores.data_ptr() if K > 1 else None, C.byref(width), _stream(input_ids))
-        else:
-            rc = lib.gram_generate_ex(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length,
-                                      float(length_penalty), C.byref(trie), C.byref(comp) if comp is not None else None,
-                                      workspace.data_ptr(), workspace.numel(), seqs.data_ptr(), scores.data_ptr() if K > 1 else None,
-                                      C.byref(width), _stream(input_ids))
-    _lib.check(rc, "gram_generate")
-    return seqs, scores, torch.tensor([width.value], dtype=torch.int32)
+        return _search(fn, "gram_generate", input_ids, attention_mask, handle, workspace, trie, comp, num_beams, num_return_sequences,
+                       max_length, length_penalty, *tail)
 
 
 @generate.register_fake
 def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
       cache_x, n_cached, cache_L, trie_sub_rows=None, trie_d_tail=0, trie_tail_steps=0):
-    B = input_ids.shape[0]
-    return (input_ids.new_empty(B * num_return_sequences, max_length),
-            input_ids.new_empty(B * num_return_sequences if num_beams > 1 else 0, dtype=torch.float32),
-            torch.empty(1, dtype=torch.int32))
+    return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
 
 
 # ---------------------------------------------------------------------------------------------- generate with per-user item filters
@@ -131,7 +159,6 @@ def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, works
         raise ValueError("generate_items: input_ids must be (B, N, L) and items (B, M)")
     B, N, L = input_ids.shape
     dev = input_ids.device
-    K, nret = num_beams, num_return_sequences
     M = items.shape[1]
     n_nodes = trie_child_off.numel() - 1
     _check("input_ids", input_ids, torch.int64)
@@ -146,41 +173,50 @@ def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, works
     lo_i, hi_i = torch.stack([items.min(), items.max()]).tolist()
     if lo_i < -1 or hi_i >= item_rank.numel():
         raise ValueError(f"generate_items: items must lie in [0, {item_rank.numel()}) or be the padding value -1")
-    trie = _lib.Trie(trie_child_off.data_ptr(), trie_child_tok.data_ptr(), trie_child_node.data_ptr(), n_nodes,
-                     trie_child_tok.numel(), trie_max_fanout, trie_min_seq_len)
-    comp = None
-    if comp_map is not None:
-        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
-                               _p(cache_slot))
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
     ranks = torch.empty(B, M, dtype=torch.int32, device=dev)
     count = torch.empty(B, dtype=torch.int32, device=dev)
     ui = _lib.UserItems(leaf_lo.data_ptr(), leaf_hi.data_ptr(), ranks.data_ptr(), count.data_ptr(), M,
                         _lib.ITEMS_ALLOW if allow else _lib.ITEMS_EXCLUDE)
-    seqs = torch.empty(B * nret, max_length, dtype=torch.int64, device=dev)
-    scores = torch.empty(B * nret if K > 1 else 0, dtype=torch.float32, device=dev)
-    width = C.c_int32(0)
     with torch.cuda.device(dev):
         _lib.check(lib.gram_user_items_prepare(item_rank.data_ptr(), item_rank.numel(), items.data_ptr(), B, M, ranks.data_ptr(),
                                                count.data_ptr(), M, _stream(input_ids)), "gram_user_items_prepare")
-        rc = lib.gram_generate_items(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, K, nret, max_length,
-                                     float(length_penalty), C.byref(trie), C.byref(comp) if comp is not None else None, C.byref(ui),
-                                     workspace.data_ptr(), workspace.numel(), seqs.data_ptr(), scores.data_ptr() if K > 1 else None,
-                                     C.byref(width), _stream(input_ids))
-    _lib.check(rc, "gram_generate_items")
-    return seqs, scores, torch.tensor([width.value], dtype=torch.int32)
+        return _search(lib.gram_generate_items, "gram_generate_items", input_ids, attention_mask, handle, workspace, trie, comp,
+                       num_beams, num_return_sequences, max_length, length_penalty, C.byref(ui))
 
 
 @generate_items.register_fake
 def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
       cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
-    B = input_ids.shape[0]
-    return (input_ids.new_empty(B * num_return_sequences, max_length),
-            input_ids.new_empty(B * num_return_sequences if num_beams > 1 else 0, dtype=torch.float32),
-            torch.empty(1, dtype=torch.int32))
+    return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
 
 
 # ---------------------------------------------------------------------------------------------- teacher-forced pass
+def _tf_inputs(op: str, input_ids: Tensor, attention_mask: Tensor, decoder_input_ids: Tensor, labels: Tensor,
+               vocab_size: int) -> Tuple[int, int, int, int, int]:
+    """What the three teacher-forced ops require of input_ids i64 (B,N,L), attention_mask u8 (B,N,L), decoder_input_ids i32 (B,C,T)
+    in [0, vocab_size) and labels i32 (B,C,T) < vocab_size (< 0 = ignored), or a ``ValueError`` in ``op``'s name; returns
+    (B, N, L, C, T).  The range check is the call's one read-back from the device."""
+    dev = input_ids.device
+    if input_ids.dim() != 3 or decoder_input_ids.dim() != 3:
+        raise ValueError(f"{op}: input_ids must be (B, N, L) and decoder_input_ids (B, C, T)")
+    B, N, L = input_ids.shape
+    _, Cn, T = decoder_input_ids.shape
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    _check("decoder_input_ids", decoder_input_ids, torch.int32, (B, None, None), dev)
+    _check("labels", labels, torch.int32, (B, Cn, T), dev)
+    if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN or Cn < 1:
+        raise ValueError(f"{op}: need 1 <= T <= {_lib.GRAM_MAX_DEC_LEN} and C >= 1 (got C={Cn}, T={T})")
+    # token ids index the embedding and lm_head tables on the device: out-of-range ones are refused here, not read there
+    lo_d, hi_d, hi_l = torch.stack([decoder_input_ids.min(), decoder_input_ids.max(), labels.max()]).tolist()
+    if lo_d < 0 or hi_d >= vocab_size or hi_l >= vocab_size:
+        raise ValueError(f"{op}: decoder_input_ids must lie in [0, {vocab_size}) and labels below {vocab_size}")
+    return B, N, L, Cn, T
+
+
 @torch.library.custom_op("gram::teacher_forced", mutates_args=("workspace",), device_types="cuda")
 def teacher_forced(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, decoder_input_ids: Tensor, labels: Tensor,
                    vocab_size: int, want_logits: bool, comp_map: Optional[Tensor], comp_ids: Optional[Tensor],
@@ -191,33 +227,16 @@ def teacher_forced(input_ids: Tensor, attention_mask: Tensor, handle: int, works
     comp_* / cache_* the gram_compaction_t fields (None = off).  Returns (logits f32 (B,C,T,V) -- empty unless want_logits --,
     token log-probs f32 (B,C,T) -- 0 where the label is ignored --, their per-sequence sums f32 (B,C))."""
     lib = _lib.load()
-    dev = input_ids.device
-    if input_ids.dim() != 3 or decoder_input_ids.dim() != 3:
-        raise ValueError("teacher_forced: input_ids must be (B, N, L) and decoder_input_ids (B, C, T)")
-    B, N, L = input_ids.shape
-    Bd, Cn, T = decoder_input_ids.shape
-    _check("input_ids", input_ids, torch.int64)
-    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
-    _check("decoder_input_ids", decoder_input_ids, torch.int32, (B, None, None), dev)
-    _check("labels", labels, torch.int32, (B, Cn, T), dev)
-    if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN or Cn < 1:
-        raise ValueError(f"teacher_forced: need 1 <= T <= {_lib.GRAM_MAX_DEC_LEN} and C >= 1 (got C={Cn}, T={T})")
-    # token ids index the embedding and lm_head tables on the device: out-of-range ones are refused here, not read there
-    lo_d, hi_d, hi_l = torch.stack([decoder_input_ids.min(), decoder_input_ids.max(), labels.max()]).tolist()
-    if lo_d < 0 or hi_d >= vocab_size or hi_l >= vocab_size:
-        raise ValueError(f"teacher_forced: decoder_input_ids must lie in [0, {vocab_size}) and labels below {vocab_size}")
-    comp = None
-    if comp_map is not None:
-        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
-                               _p(cache_slot))
-    logits = torch.empty((B, Cn, T, vocab_size) if want_logits else (0,), dtype=torch.float32, device=dev)
-    tok = torch.empty(B, Cn, T, dtype=torch.float32, device=dev)
-    seq = torch.empty(B, Cn, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gram_teacher_forced(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
-                                     C.byref(comp) if comp is not None else None, decoder_input_ids.data_ptr(), labels.data_ptr(),
-                                     Cn, T, workspace.data_ptr(), workspace.numel(), logits.data_ptr() if want_logits else None,
-                                     tok.data_ptr(), seq.data_ptr(), _stream(input_ids))
+    B, N, L, Cn, T = _tf_inputs("teacher_forced", input_ids, attention_mask, decoder_input_ids, labels, vocab_size)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
+    f = dict(dtype=torch.float32, device=input_ids.device)
+    logits = torch.empty((B, Cn, T, vocab_size) if want_logits else (0,), **f)
+    tok = torch.empty(B, Cn, T, **f)
+    seq = torch.empty(B, Cn, **f)
+    with torch.cuda.device(input_ids.device):
+        rc = lib.gram_teacher_forced(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, _ref(comp),
+                                     decoder_input_ids.data_ptr(), labels.data_ptr(), Cn, T, workspace.data_ptr(), workspace.numel(),
+                                     logits.data_ptr() if want_logits else None, tok.data_ptr(), seq.data_ptr(), _stream(input_ids))
     _lib.check(rc, "gram_teacher_forced")
     return logits, tok, seq
 
@@ -236,34 +255,20 @@ def teacher_forced_attn(input_ids: Tensor, attention_mask: Tensor, handle: int, 
                         labels: Tensor, vocab_size: int, n_dec_layers: int, n_heads: int, want_probs: bool, want_scores: bool,
                         comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor],
                         cache_x: Optional[Tensor], n_cached: int, cache_L: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """The teacher-forced pass of ``teacher_forced`` (same inputs, validated the same way) with its cross-attention probabilities
-    (gram_teacher_forced_ex).  ``n_dec_layers`` / ``n_heads`` are the model's (they size the outputs).  Returns
+    """The teacher-forced pass of ``teacher_forced`` (same inputs, validated by the same ``_tf_inputs``) with its cross-attention
+    probabilities (gram_teacher_forced_ex).  ``n_dec_layers`` / ``n_heads`` are the model's (they size the outputs).  Returns
     (probs f32 (n_dec_layers, B, H, C*T, N*L) -- empty unless want_probs: then one layer at a time lives in a scratch tensor --,
     token_scores f32 (B, C*T, N*L) = their sum over layers and heads, passage_scores f32 (B, C*T, N) = per passage the sum over its
     valid keys / (valid keys * n_dec_layers * n_heads), NaN for a passage without one -- both empty unless want_scores)."""
     lib = _lib.load()
-    dev = input_ids.device
-    if input_ids.dim() != 3 or decoder_input_ids.dim() != 3:
-        raise ValueError("teacher_forced_attn: input_ids must be (B, N, L) and decoder_input_ids (B, C, T)")
     if not (want_probs or want_scores):
         raise ValueError("teacher_forced_attn: nothing requested (want_probs / want_scores)")
-    B, N, L = input_ids.shape
-    Bd, Cn, T = decoder_input_ids.shape
-    _check("input_ids", input_ids, torch.int64)
-    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
-    _check("decoder_input_ids", decoder_input_ids, torch.int32, (B, None, None), dev)
-    _check("labels", labels, torch.int32, (B, Cn, T), dev)
-    if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN or Cn < 1 or n_dec_layers < 1 or n_heads < 1:
-        raise ValueError(f"teacher_forced_attn: need 1 <= T <= {_lib.GRAM_MAX_DEC_LEN}, C >= 1, n_dec_layers >= 1, n_heads >= 1")
-    lo_d, hi_d, hi_l = torch.stack([decoder_input_ids.min(), decoder_input_ids.max(), labels.max()]).tolist()
-    if lo_d < 0 or hi_d >= vocab_size or hi_l >= vocab_size:
-        raise ValueError(f"teacher_forced_attn: decoder_input_ids must lie in [0, {vocab_size}) and labels below {vocab_size}")
-    comp = None
-    if comp_map is not None:
-        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
-                               _p(cache_slot))
+    if n_dec_layers < 1 or n_heads < 1:
+        raise ValueError("teacher_forced_attn: need n_dec_layers >= 1, n_heads >= 1")
+    B, N, L, Cn, T = _tf_inputs("teacher_forced_attn", input_ids, attention_mask, decoder_input_ids, labels, vocab_size)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
     Q, S = Cn * T, N * L
-    f = dict(dtype=torch.float32, device=dev)
+    f = dict(dtype=torch.float32, device=input_ids.device)
     probs = torch.empty((n_dec_layers, B, n_heads, Q, S) if want_probs else (0,), **f)
     layer = None if want_probs else torch.empty(B, n_heads, Q, S, **f)
     tsc = torch.empty((B, Q, S) if want_scores else (0,), **f)
@@ -272,11 +277,10 @@ def teacher_forced_attn(input_ids: Tensor, attention_mask: Tensor, handle: int, 
     seq = torch.empty(B, Cn, **f)
     attn = _lib.XattnOut(probs.data_ptr() if want_probs else None, _p(layer), tsc.data_ptr() if want_scores else None,
                          psc.data_ptr() if want_scores else None)
-    with torch.cuda.device(dev):
-        rc = lib.gram_teacher_forced_ex(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
-                                        C.byref(comp) if comp is not None else None, decoder_input_ids.data_ptr(), labels.data_ptr(),
-                                        Cn, T, workspace.data_ptr(), workspace.numel(), None, tok.data_ptr(), seq.data_ptr(),
-                                        C.byref(attn), _stream(input_ids))
+    with torch.cuda.device(input_ids.device):
+        rc = lib.gram_teacher_forced_ex(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, _ref(comp),
+                                        decoder_input_ids.data_ptr(), labels.data_ptr(), Cn, T, workspace.data_ptr(), workspace.numel(),
+                                        None, tok.data_ptr(), seq.data_ptr(), C.byref(attn), _stream(input_ids))
     _lib.check(rc, "gram_teacher_forced_ex")
     return probs, tsc, psc
 
@@ -298,42 +302,25 @@ def teacher_forced_scores(input_ids: Tensor, attention_mask: Tensor, handle: int
                           labels: Tensor, vocab_size: int, comp_map: Optional[Tensor], comp_ids: Optional[Tensor],
                           comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor], n_cached: int,
                           cache_L: int) -> Tuple[Tensor, Tensor]:
-    """The teacher-forced pass of ``teacher_forced`` (same inputs, validated the same way) with the cross-attention scores summed
-    over heads inside the kernel (gram_teacher_forced_scores): no per-head buffer, any N*L the handle takes -- which must have been
-    raised by gram_model_set_max_fused_len (GRAM_E_ARG otherwise).  Returns (token_scores f32 (B, C*T, N*L) = the probabilities
-    summed over layers and heads, passage_scores f32 (B, C*T, N) = per passage the sum over its valid keys / (valid keys *
-    n_dec_layers * n_heads), NaN for a passage without one)."""
+    """The teacher-forced pass of ``teacher_forced`` (same inputs, validated by the same ``_tf_inputs``) with the cross-attention
+    scores summed over heads inside the kernel (gram_teacher_forced_scores): no per-head buffer, any N*L the handle takes -- which
+    must have been raised by gram_model_set_max_fused_len (GRAM_E_ARG otherwise).  Returns (token_scores f32 (B, C*T, N*L) = the
+    probabilities summed over layers and heads, passage_scores f32 (B, C*T, N) = per passage the sum over its valid keys / (valid
+    keys * n_dec_layers * n_heads), NaN for a passage without one)."""
     lib = _lib.load()
-    dev = input_ids.device
-    if input_ids.dim() != 3 or decoder_input_ids.dim() != 3:
-        raise ValueError("teacher_forced_scores: input_ids must be (B, N, L) and decoder_input_ids (B, C, T)")
-    B, N, L = input_ids.shape
-    Bd, Cn, T = decoder_input_ids.shape
-    _check("input_ids", input_ids, torch.int64)
-    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
-    _check("decoder_input_ids", decoder_input_ids, torch.int32, (B, None, None), dev)
-    _check("labels", labels, torch.int32, (B, Cn, T), dev)
-    if not 1 <= T <= _lib.GRAM_MAX_DEC_LEN or Cn < 1:
-        raise ValueError(f"teacher_forced_scores: need 1 <= T <= {_lib.GRAM_MAX_DEC_LEN} and C >= 1 (got C={Cn}, T={T})")
-    lo_d, hi_d, hi_l = torch.stack([decoder_input_ids.min(), decoder_input_ids.max(), labels.max()]).tolist()
-    if lo_d < 0 or hi_d >= vocab_size or hi_l >= vocab_size:
-        raise ValueError(f"teacher_forced_scores: decoder_input_ids must lie in [0, {vocab_size}) and labels below {vocab_size}")
-    comp = None
-    if comp_map is not None:
-        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
-                               _p(cache_slot))
+    B, N, L, Cn, T = _tf_inputs("teacher_forced_scores", input_ids, attention_mask, decoder_input_ids, labels, vocab_size)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
     Q, S = Cn * T, N * L
-    f = dict(dtype=torch.float32, device=dev)
+    f = dict(dtype=torch.float32, device=input_ids.device)
     tsc = torch.empty(B, Q, S, **f)
     psc = torch.empty(B, Q, N, **f)
     tok = torch.empty(B, Cn, T, **f)
     seq = torch.empty(B, Cn, **f)
     out = _lib.XattnScores(tsc.data_ptr(), psc.data_ptr())
-    with torch.cuda.device(dev):
-        rc = lib.gram_teacher_forced_scores(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
-                                            C.byref(comp) if comp is not None else None, decoder_input_ids.data_ptr(),
-                                            labels.data_ptr(), Cn, T, workspace.data_ptr(), workspace.numel(), None, tok.data_ptr(),
-                                            seq.data_ptr(), C.byref(out), _stream(input_ids))
+    with torch.cuda.device(input_ids.device):
+        rc = lib.gram_teacher_forced_scores(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, _ref(comp),
+                                            decoder_input_ids.data_ptr(), labels.data_ptr(), Cn, T, workspace.data_ptr(),
+                                            workspace.numel(), None, tok.data_ptr(), seq.data_ptr(), C.byref(out), _stream(input_ids))
     _lib.check(rc, "gram_teacher_forced_scores")
     return tsc, psc
 
@@ -386,20 +373,16 @@ def score_trie(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace
     if not ok:
         raise ValueError("score_trie: a row table entry is out of range (tokens in [0, vocab), pos in [0, Tq), anc in [0, Q), "
                          "row_node in [0, n_nodes), node_row in [-1, Q), node_tok in [-1, vocab), node_leaf in [-1, n_leaves))")
-    trie = _lib.Trie(trie_child_off.data_ptr(), trie_child_tok.data_ptr(), trie_child_node.data_ptr(), n_nodes, trie_child_tok.numel(),
-                     trie_max_fanout, trie_min_seq_len)
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
     rows = _lib.TrieRows(row_tokens.data_ptr(), row_pos.data_ptr(), row_anc.data_ptr(), row_node.data_ptr(), node_row.data_ptr(),
                          node_tok.data_ptr(), node_leaf.data_ptr(), Q, Tq, n_nodes, n_leaves)
-    comp = None
-    if comp_map is not None:
-        comp = _lib.Compaction(comp_map.numel(), comp_map.data_ptr(), _p(comp_ids), _p(comp_mask), n_cached, cache_L, _p(cache_x),
-                               _p(cache_slot))
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
     leaf = torch.empty(B, n_leaves, dtype=torch.float32, device=dev)
     nodes = torch.empty((B, n_nodes) if want_nodes else (0,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.gram_score_trie(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L,
-                                 C.byref(comp) if comp is not None else None, C.byref(trie), C.byref(rows), workspace.data_ptr(),
-                                 workspace.numel(), leaf.data_ptr(), nodes.data_ptr() if want_nodes else None, _stream(input_ids))
+        rc = lib.gram_score_trie(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, _ref(comp), C.byref(trie),
+                                 C.byref(rows), workspace.data_ptr(), workspace.numel(), leaf.data_ptr(),
+                                 nodes.data_ptr() if want_nodes else None, _stream(input_ids))
     _lib.check(rc, "gram_score_trie")
     return leaf, nodes
 
@@ -442,74 +425,75 @@ def _(a, w, relu=False):
 
 
 # ---------------------------------------------------------------------------------------------- encoder self-attention
-@torch.library.custom_op("gram::enc_self_attn", mutates_args=(), device_types="cuda")
-def enc_self_attn(qkv: Tensor, bias: Tensor, mask: Tensor, num_heads: int) -> Tensor:
-    """qkv 16-bit (P*L, 3*inner) rows q|k|v; bias f32 (H, 255) by (key - query + 127); mask u8 (P, L) -> 16-bit (P*L, inner)."""
+def _enc_self_attn(op: str, max_len: int, fn: str, qkv: Tensor, bias: Tensor, mask: Tensor, num_heads: int, *pieces) -> Tensor:
+    """Both encoder self-attention ops: passages of up to ``max_len`` tokens through the C call ``fn``, whose piece arguments (the
+    split form's) are ``pieces``."""
     dt = _lib.piece_dtype()
     if mask.dim() != 2:
-        raise ValueError("enc_self_attn: mask must be (P, L)")
+        raise ValueError(f"{op}: mask must be (P, L)")
     P, L = mask.shape
     inner = num_heads * 64
     _check("qkv", qkv, dt, (P * L, 3 * inner))
     _check("bias", bias, torch.float32, (num_heads, 255), qkv.device)
     _check("mask", mask, torch.uint8, None, qkv.device)
-    if L < 32 or L > _lib.GRAM_MAX_PASSAGE_LEN or L % 32 or num_heads < 1:
-        raise ValueError(f"enc_self_attn: L must be a multiple of 32 in [32, {_lib.GRAM_MAX_PASSAGE_LEN}] (got {L})")
+    if L < 32 or L > max_len or L % 32 or num_heads < 1:
+        raise ValueError(f"{op}: L must be a multiple of 32 in [32, {max_len}] (got {L})")
     out = torch.empty(P * L, inner, dtype=dt, device=qkv.device)
     with torch.cuda.device(qkv.device):
-        rc = _lib.load().gram_enc_self_attn(qkv.data_ptr(), bias.data_ptr(), mask.data_ptr(), out.data_ptr(), P, L, num_heads,
-                                            _stream(qkv))
-    _lib.check(rc, "gram_enc_self_attn")
+        rc = getattr(_lib.load(), fn)(qkv.data_ptr(), bias.data_ptr(), mask.data_ptr(), out.data_ptr(), P, L, num_heads, *pieces,
+                                      _stream(qkv))
+    _lib.check(rc, fn)
     return out
 
 
-@enc_self_attn.register_fake
-def _(qkv, bias, mask, num_heads):
+def _enc_self_attn_fake(qkv, bias, mask, num_heads):
     return qkv.new_empty(qkv.shape[0], num_heads * 64)
+
+
+@torch.library.custom_op("gram::enc_self_attn", mutates_args=(), device_types="cuda")
+def enc_self_attn(qkv: Tensor, bias: Tensor, mask: Tensor, num_heads: int) -> Tensor:
+    """qkv 16-bit (P*L, 3*inner) rows q|k|v; bias f32 (H, 255) by (key - query + 127); mask u8 (P, L) -> 16-bit (P*L, inner)."""
+    return _enc_self_attn("enc_self_attn", _lib.GRAM_MAX_PASSAGE_LEN, "gram_enc_self_attn", qkv, bias, mask, num_heads)
 
 
 @torch.library.custom_op("gram::enc_self_attn_long", mutates_args=(), device_types="cuda")
 def enc_self_attn_long(qkv: Tensor, bias: Tensor, mask: Tensor, num_heads: int) -> Tensor:
     """``enc_self_attn`` for passages of up to 512 tokens (gram_enc_self_attn_long_split, one piece): the same operands; the bias
     index is clamp(key - query, -127, 127) + 127, so the (H, 255) table must be constant beyond +-127."""
-    dt = _lib.piece_dtype()
-    if mask.dim() != 2:
-        raise ValueError("enc_self_attn_long: mask must be (P, L)")
-    P, L = mask.shape
-    inner = num_heads * 64
-    _check("qkv", qkv, dt, (P * L, 3 * inner))
-    _check("bias", bias, torch.float32, (num_heads, 255), qkv.device)
-    _check("mask", mask, torch.uint8, None, qkv.device)
-    if L < 32 or L > _lib.GRAM_MAX_LONG_PASSAGE_LEN or L % 32 or num_heads < 1:
-        raise ValueError(f"enc_self_attn_long: L must be a multiple of 32 in [32, {_lib.GRAM_MAX_LONG_PASSAGE_LEN}] (got {L})")
-    out = torch.empty(P * L, inner, dtype=dt, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        rc = _lib.load().gram_enc_self_attn_long_split(qkv.data_ptr(), bias.data_ptr(), mask.data_ptr(), out.data_ptr(), P, L, num_heads,
-                                                       1, 0, _stream(qkv))
-    _lib.check(rc, "gram_enc_self_attn_long_split")
-    return out
+    return _enc_self_attn("enc_self_attn_long", _lib.GRAM_MAX_LONG_PASSAGE_LEN, "gram_enc_self_attn_long_split", qkv, bias, mask,
+                          num_heads, 1, 0)
 
 
-@enc_self_attn_long.register_fake
-def _(qkv, bias, mask, num_heads):
-    return qkv.new_empty(qkv.shape[0], num_heads * 64)
+enc_self_attn.register_fake(_enc_self_attn_fake)
+enc_self_attn_long.register_fake(_enc_self_attn_fake)
 
 
 # ---------------------------------------------------------------------------------------------- cross-attention decode
-@torch.library.custom_op("gram::cross_attn_decode", mutates_args=(), device_types="cuda")
-def cross_attn_decode(q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor, num_beams: int) -> Tensor:
-    """q bf16 (B*K, inner); k_bank bf16 (B, H, S, 64); vt_bank bf16 (B, H, S/32, 64, 32) = V transposed, blocked by 32 keys (one
-    copy per user, shared by its K beams); mask u8 (B, S) -> bf16 (B*K, inner)."""
+def _cross_attn_inputs(op: str, max_keys: int, q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor,
+                       num_beams: int) -> Tuple[int, int, int]:
+    """What both cross-attention ops require of their operands, over up to ``max_keys`` keys; returns (B, H, S)."""
     dt = _lib.piece_dtype()
     if k_bank.dim() != 4 or k_bank.shape[-1] != 64:
-        raise ValueError("cross_attn_decode: k_bank must be (B, H, S, 64)")
+        raise ValueError(f"{op}: k_bank must be (B, H, S, 64)")
     B, H, S, _ = k_bank.shape
-    if S < 32 or S % 32 or S > 4096 or not 1 <= num_beams <= _lib.GRAM_MAX_BEAMS:
-        raise ValueError(f"cross_attn_decode: S must be a multiple of 32 in [32, 4096] and 1 <= num_beams <= {_lib.GRAM_MAX_BEAMS}")
+    if S < 32 or S % 32 or S > max_keys or not 1 <= num_beams <= _lib.GRAM_MAX_BEAMS:
+        raise ValueError(f"{op}: S must be a multiple of 32 in [32, {max_keys}] and 1 <= num_beams <= {_lib.GRAM_MAX_BEAMS}")
     _check("k_bank", k_bank, dt)
     _check("vt_bank", vt_bank, dt, (B, H, S // 32, 64, 32), k_bank.device)  # V^T blocked by 32 keys
     _check("q", q, dt, (B * num_beams, H * 64), k_bank.device)
     _check("mask", mask, torch.uint8, (B, S), k_bank.device)
+    return B, H, S
+
+
+def _cross_attn_fake(q, k_bank, vt_bank, mask, num_beams):
+    return torch.empty_like(q)
+
+
+@torch.library.custom_op("gram::cross_attn_decode", mutates_args=(), device_types="cuda")
+def cross_attn_decode(q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor, num_beams: int) -> Tensor:
+    """q bf16 (B*K, inner); k_bank bf16 (B, H, S, 64); vt_bank bf16 (B, H, S/32, 64, 32) = V transposed, blocked by 32 keys (one
+    copy per user, shared by its K beams); mask u8 (B, S) -> bf16 (B*K, inner)."""
+    B, H, S = _cross_attn_inputs("cross_attn_decode", _lib.GRAM_MAX_FUSED_LEN, q, k_bank, vt_bank, mask, num_beams)
     out = torch.empty_like(q)
     with torch.cuda.device(q.device):
         rc = _lib.load().gram_cross_attn_decode(q.data_ptr(), k_bank.data_ptr(), vt_bank.data_ptr(), mask.data_ptr(), out.data_ptr(),
@@ -518,27 +502,12 @@ def cross_attn_decode(q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor, 
     return out
 
 
-@cross_attn_decode.register_fake
-def _(q, k_bank, vt_bank, mask, num_beams):
-    return torch.empty_like(q)
-
-
 @torch.library.custom_op("gram::cross_attn_long", mutates_args=(), device_types="cuda")
 def cross_attn_long(q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor, num_beams: int) -> Tensor:
     """``cross_attn_decode`` over up to 16 384 fused keys (gram_mask_key_bits_long + gram_cross_attn_long_split, one piece): the same
     operands.  A row's bits depend on the query row and the user's valid 32-key steps in order, not on the batch or on S; they are
     not ``cross_attn_decode``'s bits (another summation order)."""
-    dt = _lib.piece_dtype()
-    if k_bank.dim() != 4 or k_bank.shape[-1] != 64:
-        raise ValueError("cross_attn_long: k_bank must be (B, H, S, 64)")
-    B, H, S, _ = k_bank.shape
-    if S < 32 or S % 32 or S > _lib.GRAM_MAX_LONG_FUSED_LEN or not 1 <= num_beams <= _lib.GRAM_MAX_BEAMS:
-        raise ValueError(f"cross_attn_long: S must be a multiple of 32 in [32, {_lib.GRAM_MAX_LONG_FUSED_LEN}] and "
-                         f"1 <= num_beams <= {_lib.GRAM_MAX_BEAMS}")
-    _check("k_bank", k_bank, dt)
-    _check("vt_bank", vt_bank, dt, (B, H, S // 32, 64, 32), k_bank.device)  # V^T blocked by 32 keys
-    _check("q", q, dt, (B * num_beams, H * 64), k_bank.device)
-    _check("mask", mask, torch.uint8, (B, S), k_bank.device)
+    B, H, S = _cross_attn_inputs("cross_attn_long", _lib.GRAM_MAX_LONG_FUSED_LEN, q, k_bank, vt_bank, mask, num_beams)
     lib = _lib.load()
     out = torch.empty_like(q)
     bits = torch.empty(B, _lib.GRAM_KEY_BITS_LONG_STRIDE, dtype=torch.int32, device=q.device)
@@ -551,9 +520,8 @@ def cross_attn_long(q: Tensor, k_bank: Tensor, vt_bank: Tensor, mask: Tensor, nu
     return out
 
 
-@cross_attn_long.register_fake
-def _(q, k_bank, vt_bank, mask, num_beams):
-    return torch.empty_like(q)
+cross_attn_decode.register_fake(_cross_attn_fake)
+cross_attn_long.register_fake(_cross_attn_fake)
 
 
 # ---------------------------------------------------------------------------------------------- Trie-constrained search step
@@ -590,8 +558,7 @@ def trie_step(logits: Tensor, tokens: Tensor, node: Tensor, beam_scores: Tensor,
                         node=node.data_ptr(), beam_scores=beam_scores.data_ptr(), seq=seq.data_ptr(), anc=anc.data_ptr(),
                         done=done.data_ptr(), n_hyps=n_hyps.data_ptr(), hyp_score=hyp_score.data_ptr(), worst=worst.data_ptr(),
                         hyp_len=hyp_len.data_ptr(), hyp_tok=hyp_tok.data_ptr(), error=error.data_ptr())
-    trie = _lib.Trie(trie_child_off.data_ptr(), trie_child_tok.data_ptr(), trie_child_node.data_ptr(), trie_child_off.numel() - 1,
-                     trie_child_tok.numel(), trie_max_fanout, 0)
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, 0)  # (a dense step has no minimum length)
     lse = torch.empty(R, dtype=torch.float32, device=logits.device)
     with torch.cuda.device(logits.device):
         _lib.check(lib.gram_row_lse(logits.data_ptr(), lse.data_ptr(), R, V, _stream(logits)), "gram_row_lse")

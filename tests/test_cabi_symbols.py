@@ -60,7 +60,11 @@ def test_ctypes_structs_match_the_header(tmp_path):
     import subprocess
     pairs = {"gram_kv_bank_t": _lib.KVBank, "gram_norm_fusion_t": _lib.NormFusion, "gram_split_t": _lib.Split, "gram_trie_t": _lib.Trie,
              "gram_beam_state_t": _lib.BeamState, "gram_live_rows_t": _lib.LiveRows, "gram_model_desc_t": _lib.ModelDesc,
-             "gram_compaction_t": _lib.Compaction}
+             "gram_compaction_t": _lib.Compaction, "gram_user_items_t": _lib.UserItems, "gram_xattn_out_t": _lib.XattnOut,
+             "gram_xattn_scores_t": _lib.XattnScores, "gram_trie_rows_t": _lib.TrieRows, "gram_trie_tail_t": _lib.TrieTail,
+             "gram_forest_t": _lib.Forest}
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gram_hip.h")).read(), flags=re.S)
+    assert sorted(re.findall(r"^\}\s*(gram_\w+_t)\s*;", header, flags=re.M)) == sorted(pairs)  # every struct the header defines
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "gram_hip.h"', "int main(void) {"]
     for cname, st in pairs.items():
         lines.append(f'  printf("{cname} size %zu\\n", sizeof({cname}));')

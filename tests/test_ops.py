@@ -92,3 +92,101 @@ def test_ops_refuse_malformed_tensors():
     for args in ((qkv[:, :256], bias, m2, 2), (qkv, bias[:, :200].contiguous(), m2, 2), (qkv, bias, torch.ones(2, 48, dtype=torch.uint8, device="cuda"), 2)):
         with pytest.raises((ValueError, RuntimeError)):
             torch.ops.gram.enc_self_attn(*args)
+
+
+@pytest.mark.gpu
+def test_whole_path_ops_refuse_before_they_launch():
+    """teacher_forced, teacher_forced_attn, teacher_forced_scores, score_trie and generate_items with one malformed argument at a
+    time, at the smallest shapes and on ``handle = 0``: each must be refused in Python, as a ``ValueError``.  A call that slips past
+    the Python checks reaches the C ABI, which answers a null handle with GRAM_E_ARG -- a ``GramHipError``, a ``RuntimeError`` -- so
+    it fails here; the well-formed teacher-forced and score_trie calls show exactly that (no launch either: the C side refuses
+    first).  Nothing runs on the device but the min / max reductions of the range checks."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
+
+    def dev(data, dtype=i32):
+        return torch.tensor(data, dtype=dtype, device="cuda")
+
+    def put(t, index, v):
+        t = t.clone()
+        t[index] = v
+        return t
+
+    V, L = 16, 32
+    nocomp = (None, None, None, None, None, 0, 0)
+    base = dict(input_ids=torch.zeros(1, 1, L, dtype=i64, device="cuda"), attention_mask=torch.ones(1, 1, L, dtype=u8, device="cuda"),
+                handle=0, workspace=torch.zeros(1024, dtype=u8, device="cuda"))
+    wide = torch.ones(1, 1, 2 * L, dtype=u8, device="cuda")
+    bad_inputs = [dict(input_ids=base["input_ids"].to(i32)), dict(input_ids=torch.zeros(1, 1, 2 * L, dtype=i64, device="cuda")[:, :, ::2]),
+                  dict(attention_mask=base["attention_mask"].bool()), dict(attention_mask=wide), dict(attention_mask=wide[:, :, ::2]),
+                  dict(attention_mask=wide[:, :, 1:L + 1])]
+
+    def refused(op, order, good, bads):
+        for bad in bads:
+            args = dict(good, **bad)
+            with pytest.raises(ValueError):
+                op(*(args[k] for k in order), *nocomp)
+            assert sorted(args) == sorted(order)
+
+    # ---- the three teacher-forced ops: B = 1, N = 1, L = 32, C = 1, T = 2
+    dec, lab = dev([[[0, V - 1]]]), dev([[[V - 1, -100]]])
+    tf = dict(base, decoder_input_ids=dec, labels=lab, vocab_size=V)
+    long_T = torch.zeros(1, 1, _lib.GRAM_MAX_DEC_LEN + 1, dtype=i32, device="cuda")
+    bad_tf = bad_inputs + [
+        dict(decoder_input_ids=dec.to(i64)), dict(labels=lab.to(i64)), dict(labels=lab.float()),
+        dict(decoder_input_ids=dev([[[0, 9, 1, 9]]])[:, :, ::2]), dict(labels=dev([[[0, 9, 1, 9]]])[:, :, ::2]),
+        dict(decoder_input_ids=dev([[[9, 0, 1]]])[:, :, 1:]), dict(labels=dev([[[9, 0, 1]]])[:, :, 1:]),      # (not 16-byte aligned)
+        dict(labels=dev([[[1, 2, 3]]])), dict(labels=dev([[[1, 2]], [[1, 2]]])), dict(labels=lab[0]), dict(decoder_input_ids=dec[0]),
+        dict(decoder_input_ids=dec[:, :, :0], labels=lab[:, :, :0]), dict(decoder_input_ids=long_T, labels=long_T),
+        dict(decoder_input_ids=put(dec, (0, 0, 1), -1)), dict(decoder_input_ids=put(dec, (0, 0, 0), V)), dict(labels=put(lab, (0, 0, 1), V)),
+        dict(input_ids=base["input_ids"].cpu()), dict(labels=lab.cpu())]
+    head = ("input_ids", "attention_mask", "handle", "workspace", "decoder_input_ids", "labels", "vocab_size")
+    for op, extra, more in ((torch.ops.gram.teacher_forced, dict(want_logits=False), []),
+                            (torch.ops.gram.teacher_forced_attn, dict(n_dec_layers=2, n_heads=2, want_probs=False, want_scores=True),
+                             [dict(n_dec_layers=0), dict(n_heads=0), dict(want_scores=False)]),
+                            (torch.ops.gram.teacher_forced_scores, {}, [])):
+        good, order = dict(tf, **extra), head + tuple(extra)
+        refused(op, order, good, bad_tf + more)
+        with pytest.raises(_lib.GramHipError):  # well-formed: past the Python checks, refused by the C ABI for its null handle
+            op(*(good[k] for k in order), *nocomp)
+
+    # ---- a Trie of three nodes: root -5-> node 1 -1-> leaf 2 (one item); rows for the two internal nodes
+    trie = dict(trie_child_off=dev([0, 1, 2, 2]), trie_child_tok=dev([5, 1]), trie_child_node=dev([1, 2]), trie_max_fanout=1,
+                trie_min_seq_len=3)
+    rows = dict(row_tokens=dev([0, 5]), row_pos=dev([0, 1]), row_anc=dev([[0, 0], [0, 1]]), row_node=dev([0, 1]), node_row=dev([0, 1, -1]),
+                node_tok=dev([-1, 5, 1]), node_leaf=dev([-1, -1, 0]), n_leaves=1, vocab_size=V, want_nodes=True)
+    good = dict(base, **trie, **rows)
+    order = tuple(base) + tuple(trie) + tuple(rows)
+    bad_rows = bad_inputs + [
+        dict(row_tokens=rows["row_tokens"].to(i64)), dict(node_leaf=rows["node_leaf"].float()), dict(trie_child_off=trie["trie_child_off"].to(i64)),
+        dict(row_anc=rows["row_anc"].t()), dict(row_anc=rows["row_anc"][0]), dict(row_pos=dev([0, 9, 1, 9])[::2]),
+        dict(row_node=dev([9, 0, 1])[1:]), dict(node_row=dev([0, 1, -1, -1])), dict(node_tok=dev([-1, 5])), dict(row_tokens=dev([0, 5, 1])),
+        dict(trie_child_node=dev([1, 2, 2])), dict(trie_child_off=dev([0, 1, 2])), dict(n_leaves=0), dict(n_leaves=3),
+        dict(row_tokens=dev([0, V])), dict(row_tokens=dev([-1, 5])), dict(row_pos=dev([0, 2])), dict(row_pos=dev([-1, 1])),
+        dict(row_anc=dev([[0, 0], [0, 2]])), dict(row_anc=dev([[0, -1], [0, 1]])), dict(row_node=dev([0, 3])), dict(row_node=dev([-1, 1])),
+        dict(node_row=dev([0, 2, -1])), dict(node_row=dev([0, 1, -2])), dict(node_tok=dev([-1, V, 1])), dict(node_tok=dev([-2, 5, 1])),
+        dict(node_leaf=dev([-1, -1, 1])), dict(node_leaf=dev([-2, -1, 0])), dict(node_leaf=rows["node_leaf"].cpu())]
+    refused(torch.ops.gram.score_trie, order, good, bad_rows)
+    with pytest.raises(_lib.GramHipError):
+        torch.ops.gram.score_trie(*(good[k] for k in order), *nocomp)
+
+    # ---- generate_items: one candidate (n_items = 1), M = 2 list entries (the well-formed call would prepare the lists on the device
+    #      before the C ABI sees the handle, so it is not made here)
+    search = dict(num_beams=2, num_return_sequences=2, max_length=3, length_penalty=1.0)
+    filt = dict(leaf_lo=dev([0, 0, 0]), leaf_hi=dev([1, 1, 1]), item_rank=dev([0]), items=dev([[0, -1]]), allow=False)
+    comp = dict(zip(("comp_map", "comp_ids", "comp_mask", "cache_slot", "cache_x", "n_cached", "cache_L"), nocomp))
+    good = dict(base, **trie, **search, **comp, **filt)
+    order = tuple(base) + tuple(trie) + tuple(search) + tuple(comp) + tuple(filt)
+    bad_items = bad_inputs + [
+        dict(items=filt["items"].to(i64)), dict(items=dev([[0, 9, -1, 9]])[:, ::2]), dict(items=dev([[9, 0, -1]])[:, 1:]),
+        dict(items=dev([0, -1])), dict(items=dev([[0, -1], [0, -1]])), dict(items=torch.zeros(1, 0, dtype=i32, device="cuda")),
+        dict(items=torch.zeros(1, _lib.GRAM_MAX_USER_ITEMS + 1, dtype=i32, device="cuda")), dict(items=dev([[0, 1]])), dict(items=dev([[0, -2]])),
+        dict(item_rank=torch.zeros(0, dtype=i32, device="cuda")), dict(item_rank=dev([[0]])), dict(item_rank=dev([0], i64)),
+        dict(leaf_lo=dev([0, 0])), dict(leaf_hi=dev([1, 1, 1, 1])), dict(leaf_hi=filt["leaf_hi"].to(i64)),
+        dict(trie_child_node=dev([1, 2, 2])), dict(trie_child_tok=dev([5, 1], i64)), dict(trie_child_off=torch.zeros(1, dtype=i32, device="cuda")),
+        dict(items=filt["items"].cpu())]
+    for bad in bad_items:
+        args = dict(good, **bad)
+        with pytest.raises(ValueError):
+            torch.ops.gram.generate_items(*(args[k] for k in order))
