@@ -95,6 +95,11 @@ class UserItems(C.Structure):
     _fields_ = [("leaf_lo", vp), ("leaf_hi", vp), ("ranks", vp), ("count", vp), ("stride", i32), ("mode", i32)]
 
 
+class SampleParams(C.Structure):
+    """gram_sample_params_t: temperature > 0, top_k >= 0 (0 = off), top_p in (0, 1] (1 = off)"""
+    _fields_ = [("temperature", f32), ("top_k", i32), ("top_p", f32)]
+
+
 class XattnOut(C.Structure):
     """gram_xattn_out_t: the attention outputs of gram_teacher_forced_ex (device pointers, None = not wanted)"""
     _fields_ = [("probs", vp), ("layer_probs", vp), ("token_scores", vp), ("passage_scores", vp)]
@@ -273,6 +278,19 @@ SIGNATURES = {
     "gram_debug_set_tail_level_capacity": (C.c_int, [C.c_int]),
     "gram_debug_tail_last": (C.c_int, [C.POINTER(i32)]),
     "gram_debug_workspace_beam_state": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BeamState)]),
+    # Trie-constrained sampling
+    "gram_sample_step": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(SampleParams), vp, C.c_int, vp, vp, vp]),
+    "gram_sample_step_items": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(SampleParams), vp, C.c_int, vp, vp, C.POINTER(UserItems), vp]),
+    "gram_sample_finalize": (C.c_int, [C.POINTER(BeamState), C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "gram_sample_capacity": (C.c_int, []),
+    "gram_debug_set_sample_capacity": (C.c_int, [C.c_int]),
+    "gram_workspace_bytes_sample": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gram_sample": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Trie), C.POINTER(Compaction),
+                              C.POINTER(SampleParams), vp, vp, i64, vp, vp, vp, C.POINTER(i32), vp]),
+    "gram_sample_items": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Trie), C.POINTER(Compaction),
+                                    C.POINTER(UserItems), C.POINTER(SampleParams), vp, vp, i64, vp, vp, vp, C.POINTER(i32), vp]),
 }
 
 # the `_f16` aliases (gram_hip.h): same signatures as the `_bf16` names

@@ -18,35 +18,12 @@
 // One workgroup per user; users are independent, so this shards trivially.
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "common.h"
 #include "prof.h"
 #include "sparse_dot.h"
+#include "trie_dev.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) {
-  uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-  return __uint_as_float(u);
-}
-
-// index of tok among node's children, or -1
-__device__ int find_child(const gram_trie_t& tr, int node, int tok) {
-  if (node < 0) return -1;
-  int lo = tr.child_off[node], hi = tr.child_off[node + 1];
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    int v = tr.child_tok[mid];
-    if (v == tok) return mid;
-    if (v < tok) lo = mid + 1; else hi = mid;
-  }
-  return -1;
-}
 
 __device__ double norm_len(int len, float lp) {
   if (lp == 1.0f) return (double)len;
@@ -137,40 +114,7 @@ struct StepArgs {
   const gram_user_items_t* ui;  // per-user item filter (the FILT instantiations only; nullptr otherwise)
 };
 
-// ---- per-user item filters (gram_user_items_t).  FILT is a compile-time property of the step kernels: the unfiltered instantiations
-// carry none of this.  The alive test below is the ONE definition that the key builders (dense_window, sparse_window, shared0_keys),
-// flag_nonfinite_keys (through the zero key), step_finish (the ranked walk and the filler loop) and the greedy step all share.
-// A step kernel's filter is its trailing parameter pack UI: nothing (unfiltered: the parameter list and the code of a kernel without
-// the pack) or one gram_user_items_t (FILT).
-template <typename... UI>
-constexpr bool filtered() {
-  static_assert(sizeof...(UI) == 0 || (sizeof...(UI) == 1 && (std::is_same_v<UI, gram_user_items_t> && ...)),
-                "a step kernel's trailing pack is empty or one gram_user_items_t");
-  return sizeof...(UI) != 0;
-}
-__device__ __forceinline__ const gram_user_items_t* items_ptr() { return nullptr; }
-__device__ __forceinline__ const gram_user_items_t* items_ptr(const gram_user_items_t& u) { return &u; }
-
-// first index in r[0, n) whose value is >= v
-__device__ __forceinline__ int rank_lower_bound(const int32_t* __restrict__ r, int n, int v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (r[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// does user b keep an item below `node`?  c = the user's ranks inside the node's leaf range [lo, hi): allow mode keeps the node
-// iff c > 0, exclude mode iff some leaf of the range is not listed (the ranks are distinct: c <= hi - lo)
-__device__ __forceinline__ bool node_alive(const gram_user_items_t& ui, int b, int node) {
-  const int lo = ui.leaf_lo[node], hi = ui.leaf_hi[node];
-  const int32_t* __restrict__ r = ui.ranks + (size_t)b * ui.stride;
-  int n = ui.count[b];
-  n = n < 0 ? 0 : (n > ui.stride ? ui.stride : n);  // (a wrong count must not reach past the user's row)
-  const int c = rank_lower_bound(r, n, hi) - rank_lower_bound(r, n, lo);
-  return ui.mode == GRAM_ITEMS_ALLOW ? c > 0 : c < hi - lo;
-}
+// (the per-user item filters -- filtered(), items_ptr(), node_alive() -- are trie_dev.h's, shared with the sampling step)
 template <bool FILT>
 __device__ __forceinline__ bool child_alive(const StepArgs& a, int b, int edge) {
   if constexpr (FILT) return node_alive(*a.ui, b, a.tr.child_node[edge]);
@@ -1188,14 +1132,6 @@ extern "C" int gram_debug_set_beam_chunked(int mode) {
 extern "C" int gram_debug_set_beam_chunk_capacity(int candidates) {
   if (candidates < 0) return GRAM_E_ARG;
   g_beam_chunk_cap = candidates;
-  return 0;
-}
-
-// the per-user lists of the *_items entry points (gram_user_items_t): every array present, stride and mode in range
-static int check_items(const gram_user_items_t* it) {
-  if (!it || !it->leaf_lo || !it->leaf_hi || !it->ranks || !it->count || it->stride < 1 || it->stride > GRAM_MAX_USER_ITEMS ||
-      (it->mode != GRAM_ITEMS_EXCLUDE && it->mode != GRAM_ITEMS_ALLOW))
-    return GRAM_E_ARG;
   return 0;
 }
 

@@ -983,6 +983,21 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
 
 }  // namespace
 
+// The end of a whole-path call: with width_host, the returned width and the device's error flag come back (the call's one stream
+// synchronise) and the flag becomes the return code.
+static int read_width_and_error(const Workspace& w, int32_t* width_host, void* stream) {
+  if (!width_host) return 0;
+  int32_t host[2] = {0, 0};
+  hipError_t e = hipMemcpyAsync(&host[0], w.width, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&host[1], w.beam.error, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  *width_host = host[0];
+  if (host[1] == 4) return GRAM_E_NONFINITE;
+  if (host[1] != 0) return GRAM_E_BEAM;
+  return 0;
+}
+
 // gram_generate_ex and gram_generate_items (items: the per-user item filters, NULL for gram_generate_ex)
 static int generate_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                          int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp,
@@ -1008,17 +1023,7 @@ static int generate_call(const gram_model_t* m, const int64_t* input_ids, const 
   }
   w.beam.length_penalty = length_penalty;
   TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, sequences, scores, stream));
-  if (width_host) {
-    int32_t host[2] = {0, 0};
-    hipError_t e = hipMemcpyAsync(&host[0], w.width, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&host[1], w.beam.error, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    *width_host = host[0];
-    if (host[1] == 4) return GRAM_E_NONFINITE;
-    if (host[1] != 0) return GRAM_E_BEAM;
-  }
-  return 0;
+  return read_width_and_error(w, width_host, stream);
 }
 
 extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
@@ -1053,6 +1058,111 @@ extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_i
     return GRAM_E_ARG;
   return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
                        workspace_bytes, sequences, scores, width_host, stream);
+}
+
+// ---- Trie-constrained sampling (gram_sample) ------------------------------------------------------------------------
+namespace {
+
+// What sampling needs beyond carve()'s layout, BEHIND `bytes` (nothing above moves): the two per-row accumulators and, for a Trie whose
+// fan-out exceeds what the sampling step holds on chip, the streamed candidates of every row.
+struct SampleScratch {
+  float *model_lp, *sample_lp;  // [B * R]
+  int64_t bytes;
+};
+SampleScratch carve_sample(Workspace& w, void* ws, int B, int R, int max_fanout) {
+  Carve cv(ws);
+  cv.off = w.bytes;
+  SampleScratch s{};
+  const int64_t rows = (int64_t)B * R;
+  s.model_lp = cv.take<float>(rows);
+  s.sample_lp = cv.take<float>(rows);
+  if (max_fanout > gram_sample_capacity()) {
+    w.beam.cand_logits_users = (int32_t)rows;
+    w.beam.cand_logits_stride = max_fanout;
+    w.beam.cand_logits = cv.take<float>(rows * max_fanout);
+  }
+  s.bytes = (cv.off + 255) & ~(int64_t)255;
+  return s;
+}
+inline bool sample_shape_ok(int B, int R, int max_fanout) {
+  return max_fanout >= 0 && (int64_t)B * R <= INT32_MAX / GRAM_MAX_DEC_LEN && (int64_t)B * R * max_fanout <= ((int64_t)1 << 40);
+}
+
+// encode -> R sampled rows per user -> finalize, next to generate_body: the same encode_call / decode_step / gram_lse_combine launches
+// with the search step replaced by the sampling step.  A user's R rows share its bank as K beams do; step 0 runs on one decoder row
+// per user; no row is ever reordered, so the ancestor table stays gram_beam_init's identity.  Finished rows keep being decoded.
+int sample_body(const gram_model* m, Workspace& w, const SampleScratch& s, const int64_t* input_ids, const uint8_t* mask, int B, int N,
+                int L, int R, int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
+                const gram_sample_params_t* prm, const float* uniforms, int64_t* sequences, float* seq_logprobs, float* sample_logprobs,
+                void* stream) {
+  const gram_model_desc_t& c = m->d;
+  const size_t rows = (size_t)B * R;
+  TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
+  TRY(gram_beam_init(&w.beam, trie, /*decoder_start_token_id=*/0, stream));
+  // the rows' "finished" lengths live in the unused hypothesis heap (gram_hip.h); they and the accumulators start at zero
+  hipError_t e = hipMemsetAsync(w.beam.hyp_len, 0, rows * sizeof(int32_t), (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s.model_lp, 0, rows * sizeof(float), (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s.sample_lp, 0, rows * sizeof(float), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  for (int t = 0; t + 1 < max_length; ++t) {
+    const int Kt = t == 0 ? 1 : R;
+    TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, Kt, B * R, max_length, t, nullptr, w.lse_part, nullptr, stream));
+    TRY(gram_lse_combine(w.lse_part, w.lse, B * Kt, c.vocab / 64, stream));
+    const void* const lm16 = w.pieces > 1 ? nullptr : c.lm_head_bf16;  // (the search step's operands: search_step)
+    if (items)
+      TRY(gram_sample_step_items(&w.beam, trie, w.dec.h, lm16, c.lm_head_f32, c.d_model, w.lse, c.vocab, t + 1, Kt, w.pieces, prm,
+                                 uniforms + t, max_length - 1, s.sample_lp, s.model_lp, items, stream));
+    else
+      TRY(gram_sample_step(&w.beam, trie, w.dec.h, lm16, c.lm_head_f32, c.d_model, w.lse, c.vocab, t + 1, Kt, w.pieces, prm, uniforms + t,
+                           max_length - 1, s.sample_lp, s.model_lp, stream));
+  }
+  return gram_sample_finalize(&w.beam, max_length, s.model_lp, s.sample_lp, sequences, seq_logprobs, sample_logprobs, w.width, stream);
+}
+
+int sample_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R, int max_length,
+                const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items, const gram_sample_params_t* prm,
+                const float* uniforms, void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs,
+                float* sample_logprobs, int32_t* width_host, void* stream) {
+  TRY(check_shapes(m, B, N, L, R, max_length));
+  TRY(check_compaction(comp, B, N));
+  if (!trie || !prm || !uniforms || !sequences || !seq_logprobs || !sample_logprobs || !mask || (!comp && !input_ids) ||
+      !sample_shape_ok(B, R, trie->max_fanout))
+    return GRAM_E_ARG;
+  if (!(prm->temperature > 0.f) || prm->top_k < 0 || !(prm->top_p > 0.f) || !(prm->top_p <= 1.f)) return GRAM_E_ARG;
+  Workspace w = carve(m, workspace, B, N, L, R, max_length);
+  const SampleScratch s = carve_sample(w, workspace, B, R, trie->max_fanout);
+  if (!workspace || workspace_bytes < s.bytes) return GRAM_E_WORKSPACE;
+  memset(g_tail_last, 0, sizeof(g_tail_last));  // (gram_debug_tail_last speaks of the last generate call of any kind)
+  TRY(sample_body(m, w, s, input_ids, mask, B, N, L, R, max_length, trie, comp, items, prm, uniforms, sequences, seq_logprobs,
+                  sample_logprobs, stream));
+  return read_width_and_error(w, width_host, stream);
+}
+
+}  // namespace
+
+extern "C" int64_t gram_workspace_bytes_sample(const gram_model_t* m, int B, int N, int L, int R, int max_length, int max_fanout) {
+  if (check_shapes(m, B, N, L, R, max_length) || !sample_shape_ok(B, R, max_fanout)) return GRAM_E_ARG;
+  Workspace w = carve(m, nullptr, B, N, L, R, max_length);
+  return carve_sample(w, nullptr, B, R, max_fanout).bytes;
+}
+
+extern "C" int gram_sample(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R, int max_length,
+                           const gram_trie_t* trie, const gram_compaction_t* comp, const gram_sample_params_t* params,
+                           const float* uniforms, void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs,
+                           float* sample_logprobs, int32_t* width_host, void* stream) {
+  return sample_call(m, input_ids, mask, B, N, L, R, max_length, trie, comp, nullptr, params, uniforms, workspace, workspace_bytes,
+                     sequences, seq_logprobs, sample_logprobs, width_host, stream);
+}
+
+extern "C" int gram_sample_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R,
+                                 int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
+                                 const gram_sample_params_t* params, const float* uniforms, void* workspace, int64_t workspace_bytes,
+                                 int64_t* sequences, float* seq_logprobs, float* sample_logprobs, int32_t* width_host, void* stream) {
+  if (!items || !items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
+      items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW))
+    return GRAM_E_ARG;
+  return sample_call(m, input_ids, mask, B, N, L, R, max_length, trie, comp, items, params, uniforms, workspace, workspace_bytes,
+                     sequences, seq_logprobs, sample_logprobs, width_host, stream);
 }
 
 // ---- teacher-forced decoder pass (gram_teacher_forced) -----------------------------------------------------------------------------

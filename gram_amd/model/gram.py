@@ -1201,7 +1201,8 @@ class GRAM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask, max_length, prefix_allowed_tokens_fn=None, num_beams=1,
                  num_return_sequences=None, output_scores=True, return_dict_in_generate=True, length_penalty=1.0,
-                 exclude_items=None, allowed_items=None, candidates=None, **unused):
+                 exclude_items=None, allowed_items=None, candidates=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
+                 uniforms=None, generator=None, **unused):
         """GRAM.generate (gram.py:74-107) with the kwargs single_runner_gram.py:641-651 passes.
 
         input_ids (B,N,L) int64, attention_mask (B,N,L) bool on the model's device.  Returns a
@@ -1214,13 +1215,27 @@ class GRAM(nn.Module):
         takes; required with either).  User b then gets exactly what this call returns for that user alone with
         ``prefix_allowed_tokens_fn(Trie(A_b))``, A_b its remaining candidates, bit for bit -- the search walks a per-user view of
         the one shared device Trie.  Two candidates that spell the same sequence share a Trie leaf: naming
-        either names the sequence.  At most 4096 entries per user; a user left without any item is a ``ValueError``."""
+        either names the sequence.  At most 4096 entries per user; a user left without any item is a ``ValueError``.
+
+        Sampling: ``do_sample=True`` (with ``num_beams=1``) draws ``num_return_sequences`` = R <= 64 items per user from
+        p(item | user) restricted to the Trie -- HF 4.26's ``sample``: the Trie mask, then ``temperature`` (> 0), ``top_k`` (None =
+        HF's default 50, 0 = off) and ``top_p`` (in (0, 1]) on the raw logits of the row's Trie children, then one draw (DESIGN.md
+        section 4.8).  The draw is inverse-CDF sampling from ``uniforms``, float32 (B, R, max_length - 1) in [0, 1) on any device --
+        row (b, r) takes the first kept child whose cumulative weight exceeds ``uniforms[b, r, t]`` times the total at step t --
+        or, without it, from ``torch.rand(..., generator=generator)`` on the model's device.  That is the same DISTRIBUTION as HF's
+        ``torch.multinomial``, not the same draw for a given torch seed.  Returns ``sequences`` (B*R, width) user-major,
+        ``sequences_scores=None`` (as HF's ``sample``), ``sequence_logprobs`` (B*R,) = the model's log-probability of each row (what
+        ``score_sequences`` returns for it) and ``sample_logprobs`` (B*R,) = its log-probability under the warped distribution it was
+        drawn from.  ``exclude_items`` / ``allowed_items`` work as for beam search.  A row's draw depends on its user, its uniforms and
+        the parameters only, not on the batch or on R.  Without ``do_sample`` the five sampling arguments are ignored, as before."""
         if prefix_allowed_tokens_fn is None:
             raise NotImplementedError("unconstrained generation is not on GRAM's scoring path (a Trie is always passed)")
         # HF kwargs that would change the search: refuse the ones this path does not implement instead of ignoring them
         neutral = {"do_sample": False, "early_stopping": False, "num_beam_groups": 1, "repetition_penalty": 1.0,
                    "no_repeat_ngram_size": 0, "diversity_penalty": 0.0, "use_cache": True, "temperature": 1.0, "top_k": 50,
                    "top_p": 1.0, "min_length": 0, "pad_token_id": 0, "eos_token_id": 1, "decoder_start_token_id": 0}
+        if not do_sample:  # (greedy and beam search ignore the sampling arguments, by name as they always did)
+            unused = dict(unused, **{k: v for k, v in (("uniforms", uniforms), ("generator", generator)) if v is not None})
         for k, v in unused.items():
             if k in neutral:
                 if v is not None and v != neutral[k] and k not in ("temperature", "top_k", "top_p"):
@@ -1231,6 +1246,9 @@ class GRAM(nn.Module):
                 warnings.warn(f"gram_amd.GRAM.generate ignores the keyword argument {k!r}")
         if input_ids.dim() != 3:
             raise ValueError("input_ids must be (B, N, L)")
+        if do_sample:  # (every refusal of the sampling path, before anything touches the device)
+            sampling = self._sample_args(input_ids.shape[0], int(max_length), num_beams, num_return_sequences, temperature, top_k, top_p,
+                                         uniforms, prefix_allowed_tokens_fn)
         self._check_passage_len(input_ids.shape[-1])
         self._check_fused_len(input_ids.shape[1], input_ids.shape[2])
         handle = self._pack()
@@ -1265,6 +1283,33 @@ class GRAM(nn.Module):
             items = self._user_item_lists(allowed_items if allow else exclude_items, allow, B, flat, candidates, dev)
         comp, harvest_plan = self._plan(ids, mask, B, N, Lp)
         _ctrie, (t_off, t_tok, t_node) = flat.to_device(dev)
+        if do_sample:
+            # HF's sample on the Trie: ONE custom op over the C ABI (gram_amd/ops.py -> gram_sample / gram_sample_items)
+            R, tau, k_top, p_top = sampling
+            need = int(lib.gram_workspace_bytes_sample(handle, B, N, Lp, R, int(max_length), int(flat.max_fanout)))
+            if need < 0:
+                raise _lib.GramHipError(f"unsupported problem size B={B} N={N} L={Lp} num_return_sequences={R} max_length={max_length}")
+            ws = self._ensure_workspace(need)
+            if uniforms is None:
+                shape = (B, R, int(max_length) - 1)
+                gdev = generator.device if generator is not None else dev
+                uniforms = torch.rand(shape, generator=generator, dtype=torch.float32, device=gdev)
+            uni = uniforms.detach().to(dev).contiguous()
+            from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
+            args = (ids, mask, int(handle), ws, t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len), R, int(max_length),
+                    tau, k_top, p_top, uni, *self._comp_args(comp))
+            if filtered:
+                leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
+                seqs, model_lp, sample_lp, width = torch.ops.gram.sample_items(*args, leaf_lo, leaf_hi,
+                                                                                flat.item_ranks_on(dev, candidates)[1], items, allow)
+            else:
+                seqs, model_lp, sample_lp, width = torch.ops.gram.sample(*args)
+            if harvest_plan is not None:
+                self._harvest_from_workspace(harvest_plan, ws, handle, B, N, Lp, R, int(max_length))
+            seqs = seqs[:, : int(width[0])]
+            if not return_dict_in_generate:
+                return seqs
+            return GenerateOutput(sequences=seqs, sequences_scores=None, sequence_logprobs=model_lp, sample_logprobs=sample_lp)
         # the tail pass (gram_generate_tail; taken by size, GRAM_TAIL_PASS=0 switches it off: gram_tail_pass_wanted): where the Trie has a tail inside this call's
         # steps, the workspace grows by the forest's rows (gram_workspace_bytes_tail); a device that cannot hold them decodes step by
         # step -- the same results
@@ -1294,6 +1339,33 @@ class GRAM(nn.Module):
         if not return_dict_in_generate:
             return seqs
         return GenerateOutput(sequences=seqs, sequences_scores=scores)
+
+    def _sample_args(self, B: int, max_length: int, num_beams, num_return_sequences, temperature, top_k, top_p, uniforms, fn):
+        """The arguments of ``generate(do_sample=True)`` as (R, temperature, top_k, top_p), or the refusal: everything is checked on
+        the host, before the model is packed or a tensor is moved."""
+        if int(num_beams) != 1:
+            raise NotImplementedError("generate(do_sample=True) with num_beams > 1 (HF's beam-sample) is not implemented: "
+                                      "sampling runs with num_beams=1 and num_return_sequences draws per user")
+        if self._closure_trie(fn) is None:
+            raise NotImplementedError("generate(do_sample=True) needs the Trie closure form of prefix_allowed_tokens_fn")
+        R = 1 if num_return_sequences is None else int(num_return_sequences)
+        if not 1 <= R <= _lib.GRAM_MAX_BEAMS:
+            raise ValueError(f"generate(do_sample=True): num_return_sequences must lie in [1, {_lib.GRAM_MAX_BEAMS}] (got {R})")
+        tau, p_top = float(temperature), float(top_p)
+        k_top = 50 if top_k is None else int(top_k)  # (HF's default)
+        if not (tau > 0 and tau < float("inf")):
+            raise ValueError(f"generate(do_sample=True): temperature must be a positive number (got {temperature!r})")
+        if not 0 < p_top <= 1:
+            raise ValueError(f"generate(do_sample=True): top_p must lie in (0, 1] (got {top_p!r})")
+        if k_top < 0:
+            raise ValueError(f"generate(do_sample=True): top_k must be >= 0, 0 switches it off (got {top_k!r})")
+        if uniforms is not None:
+            want = (B, R, max_length - 1)
+            if not isinstance(uniforms, torch.Tensor) or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != want:
+                got = (tuple(uniforms.shape), uniforms.dtype) if isinstance(uniforms, torch.Tensor) else type(uniforms).__name__
+                raise ValueError(f"generate(do_sample=True): uniforms must be a float32 tensor of shape {want} = (B, "
+                                 f"num_return_sequences, max_length - 1), got {got}")
+        return R, tau, k_top, p_top
 
     @staticmethod
     def _user_item_lists(lists, allow: bool, B: int, flat: FlatTrie, candidates, device="cpu") -> torch.Tensor:

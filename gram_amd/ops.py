@@ -8,6 +8,9 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
     torch.ops.gram.generate          GRAM.generate's whole path (gram_generate_ex) -- what ``GRAM.generate`` calls
     torch.ops.gram.generate_items    the same path with per-user item filters (gram_user_items_prepare + gram_generate_items) --
                                      ``GRAM.generate(exclude_items= / allowed_items=)``
+    torch.ops.gram.sample            Trie-constrained sampling, R draws per user with their log-probabilities (gram_sample) --
+                                     ``GRAM.generate(do_sample=True)``
+    torch.ops.gram.sample_items      the same with per-user item filters (gram_user_items_prepare + gram_sample_items)
     torch.ops.gram.teacher_forced    the teacher-forced decoder pass (gram_teacher_forced) -- ``GRAM.forward(labels=...)`` and
                                      ``GRAM.score_sequences``
     torch.ops.gram.teacher_forced_attn  the same pass with its cross-attention probabilities (gram_teacher_forced_ex) --
@@ -27,7 +30,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
 Every op keeps its full explicit signature (``torch.library`` derives the schema from it).  What several ops do with the same
 arguments is stated once, in the private helpers below the ``_check`` they are built on: ``_compaction`` / ``_trie`` build the
 gram_compaction_t / gram_trie_t of a call, ``_tf_inputs`` is the validation of the three teacher-forced ops, ``_search`` the
-outputs and the C call of the two ``generate`` ops, ``_enc_self_attn`` / ``_cross_attn_inputs`` the short and long attention forms.
+outputs and the C call of the two ``generate`` ops, ``_user_items`` the validated lists of the two ``*_items`` ops, ``_sample`` the
+checks, outputs and C call of the two ``sample`` ops, ``_enc_self_attn`` / ``_cross_attn_inputs`` the short and long attention forms.
 """
 from __future__ import annotations
 
@@ -143,20 +147,15 @@ def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_t
 
 
 # ---------------------------------------------------------------------------------------------- generate with per-user item filters
-@torch.library.custom_op("gram::generate_items", mutates_args=("workspace",), device_types="cuda")
-def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
-                   trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
-                   num_return_sequences: int, max_length: int, length_penalty: float, comp_map: Optional[Tensor],
-                   comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor],
-                   n_cached: int, cache_L: int, leaf_lo: Tensor, leaf_hi: Tensor, item_rank: Tensor, items: Tensor,
-                   allow: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    """``generate`` (same inputs, same outputs) with every user searching its own view of the Trie (gram_user_items_t): leaf_lo /
-    leaf_hi i32 (n_nodes,) the leaf-rank range below every node, item_rank i32 (n_items,) the leaf rank of every candidate, items
-    i32 (B, M) each user's candidate indices padded with -1, M <= 4096; ``allow``: the lists are what a user may get (else what it
-    may not).  The lists become sorted distinct ranks on the device (gram_user_items_prepare), then gram_generate_items runs."""
+def _user_items(op: str, input_ids: Tensor, attention_mask: Tensor, trie_child_off: Tensor, trie_child_tok: Tensor,
+                trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, comp_map, comp_ids, comp_mask, cache_slot, cache_x,
+                n_cached: int, cache_L: int, leaf_lo: Tensor, leaf_hi: Tensor, item_rank: Tensor, items: Tensor, allow: bool):
+    """What the two ``*_items`` ops require of their tensors, or a ``ValueError`` in ``op``'s name; then the lists as sorted distinct
+    leaf ranks on the device (gram_user_items_prepare, on input_ids' current stream).  Returns (gram_trie_t, gram_compaction_t or
+    None, gram_user_items_t, the tensors the last one points into)."""
     lib = _lib.load()
     if input_ids.dim() != 3 or items.dim() != 2:
-        raise ValueError("generate_items: input_ids must be (B, N, L) and items (B, M)")
+        raise ValueError(f"{op}: input_ids must be (B, N, L) and items (B, M)")
     B, N, L = input_ids.shape
     dev = input_ids.device
     M = items.shape[1]
@@ -168,11 +167,11 @@ def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, works
                            ("leaf_hi", leaf_hi, (n_nodes,)), ("item_rank", item_rank, (None,)), ("items", items, (B, None))):
         _check(name, t, torch.int32, shape, dev)
     if n_nodes < 1 or item_rank.numel() < 1 or not 1 <= M <= _lib.GRAM_MAX_USER_ITEMS:
-        raise ValueError(f"generate_items: need a Trie, at least one candidate and 1 <= M <= {_lib.GRAM_MAX_USER_ITEMS} (got M={M})")
+        raise ValueError(f"{op}: need a Trie, at least one candidate and 1 <= M <= {_lib.GRAM_MAX_USER_ITEMS} (got M={M})")
     # candidate indices index item_rank on the device: out-of-range ones are refused here, not read there
     lo_i, hi_i = torch.stack([items.min(), items.max()]).tolist()
     if lo_i < -1 or hi_i >= item_rank.numel():
-        raise ValueError(f"generate_items: items must lie in [0, {item_rank.numel()}) or be the padding value -1")
+        raise ValueError(f"{op}: items must lie in [0, {item_rank.numel()}) or be the padding value -1")
     trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
     comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
     ranks = torch.empty(B, M, dtype=torch.int32, device=dev)
@@ -182,7 +181,25 @@ def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, works
     with torch.cuda.device(dev):
         _lib.check(lib.gram_user_items_prepare(item_rank.data_ptr(), item_rank.numel(), items.data_ptr(), B, M, ranks.data_ptr(),
                                                count.data_ptr(), M, _stream(input_ids)), "gram_user_items_prepare")
-        return _search(lib.gram_generate_items, "gram_generate_items", input_ids, attention_mask, handle, workspace, trie, comp,
+    return trie, comp, ui, (ranks, count)
+
+
+@torch.library.custom_op("gram::generate_items", mutates_args=("workspace",), device_types="cuda")
+def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                   trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
+                   num_return_sequences: int, max_length: int, length_penalty: float, comp_map: Optional[Tensor],
+                   comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor],
+                   n_cached: int, cache_L: int, leaf_lo: Tensor, leaf_hi: Tensor, item_rank: Tensor, items: Tensor,
+                   allow: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """``generate`` (same inputs, same outputs) with every user searching its own view of the Trie (gram_user_items_t): leaf_lo /
+    leaf_hi i32 (n_nodes,) the leaf-rank range below every node, item_rank i32 (n_items,) the leaf rank of every candidate, items
+    i32 (B, M) each user's candidate indices padded with -1, M <= 4096; ``allow``: the lists are what a user may get (else what it
+    may not).  The lists become sorted distinct ranks on the device (gram_user_items_prepare), then gram_generate_items runs."""
+    trie, comp, ui, _keep = _user_items("generate_items", input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node,
+                                        trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
+                                        cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
+    with torch.cuda.device(input_ids.device):
+        return _search(_lib.load().gram_generate_items, "gram_generate_items", input_ids, attention_mask, handle, workspace, trie, comp,
                        num_beams, num_return_sequences, max_length, length_penalty, C.byref(ui))
 
 
@@ -191,6 +208,93 @@ def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_t
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
       cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
     return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
+
+
+# ---------------------------------------------------------------------------------------------- Trie-constrained sampling
+def _sample(fn, what: str, input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie: _lib.Trie,
+            comp: Optional[_lib.Compaction], num_return_sequences: int, max_length: int, temperature: float, top_k: int, top_p: float,
+            uniforms: Tensor, *extra) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The checks, the outputs and the C call ``fn`` (gram_sample, or gram_sample_items with its lists in ``extra``) of the two
+    ``sample`` ops, and their return value."""
+    if input_ids.dim() != 3:
+        raise ValueError(f"{what}: input_ids must be (B, N, L)")
+    B, N, L = input_ids.shape
+    R, dev = num_return_sequences, input_ids.device
+    if not 1 <= R <= _lib.GRAM_MAX_BEAMS or not 2 <= max_length <= _lib.GRAM_MAX_DEC_LEN:
+        raise ValueError(f"{what}: need 1 <= num_return_sequences <= {_lib.GRAM_MAX_BEAMS} and 2 <= max_length <= {_lib.GRAM_MAX_DEC_LEN}")
+    if not temperature > 0 or top_k < 0 or not 0 < top_p <= 1:
+        raise ValueError(f"{what}: need temperature > 0, top_k >= 0 and 0 < top_p <= 1")
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    _check("uniforms", uniforms, torch.float32, (B, R, max_length - 1), dev)
+    prm = _lib.SampleParams(float(temperature), int(top_k), float(top_p))
+    seqs = torch.empty(B * R, max_length, dtype=torch.int64, device=dev)
+    model_lp = torch.empty(B * R, dtype=torch.float32, device=dev)
+    sample_lp = torch.empty(B * R, dtype=torch.float32, device=dev)
+    width = C.c_int32(0)
+    with torch.cuda.device(dev):
+        rc = fn(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, R, max_length, C.byref(trie), _ref(comp), *extra,
+                C.byref(prm), uniforms.data_ptr(), workspace.data_ptr(), workspace.numel(), seqs.data_ptr(), model_lp.data_ptr(),
+                sample_lp.data_ptr(), C.byref(width), _stream(input_ids))
+    _lib.check(rc, what)
+    return seqs, model_lp, sample_lp, torch.tensor([width.value], dtype=torch.int32)
+
+
+def _sample_fake(input_ids, num_return_sequences, max_length):
+    rows = input_ids.shape[0] * num_return_sequences
+    f = dict(dtype=torch.float32)
+    return (input_ids.new_empty(rows, max_length), input_ids.new_empty(rows, **f), input_ids.new_empty(rows, **f),
+            torch.empty(1, dtype=torch.int32))
+
+
+@torch.library.custom_op("gram::sample", mutates_args=("workspace",), device_types="cuda")
+def sample(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor, trie_child_tok: Tensor,
+           trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_return_sequences: int, max_length: int,
+           temperature: float, top_k: int, top_p: float, uniforms: Tensor, comp_map: Optional[Tensor], comp_ids: Optional[Tensor],
+           comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor], n_cached: int,
+           cache_L: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """HF ``sample`` on the Trie (gram_sample): R = num_return_sequences draws per user.  input_ids / attention_mask / handle / the Trie /
+    comp_* / cache_* as ``generate``; ``workspace`` a u8 scratch tensor of gram_workspace_bytes_sample; temperature > 0, top_k >= 0 (0 =
+    off), 0 < top_p <= 1; uniforms f32 (B, R, max_length - 1) in [0, 1): row (b, r) consumes uniforms[b, r, t] at step t (inverse-CDF
+    sampling).  Returns (sequences i64 (B*R, max_length) user-major, the model's log-probability of each row f32 (B*R), its
+    log-probability under the warped distribution it was drawn from f32 (B*R), width i32 (1,))."""
+    for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),))):
+        _check(name, t, torch.int32, shape, input_ids.device)
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
+    return _sample(_lib.load().gram_sample, "gram_sample", input_ids, attention_mask, handle, workspace, trie, comp, num_return_sequences,
+                   max_length, temperature, top_k, top_p, uniforms)
+
+
+@sample.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len,
+      num_return_sequences, max_length, temperature, top_k, top_p, uniforms, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
+      cache_L):
+    return _sample_fake(input_ids, num_return_sequences, max_length)
+
+
+@torch.library.custom_op("gram::sample_items", mutates_args=("workspace",), device_types="cuda")
+def sample_items(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                 trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int,
+                 num_return_sequences: int, max_length: int, temperature: float, top_k: int, top_p: float, uniforms: Tensor,
+                 comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor],
+                 cache_x: Optional[Tensor], n_cached: int, cache_L: int, leaf_lo: Tensor, leaf_hi: Tensor, item_rank: Tensor,
+                 items: Tensor, allow: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``sample`` (same inputs, same outputs) with every user drawing from its own view of the Trie: the lists of ``generate_items``
+    (leaf_lo / leaf_hi / item_rank / items / allow), prepared the same way, then gram_sample_items."""
+    trie, comp, ui, _keep = _user_items("sample_items", input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node,
+                                        trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
+                                        cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
+    return _sample(_lib.load().gram_sample_items, "gram_sample_items", input_ids, attention_mask, handle, workspace, trie, comp,
+                   num_return_sequences, max_length, temperature, top_k, top_p, uniforms, C.byref(ui))
+
+
+@sample_items.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len,
+      num_return_sequences, max_length, temperature, top_k, top_p, uniforms, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
+      cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
+    return _sample_fake(input_ids, num_return_sequences, max_length)
 
 
 # ---------------------------------------------------------------------------------------------- teacher-forced pass
@@ -573,4 +677,6 @@ def _(logits, tokens, node, beam_scores, seq, anc, done, n_hyps, hyp_score, wors
     return logits.new_empty(logits.shape[0])
 
 
+# (``sample`` / ``sample_items`` are reached as torch.ops.gram.* like the rest; their schemas are pinned by tests/test_sample_host.py, the
+# twelve names below by tests/test_ops_host.py, which counts them)
 __all__ = ["generate", "generate_items", "teacher_forced", "teacher_forced_attn", "teacher_forced_scores", "score_trie", "linear", "enc_self_attn", "enc_self_attn_long", "cross_attn_decode", "cross_attn_long", "trie_step"]

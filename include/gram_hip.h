@@ -602,6 +602,74 @@ int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const u
                         const gram_user_items_t* items_host, void* workspace, int64_t workspace_bytes, int64_t* sequences,
                         float* scores, int32_t* width_host, void* stream);
 
+/* ---- Trie-constrained sampling: HF 4.26 `sample` restated for a Trie ------------------------------------------------
+ * The state is a gram_beam_state_t with K = R samples per user; nothing is ever reordered, so anc keeps the identity gram_beam_init
+ * wrote (except slot 0 at the compact step 0, below).  Sampling leaves the hypothesis heap unused and keeps its per-row "finished"
+ * there: hyp_len[row] (row < B * R) = the length at which the row drew EOS, 0 = still running; the caller zeroes hyp_len[0, B * R)
+ * before the first step.  done / n_hyps / beam_scores are not touched.
+ * One step, for every row at Trie node n with children c_0 < ... < c_{F-1} in token order (with the lists: the alive ones only):
+ *   z_i = hidden[row] . lm_head[c_i] (fp32; the search step's sparse logit: the same function, the same bits), y_i = z_i / temperature;
+ *   top_k (0 = off): k' = min(max(top_k, 1), F), child i is kept iff y_i >= the k'-th largest y (ties at the threshold all stay);
+ *   top_p (< 1; over what top_k kept): w_i = exp(y_i - y_max), child i stays iff sum_{j kept, y_j <= y_i} w_j > (1 - top_p) * sum_kept w
+ *     (the maximum always stays; equal y stay or go together);
+ *   draw: W = sum of the kept w, the row takes the first kept child in token order whose running sum exceeds u * W (none, by rounding:
+ *     the last kept child) -- inverse-CDF sampling;
+ *   sample_logprob[row] += (y_i - y_max) - log W;  model_logprob[row] += z_i - lse[row].
+ * A row that draws EOS is finished: from then on it emits pad, its node is -1 and its accumulators do not move.  Every sum is fp32 in
+ * an order fixed by the row's own (alive) children, so a row's draw depends on its node, its hidden row, its u and the parameters
+ * only -- not on B, R or the other rows.  A row without any child is error 1 (GRAM_E_BEAM), non-finite logits / lse error 4. */
+struct gram_sample_params {
+  float temperature; /* > 0                                   */
+  int32_t top_k;     /* >= 0; 0 = off                          */
+  float top_p;       /* in (0, 1]; 1 = off                     */
+};
+typedef struct gram_sample_params gram_sample_params_t; /* (layout against its ctypes mirror: tests/test_sample_host.py) */
+
+/* One sampling step (cur_len = tokens already in each row).  hidden / lm_head_bf16 / lm_head_f32 / d / pieces as in
+ * gram_beam_step_sparse (pieces == 1: lm_head_bf16) and gram_beam_step_sparse_split (pieces == 2, or lm_head_bf16 NULL: lm_head_f32).
+ * rows_per_user = R normally; 1 at the compact step 0 (hidden and lse hold one row per user), which also sets anc[0][row] = user.
+ * u: row r's uniform in [0, 1) at u[r * u_stride].  Writes tokens, node, seq[row][cur_len], hyp_len and the two accumulators
+ * (f32 [B * R] each).  A row's candidates are held on chip up to 8 192 of them (32 KB of LDS: four workgroups per CU); a Trie with
+ * max_fanout above that streams them through st->cand_logits, which must then hold f32 [B * R][cand_logits_stride >= max_fanout]
+ * (cand_logits_users >= B * R; GRAM_E_ARG otherwise) -- the same results bit for bit. */
+int gram_sample_step(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16, const void* lm_head_bf16,
+                     const float* lm_head_f32, int d, const float* lse, int V, int cur_len, int rows_per_user, int pieces,
+                     const gram_sample_params_t* params_host, const float* u, int u_stride, float* sample_logprob,
+                     float* model_logprob, void* stream);
+/* gram_sample_step with per-user item filters: a row's children are those alive for its user (gram_user_items_t). */
+int gram_sample_step_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
+                           const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                           int rows_per_user, int pieces, const gram_sample_params_t* params_host, const float* u, int u_stride,
+                           float* sample_logprob, float* model_logprob, const gram_user_items_t* items_host, void* stream);
+/* sequences i64 [B * R][max_length] (pad behind a finished row), the two accumulators copied to seq_logprobs / sample_logprobs
+ * f32 [B * R] (a non-finite one is error 4), *out_width (device) = 1 + the longest row capped at max_length, as gram_greedy_finalize. */
+int gram_sample_finalize(const gram_beam_state_t* st_host, int max_length, const float* model_logprob, const float* sample_logprob,
+                         int64_t* sequences, float* seq_logprobs, float* sample_logprobs, int32_t* out_width, void* stream);
+/* Candidates of a row the sampling step holds on chip (8 192, or what gram_debug_set_sample_capacity lowered it to). */
+int gram_sample_capacity(void);
+/* TEST hook: lowers that capacity (0 = the default), so that the streamed form is reachable at small fan-outs.  Results do not
+ * depend on it.  Process-wide. */
+int gram_debug_set_sample_capacity(int candidates);
+
+/* Bytes of scratch gram_sample needs: gram_workspace_bytes(m, B, N, L, R, max_length) -- the layout is unchanged -- plus, behind it,
+ * the two accumulators and, where max_fanout exceeds gram_sample_capacity(), the streamed candidates [B * R][max_fanout]. */
+int64_t gram_workspace_bytes_sample(const gram_model_t* m, int B, int N, int L, int R, int max_length, int max_fanout);
+
+/* generate(do_sample=True, num_beams=1, num_return_sequences=R): encoder -> late fusion -> bank (shared by a user's R samples as by
+ * K beams) -> max_length - 1 steps of decoder + gram_sample_step (step 0 on one decoder row per user) -> gram_sample_finalize.
+ * uniforms f32 [B][R][max_length - 1] (device): row (b, r) consumes uniforms[b][r][t] at step t.  sequences i64 [B * R][max_length],
+ * seq_logprobs (the model's full-vocabulary log-probability of each row, what gram_teacher_forced sums) and sample_logprobs (under the
+ * distribution drawn from) f32 [B * R]; width_host as in gram_generate.  Finished rows keep being decoded. */
+int gram_sample(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R, int max_length,
+                const gram_trie_t* trie_host, const gram_compaction_t* compaction_host, const gram_sample_params_t* params_host,
+                const float* uniforms, void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs,
+                float* sample_logprobs, int32_t* width_host, void* stream);
+/* gram_sample with per-user item filters (as gram_generate_items). */
+int gram_sample_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R, int max_length,
+                      const gram_trie_t* trie_host, const gram_compaction_t* compaction_host, const gram_user_items_t* items_host,
+                      const gram_sample_params_t* params_host, const float* uniforms, void* workspace, int64_t workspace_bytes,
+                      int64_t* sequences, float* seq_logprobs, float* sample_logprobs, int32_t* width_host, void* stream);
+
 /* ---- the tail pass: the chain-like lower levels of the Trie decoded in one pass per user forest ---------------------
  * Once a user's beams stand on prefixes of length d_tail (start token counted), every decoder state the remaining search steps can
  * ask for belongs to a known forest: the beams' nodes and their descendants that have children.  gram_generate_tail builds that

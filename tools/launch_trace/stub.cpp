@@ -54,6 +54,7 @@ void put(const gram_user_items_t* u) { fields(u->leaf_lo, u->leaf_hi, u->ranks, 
 void put(const gram_trie_rows_t* r) {
   fields(r->tokens, r->pos, r->anc, r->row_node, r->node_row, r->node_tok, r->node_leaf, r->Q, r->Tq, r->n_nodes, r->n_leaves);
 }
+void put(const gram_sample_params_t* p) { fields(p->temperature, p->top_k, p->top_p); }
 void put(const gram_live_rows_t* l) { fields(l->rows, l->rowpos, l->users, l->tokens, l->counts); }
 void put(const gram_trie_tail_t* t) { fields(t->sub_rows, t->d_tail, t->steps); }
 void put(const gram_forest_t* f) {
@@ -214,6 +215,21 @@ int gram_greedy_finalize(const gram_beam_state_t* s, int max_length, int64_t* se
 }
 int gram_beam_finalize(const gram_beam_state_t* s, int nret, int max_length, int64_t* sequences, float* scores, int32_t* width, void* st) {
   REC(s, nret, max_length, sequences, scores, width, st);
+}
+int gram_sample_capacity(void) { return 8192; }  // the product default (a query, not a launch -- nothing recorded)
+int gram_sample_step(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, const float* lm32, int d,
+                     const float* lse, int V, int cur_len, int rows_per_user, int pieces, const gram_sample_params_t* prm, const float* u,
+                     int u_stride, float* sample_lp, float* model_lp, void* st) {
+  REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, pieces, prm, u, u_stride, sample_lp, model_lp, st);
+}
+int gram_sample_step_items(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, const float* lm32, int d,
+                           const float* lse, int V, int cur_len, int rows_per_user, int pieces, const gram_sample_params_t* prm,
+                           const float* u, int u_stride, float* sample_lp, float* model_lp, const gram_user_items_t* items, void* st) {
+  REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, pieces, prm, u, u_stride, sample_lp, model_lp, items, st);
+}
+int gram_sample_finalize(const gram_beam_state_t* s, int max_length, const float* model_lp, const float* sample_lp, int64_t* sequences,
+                         float* seq_logprobs, float* sample_logprobs, int32_t* width, void* st) {
+  REC(s, max_length, model_lp, sample_lp, sequences, seq_logprobs, sample_logprobs, width, st);
 }
 int gram_live_rows(const gram_beam_state_t* s, const gram_trie_t* trie, const gram_live_rows_t* out, void* st) {
   // the scripted counts of this call: {live rows, users owning one}, two entries of g_live_script per call
