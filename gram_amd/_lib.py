@@ -269,6 +269,9 @@ SIGNATURES = {
     "gram_scatter_rows": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "gram_cross_attn_entries_split": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, i64, i64, vp,
                                                 vp]),
+    "gram_dec_self_attn_forest_split": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, i64, i64, vp]),
+    "gram_debug_set_tail_forest_attn": (C.c_int, [C.c_int]),
     "gram_workspace_bytes_tail": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gram_generate_tail": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
                                      C.POINTER(Compaction), C.POINTER(TrieTail), vp, i64, vp, vp, C.POINTER(i32), vp]),

@@ -555,6 +555,21 @@ int search_step(const gram_model* m, const Workspace& w, const gram_trie_t* trie
   return gram_beam_step_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.d_model, w.lse, c.vocab, cur_len, rows_per_user, st);
 }
 
+// Which self-attention the tail pass runs (gram_debug_set_tail_forest_attn).  The forest kernel is one launch per layer where the
+// step-wise kernel is two per user group and level; it is taken by default from kForestAttnMinRows forest rows on, which -- like
+// kTailMinBankBytes below -- is no performance crossover: the launch-train goldens and the suite's small calls with the pass forced
+// on pin the level-by-level train (their forests hold up to a few thousand rows), the calls of 2049 users and the bench (330 010
+// rows) lie above it.
+int g_tail_forest_attn = -1;  // -1: the GRAM_TAIL_FOREST_ATTN environment variable decides, then the size
+constexpr int kForestAttnMinRows = 16384;
+bool tail_forest_attn_wanted(int n_rows) {
+  if (g_tail_forest_attn >= 0) return g_tail_forest_attn != 0;  // (forced either way)
+  const char* e = getenv("GRAM_TAIL_FOREST_ATTN");
+  if (e && e[0] == '0') return false;
+  if (e && e[0] == '1') return true;
+  return n_rows >= kForestAttnMinRows;
+}
+
 // The tail pass (gram_generate_tail): decode_step's layers ONCE over the n_rows rows of the forest in w.forest -- embedding by row
 // token, layer 0's q|k|v from the token table as decode_step reads it, the forest self-attention over cache and in-pass ancestors,
 // the cross-attention per entry of <= 64 rows -- then the lm_head with its LSE partials.  `w` is the call's workspace with w.dec /
@@ -573,16 +588,27 @@ int tail_pass(const gram_model* m, const Workspace& w, const uint8_t* mask, int 
   for (int g = 0; g < 2; ++g)
     for (int l = 0; l < f.n_levels; ++l)
       if (lvl_n[g * GRAM_TAIL_MAX_STEPS + l] > 0 && t0 + l >= Tmax - 1) cut = 1, nlev = l < nlev ? l : nlev;
+  const bool forest_attn = tail_forest_attn_wanted(n_rows);
   TRY(decoder_layers(
       m, w, f.tokens, n_rows, table != nullptr,
       [&](int i) {
-        // The step-wise kernel, level by level: the level's rows gathered by slot (qkv_rows), their k and v written to the cache rows
-        // of that position (no step reads them any more), the result -- compact, in the cross-attention's query buffer, free until its
-        // GEMM -- put back by row.
         if (cut) {
           hipError_t e = hipMemsetAsync(r.attn, 0, (size_t)n_rows * inner * w.pieces * sizeof(p16), (hipStream_t)st);
           if (e != hipSuccess) return (int)e;
         }
+        // The forest kernel: every row in one launch, its in-pass ancestors read from their own q|k|v rows, the result written by row.
+        if (forest_attn) {
+          if (i == 0 && table)
+            return gram_dec_self_attn_forest_split(table, f.tokens, w.kcache, w.vcache, w.beam.anc, f.pos, f.parent, f.root, c.dec_bias_f32,
+                                                   r.attn, n_rows, R, H, t0, Tmax, nlev, w.pieces, (int64_t)c.vocab * 3 * inner, w.ps_cache,
+                                                   st);
+          return gram_dec_self_attn_forest_split(r.qkv, nullptr, w.kcache + i * cache_layer, w.vcache + i * cache_layer, w.beam.anc, f.pos,
+                                                 f.parent, f.root, c.dec_bias_f32, r.attn, n_rows, R, H, t0, Tmax, nlev, w.pieces, r.ps_qkv,
+                                                 w.ps_cache, st);
+        }
+        // The step-wise kernel, level by level: the level's rows gathered by slot (qkv_rows), their k and v written to the cache rows
+        // of that position (no step reads them any more), the result -- compact, in the cross-attention's query buffer, free until its
+        // GEMM -- put back by row.
         // (two groups of users, one after the other: the second reuses the first's cache rows, which nothing reads any more)
         for (int g = 0; g < 2; ++g)
           for (int l = 0; l < nlev; ++l) {
@@ -641,6 +667,10 @@ bool tail_wanted(const gram_model* m, int B, int N, int L) {
 
 extern "C" int gram_debug_set_tail_pass(int on) {
   g_tail_pass = on;
+  return 0;
+}
+extern "C" int gram_debug_set_tail_forest_attn(int on) {
+  g_tail_forest_attn = on;
   return 0;
 }
 extern "C" int gram_tail_pass_wanted(const gram_model_t* m, int B, int N, int L) {

@@ -677,7 +677,8 @@ int gram_sample_items(const gram_model_t* m, const int64_t* input_ids, const uin
  * cross-attention reads a user's bank once per 64 forest rows instead of once per step -- and replays the remaining search steps on
  * the stored hidden states (gram_tail_rowpos maps each beam to its forest row; no decoder launch in between).  Sequences, scores
  * and the beam state after every step are gram_generate_ex's bit for bit: every kernel of the pass is row-independent, the
- * self-attention IS the step-wise kernel (level by level) and the cross-attention is the step-wise kernel's template. */
+ * self-attention is the step-wise kernel (level by level) or the forest kernel, which calls the same row arithmetic
+ * (gram_dec_self_attn_forest_split), and the cross-attention is the step-wise kernel's template. */
 #define GRAM_TAIL_MAX_STEPS 16  /* decode steps one pass replaces at most (a forest row walks that many parents at most) */
 #define GRAM_TAIL_ENTRY_ROWS 64 /* forest rows of one cross-attention entry: the four 16-row tiles of the entry kernel        */
 typedef struct {
@@ -702,7 +703,8 @@ typedef struct {
   int32_t* rowpos;    /* [B * K]     forest row of each beam in the coming search step, -1 = the beam is not live    */
   int32_t* counts;    /* [4 + 2 * GRAM_TAIL_MAX_STEPS]  rows, entries, most rows of one user, 0, then the rows of every level of
                          the even users [GRAM_TAIL_MAX_STEPS] and of the odd users [GRAM_TAIL_MAX_STEPS]                 */
-  /* The self-attention of the pass is the step-wise kernel, run level by level: level l (position t + l) takes its rows gathered
+  /* Small forests (gram_debug_set_tail_forest_attn; large ones read pos / parent / root above, gram_dec_self_attn_forest_split):
+   * the self-attention of the pass is the step-wise kernel, run level by level: level l (position t + l) takes its rows gathered
    * by SLOT -- a row's index among the rows of its level, which is also the cache row the kernel writes its k and v to -- and an
    * ancestor table of its own: column s holds, for positions < t, what the beam's column of gram_beam_state_t.anc holds, and from
    * t on the slots of the row's ancestors in the forest.  A level of the forest may hold more rows than the cache has per position
@@ -734,6 +736,18 @@ int gram_tail_rowpos(const gram_beam_state_t* st_host, const gram_trie_t* trie_h
  * tail pass runs its self-attention level by level with the step-wise kernel, on the level's rows gathered by slot, and puts the
  * results back with this. */
 int gram_scatter_rows(const void* src, const int32_t* rows, void* dst, int n, int row_bytes, int dst_rows, void* stream);
+/* The self-attention of the tail pass in one launch over all n_rows forest rows (forest_attn.hip): row i at position p = pos[i],
+ * t0 <= p < min(t0 + nlev, Tmax), attends in position order the cache rows (j, anc[j * R + root[i]]) of the positions j < t0
+ * (anc: gram_beam_state_t.anc; root clamped to [0, R)), then the k and v columns of the q|k|v rows of its ancestors at the positions
+ * t0 .. p - 1 -- parent[] walked from i, every index clamped to [0, n_rows) -- then its own, and writes row i of out.  qkv and
+ * qkv_rows as gram_dec_self_attn_rows_split's: the pass's q|k|v buffer [n_rows][3 * inner] (qkv_rows NULL), or a per-token table
+ * and the forest's tokens.  A row at any other position is left alone, rows >= n_rows too, and the cache is only read.  A row's bits
+ * are those of the level-by-level train of gram_dec_self_attn_rows_split + gram_scatter_rows over gram_tail_forest's tables: both
+ * kernels call the one row arithmetic of self_attn_row.h on the same pieces in the same order. */
+int gram_dec_self_attn_forest_split(const void* qkv, const int32_t* qkv_rows, const void* kcache, const void* vcache, const int32_t* anc,
+                                    const int32_t* pos, const int32_t* parent, const int32_t* root, const float* bias, void* out,
+                                    int n_rows, int R, int H, int t0, int Tmax, int nlev, int pieces, int64_t qkv_pstride,
+                                    int64_t cache_pstride, void* stream);
 /* gram_cross_attn_decode_split's live-row form over entries: workgroup row e serves user ent_users[e] and the up to 64 rows
  * ent_rows[e * 64 ..] of q / out (-1: none).  K is the beam count of the search whose bits are restated (it selects the one- or
  * two-wave split of the keys, as gram_cross_attn_decode_split does): a row gets the bits that call gives it. */
@@ -1000,6 +1014,12 @@ int gram_debug_set_token_tables(int on);
  * small calls on the step-wise train because the suite pins that train there.
  * Results are bit-identical either way.  Process-wide. */
 int gram_debug_set_tail_pass(int on);
+/* A/B hook: which self-attention the tail pass runs.  0 = the step-wise kernel level by level (gram_dec_self_attn_rows_split +
+ * gram_scatter_rows per user group and level), 1 = gram_dec_self_attn_forest_split, one launch per layer, -1 (default) = what the
+ * GRAM_TAIL_FOREST_ATTN environment variable says (0 / 1), and without it by size: the forest kernel for forests of at least
+ * 16 384 rows.  Not a performance crossover: the suite pins the launch train of small calls.  Results are
+ * bit-identical either way.  Process-wide. */
+int gram_debug_set_tail_forest_attn(int on);
 /* 1 if gram_generate_tail would take the tail pass for a call of this shape on a Trie with a tail (the switch and the size rule
  * above), 0 if not: what a caller sizes its workspace by.  < 0: GRAM_E_ARG. */
 int gram_tail_pass_wanted(const gram_model_t* m, int B, int N, int L);

@@ -38,6 +38,7 @@ struct Case {
   int max_L;                  // != 0: gram_model_set_max_passage_len first (a long-mode handle: the tiled encoder attention at every L)
   int max_S;                  // != 0: gram_model_set_max_fused_len first (the long cross-attention at every S; the model takes 40 passages)
   int tail_rows;              // != 0: gram_generate_tail with d_tail = 2 and two steps left; gram_tail_forest reports this many rows
+  int forest_attn;            // 1: gram_debug_set_tail_forest_attn(1) first (0: the default -- forests this small keep the level train)
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -105,6 +106,12 @@ const Case kCases[] = {
     // plus, per layer, the head-summed token scores; the passage scores behind the last layer
     {"tf_scores_fused_96", TEACHER_FORCED, 2, 1, 2, 3, 32, 3, 4, OFF, false, false, false, false, 3, false, 0, 16384},
     {"tf_scores_fused_4704", TEACHER_FORCED, 2, 1, 2, 21, 224, 3, 4, OFF, false, false, false, false, 3, false, 256, 16384},
+    // the forest self-attention forced on: the trains of generate_tail_p2_tables / generate_tail_p1 with ONE self-attention launch per
+    // layer over the 11 rows in place of the launches per group and level and their scatters (the forest's tables stay what they
+    // were); then max_length = 3, which ends inside the tail: the rows of level 1 are left to the memset in front of the launch
+    {"generate_tail_forest_p2_tables", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, true, 0, false, 0, 0, 11, 1},
+    {"generate_tail_forest_p1", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 11, 1},
+    {"generate_tail_forest_cut", GENERATE, 2, 1, 2, 3, 32, 4, 3, SOME, false, false, false, false, 0, false, 0, 0, 11, 1},
 };
 
 gram_model_t* make_model(int pieces, int fold, int max_passages) {
@@ -171,6 +178,7 @@ int run(const Case& c) {
     g_tail_script.resize(4 + GRAM_TAIL_MAX_STEPS, 0);
     g_tail_script.push_back(3);
     gram_debug_set_tail_pass(1);  // (whatever GRAM_TAIL_PASS says in the caller's environment)
+    if (c.forest_attn) gram_debug_set_tail_forest_attn(1);
     g_ws_bytes = gram_workspace_bytes_tail(m, B, N, L, K, T, tail.steps);
     trace_line("gram_workspace_bytes_tail", g_ws_bytes);
   }

@@ -251,6 +251,11 @@ int gram_tail_rowpos(const gram_beam_state_t* s, const gram_trie_t* trie, const 
 int gram_scatter_rows(const void* src, const int32_t* rows, void* dst, int n, int row_bytes, int dst_rows, void* st) {
   REC(src, rows, dst, n, row_bytes, dst_rows, st);
 }
+int gram_dec_self_attn_forest_split(const void* qkv, const int32_t* qkv_rows, const void* kcache, const void* vcache, const int32_t* anc,
+                                    const int32_t* pos, const int32_t* parent, const int32_t* root, const float* bias, void* out, int n_rows,
+                                    int R, int H, int t0, int Tmax, int nlev, int pieces, int64_t qkv_ps, int64_t cache_ps, void* st) {
+  REC(qkv, qkv_rows, kcache, vcache, anc, pos, parent, root, bias, out, n_rows, R, H, t0, Tmax, nlev, pieces, qkv_ps, cache_ps, st);
+}
 int gram_cross_attn_entries_split(const void* q, const void* k, const void* vt, const uint8_t* mask, void* out, int n_entries, int K, int H,
                                   int S, const int32_t* ent_users, const int32_t* ent_rows, int pieces, int64_t q_ps, int64_t bank_ps,
                                   const uint32_t* key_bits, void* st) {
