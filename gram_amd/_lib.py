@@ -281,6 +281,13 @@ SIGNATURES = {
     "gram_debug_set_tail_level_capacity": (C.c_int, [C.c_int]),
     "gram_debug_tail_last": (C.c_int, [C.POINTER(i32)]),
     "gram_debug_workspace_beam_state": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BeamState)]),
+    # group (diverse) beam search
+    "gram_beam_init_groups": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), C.c_int, C.c_int, vp]),
+    "gram_beam_step_groups": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
+    "gram_beam_step_groups_sparse": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                               vp, C.c_int, C.c_int, f32, C.POINTER(UserItems), vp]),
+    "gram_generate_groups": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
+                                       C.POINTER(Compaction), C.c_int, f32, C.POINTER(UserItems), vp, i64, vp, vp, C.POINTER(i32), vp]),
     # Trie-constrained sampling
     "gram_sample_step": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(SampleParams), vp, C.c_int, vp, vp, vp]),

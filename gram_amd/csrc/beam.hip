@@ -72,7 +72,8 @@ __device__ void hyp_add(const gram_beam_state_t& st, int b, const int32_t* toks,
   }
 }
 
-__global__ void beam_init_kernel(gram_beam_state_t st, gram_trie_t tr, int start) {
+// gs: beams per group (K for the plain search: one group).  The first beam of every group starts at 0, the others at -1e9
+__global__ void beam_init_kernel(gram_beam_state_t st, gram_trie_t tr, int start, int gs) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   const int R = st.B * st.K;
   if (r == 0) st.error[0] = 0;
@@ -83,7 +84,7 @@ __global__ void beam_init_kernel(gram_beam_state_t st, gram_trie_t tr, int start
   }
   if (r >= R) return;
   st.tokens[r] = start;
-  st.beam_scores[r] = (r % st.K) == 0 ? 0.f : -1e9f;
+  st.beam_scores[r] = ((r % st.K) % gs) == 0 ? 0.f : -1e9f;
   for (int p = 0; p < st.Tmax; ++p) {
     st.seq[(size_t)r * st.Tmax + p] = p == 0 ? start : 0;
     st.anc[(size_t)p * R + r] = r;
@@ -112,6 +113,7 @@ struct StepArgs {
   const float* __restrict__ pre;
   int pre_stride;
   const gram_user_items_t* ui;  // per-user item filter (the FILT instantiations only; nullptr otherwise)
+  float lam = 0.f;              // diversity penalty (the group step only)
 };
 
 // (the per-user item filters -- filtered(), items_ptr(), node_alive() -- are trie_dev.h's, shared with the sampling step)
@@ -133,6 +135,15 @@ struct StepShared {
 
 __device__ __forceinline__ unsigned long long cand_key(float sc, int k, int V, int tok) {
   return ((unsigned long long)f2ord(sc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(k * V + tok));
+}
+
+// The Hamming diversity term of a group step: lp = logit - lse of a candidate with token tok, sel_tok[0, nprev) the
+// tokens the earlier groups of this user chose in this step.  fp32, one rounding per operation (no contraction into an FMA): the
+// bits of HF's `scores -= diversity_penalty * bincount`; nothing is subtracted where that would subtract 0.
+__device__ __forceinline__ float diversity(const StepArgs& a, const StepShared& sh, int nprev, int tok, float lp) {
+  int c = 0;
+  for (int i = 0; i < nprev; ++i) c += sh.sel_tok[i] == tok ? 1 : 0;
+  return (a.lam == 0.f || c == 0) ? lp : __fsub_rn(lp, __fmul_rn(a.lam, (float)c));
 }
 
 // per beam: first child edge, child count, hidden-state row; then the prefix sums of the counts: candidate ci of the user is child
@@ -179,9 +190,10 @@ __device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, in
 // K keys of each.  The caller puts a barrier behind it.
 // FILT: a candidate whose child node is not alive for the user gets the zero key ("nothing", below every real key) and no dot product;
 // the shared step-0 row computes every child's logit and leaves the test to shared0_keys.
-template <int NTHR, bool FILT>
+// GRP (the group step): the diversity term over the nprev tokens chosen so far goes between the log-probability and the beam score.
+template <int NTHR, bool FILT, bool GRP = false>
 __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, float* s_log, int b, int tid,
-                                              int c0, int n, bool shared0) {
+                                              int c0, int n, bool shared0, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
   const gram_trie_t& tr = a.tr;
   const int row0 = b * st.K, V = a.V;
@@ -231,7 +243,9 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
         if (shared0) {
           s_log[i2[w]] = acc2[w];
         } else {
-          const float sc = (acc2[w] - a.lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
+          float sc;
+          if constexpr (GRP) sc = diversity(a, sh, nprev, tok2[w], acc2[w] - a.lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
+          else sc = (acc2[w] - a.lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
           kw[i2[w]] = dead2[w] ? 0ull : cand_key(sc, k2[w], V, tok2[w]);
         }
       }
@@ -242,9 +256,9 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
 // step 0's shared row: the keys of beams [k0, k0 + kg) x children [j0, j0 + nj) of the shared node, from the nj logits that
 // sparse_window left in s_log: kw[(k - k0) * nj + (j - j0)].  (k0 = j0 = 0, kg = K, nj = the node's fan-out: the user's whole list
 // in its flat-index order)
-template <int NTHR, bool FILT>
+template <int NTHR, bool FILT, bool GRP = false>
 __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared& sh, unsigned long long* kw, const float* s_log, int b,
-                                             int tid, int j0, int nj, int k0, int kg) {
+                                             int tid, int j0, int nj, int k0, int kg, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
   const gram_trie_t& tr = a.tr;
   const int row0 = b * st.K;
@@ -254,15 +268,17 @@ __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared
     const int kk = i / nj, jj = i - kk * nj;
     const int k = k0 + kk;
     const int tok = tr.child_tok[off0 + j0 + jj];
-    const float sc = (s_log[jj] - a.lse[b]) + st.beam_scores[row0 + k];
+    float sc;
+    if constexpr (GRP) sc = diversity(a, sh, nprev, tok, s_log[jj] - a.lse[b]) + st.beam_scores[row0 + k];
+    else sc = (s_log[jj] - a.lse[b]) + st.beam_scores[row0 + k];
     kw[i] = child_alive<FILT>(a, b, off0 + j0 + jj) ? cand_key(sc, k, a.V, tok) : 0ull;
   }
 }
 
 // DENSE mode, gather: log_softmax at the allowed tokens + running beam score.  Candidates [c0, c0 + n) -> kw[0, n); kw[n, npad) = 0
-template <int NTHR, bool FILT>
+template <int NTHR, bool FILT, bool GRP = false>
 __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, int b, int tid, int c0, int n,
-                                             int npad) {
+                                             int npad, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
   const gram_trie_t& tr = a.tr;
   const int row0 = b * st.K, V = a.V;
@@ -277,7 +293,9 @@ __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared
       const int tok = tr.child_tok[e];
       // rows_per_user == 1: the K beams of a user share one logits row (step 0: identical beams)
       const int lr = a.rows_per_user == 1 ? b : r;
-      const float sc = (a.logits[(size_t)lr * V + tok] - a.lse[lr]) + st.beam_scores[r];
+      float sc;
+      if constexpr (GRP) sc = diversity(a, sh, nprev, tok, a.logits[(size_t)lr * V + tok] - a.lse[lr]) + st.beam_scores[r];
+      else sc = (a.logits[(size_t)lr * V + tok] - a.lse[lr]) + st.beam_scores[r];
       key = child_alive<FILT>(a, b, e) ? cand_key(sc, k, V, tok) : 0ull;
     }
     kw[i] = key;
@@ -360,21 +378,24 @@ __device__ __forceinline__ void top_p_select(unsigned long long* keys, int NC, i
 // all).  BeamSearchScorer.process on one thread, then the sequences / ancestor table / per-row state are advanced through
 // new_seq [K][Tmax] / new_anc [Tmax][K] (LDS).  FILT: the zero keys of dead candidates sort last, so the ranking ends at the first
 // one, and a filler token is any token that is not an ALIVE child of beam 0's node.
+//
+// It comes in two halves.  step_rank is the scorer for beams [k0, k0 + kn) of the user -- all K of the plain search, one group of a
+// group search: keys[0, min(C, 2 kn)) are THEIR best candidates (C of them in all), their slots of sel_* are filled,
+// "beam 0" of the filler rule is beam k0, EOS candidates go to the user's one heap of capacity K and the done test runs against it.
+// step_advance then moves all K rows at once.
 template <int NTHR, bool FILT>
-__device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int* new_seq, int* new_anc,
-                                            int b, int tid) {
+__device__ __forceinline__ void step_rank(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int b, int tid, int k0, int kn,
+                                          int C) {
   const gram_beam_state_t& st = a.st;
   const gram_trie_t& tr = a.tr;
-  const int K = st.K, T = st.Tmax, R = st.B * K, V = a.V, cur_len = a.cur_len;
+  const int K = st.K, T = st.Tmax, V = a.V, cur_len = a.cur_len;
   const int row0 = b * K;
-  const int t = cur_len - 1;  // decode step whose K/V were just written
-  const int C = sh.C;
   const bool isdone = sh.isdone != 0;
 
   // the Trie edge of every ranked candidate, looked up by 2K threads at once (one binary search each; the walk below ran them one
   // after the other: up to K dependent searches of ~6 global loads each on a single thread)
   if (!isdone) {
-    for (int rank = tid; rank < 2 * K; rank += NTHR) {
+    for (int rank = tid; rank < 2 * kn; rank += NTHR) {
       int e = -1;
       if (rank < C && (!FILT || keys[rank] != 0ull)) {
         const unsigned long long key = keys[rank];
@@ -390,7 +411,7 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
   if (tid == 0) {
     if (isdone) {
       // BeamSearchScorer.process pads a finished user
-      for (int j = 0; j < K; ++j) {
+      for (int j = k0; j < k0 + kn; ++j) {
         sh.sel_score[j] = 0.f;
         sh.sel_tok[j] = st.pad;
         sh.sel_par[j] = j;
@@ -398,10 +419,10 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
       }
     } else {
       int j = 0;
-      int ftok = 0;  // next filler token candidate (beam 0, -inf), ascending flat index
-      const int node0 = st.node[row0];
+      int ftok = 0;  // next filler token candidate (beam k0, -inf), ascending flat index
+      const int node0 = st.node[row0 + k0];
       float best = -INFINITY;
-      for (int rank = 0; rank < 2 * K && j < K; ++rank) {
+      for (int rank = 0; rank < 2 * kn && j < kn; ++rank) {
         float sc;
         int k, tok;
         const bool real = rank < C && (!FILT || keys[rank] != 0ull);
@@ -421,25 +442,25 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
             while (ftok < V && find_child(tr, node0, ftok) >= 0) ++ftok;
           }
           sc = -INFINITY;
-          k = 0;
+          k = k0;
           tok = ftok++;
         }
         if (rank == 0) best = sc;
         if (tok == st.eos) {
-          if (rank >= K) continue;
+          if (rank >= kn) continue;
           hyp_add(st, b, st.seq + (size_t)(row0 + k) * T, cur_len, sc);
         } else {
           const int e = real ? sh.edge[rank] : -1;
-          sh.sel_score[j] = sc;
-          sh.sel_tok[j] = tok;
-          sh.sel_par[j] = k;
-          sh.sel_node[j] = e < 0 ? -1 : tr.child_node[e];
+          sh.sel_score[k0 + j] = sc;
+          sh.sel_tok[k0 + j] = tok;
+          sh.sel_par[k0 + j] = k;
+          sh.sel_node[k0 + j] = e < 0 ? -1 : tr.child_node[e];
           ++j;
         }
       }
-      if (j < K) {
+      if (j < kn) {
         st.error[0] = 1;  // HF raises ValueError here
-        for (; j < K; ++j) { sh.sel_score[j] = -INFINITY; sh.sel_tok[j] = st.pad; sh.sel_par[j] = 0; sh.sel_node[j] = -1; }
+        for (; j < kn; ++j) { sh.sel_score[k0 + j] = -INFINITY; sh.sel_tok[k0 + j] = st.pad; sh.sel_par[k0 + j] = k0; sh.sel_node[k0 + j] = -1; }
       }
       // BeamHypotheses.is_done(best_sum_logprobs = next_scores.max(), cur_len)
       if (st.n_hyps[b] >= K) {
@@ -449,8 +470,15 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
     }
   }
   gram_sync();
+}
 
-  // advance sequences / ancestor table / per-row state (read old -> LDS -> write)
+// advance sequences / ancestor table / per-row state of all K rows from sel_* (read old -> LDS -> write)
+template <int NTHR>
+__device__ __forceinline__ void step_advance(const StepArgs& a, const StepShared& sh, int* new_seq, int* new_anc, int b, int tid) {
+  const gram_beam_state_t& st = a.st;
+  const int K = st.K, T = st.Tmax, R = st.B * K, cur_len = a.cur_len;
+  const int row0 = b * K;
+  const int t = cur_len - 1;  // decode step whose K/V were just written
   for (int idx = tid; idx < K * T; idx += NTHR) {
     const int j = idx / T, p = idx - j * T;
     int v = 0;
@@ -477,6 +505,14 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, c
     st.tokens[row0 + tid] = sh.sel_tok[tid];
     st.node[row0 + tid] = sh.sel_node[tid];
   }
+}
+
+// the plain search: one group of K beams over the user's C = sh.C candidates
+template <int NTHR, bool FILT>
+__device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int* new_seq, int* new_anc,
+                                            int b, int tid) {
+  step_rank<NTHR, FILT>(a, sh, keys, b, tid, 0, a.st.K, sh.C);
+  step_advance<NTHR>(a, sh, new_seq, new_anc, b, tid);
 }
 
 constexpr int kOneShotMaxKeys = 16384;  // K * max_fanout the one-shot kernel takes (128 KB of keys)
@@ -619,6 +655,129 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
   }
   step_finish<NTHR, FILT>(a, sh, keys, new_seq, new_anc, b, tid);
 }
+// GROUP form (HF group_beam_search + HammingDiversityLogitsProcessor): the K beams are G groups of gs = K / G, searched
+// one after the other inside the step.  The workgroup of a user loops over the groups: group g's keys are built from ITS beams'
+// candidates only -- a contiguous range [pre[g gs], pre[(g + 1) gs]) of the user's list, so the plain step's windows serve -- with
+// the diversity term over the tokens groups 0..g-1 just chose (sel_tok[0, g gs), in LDS), then the same top-P selection (P >= 2 gs)
+// and step_rank for the group's slots; a user that finishes at group g has its later groups padded in the same step.  All K rows
+// advance together at the end.  Every candidate's logit is still computed once per step (step 0's shared row: once into s_log while
+// it fits there), and nothing but the final state goes to HBM.
+// CHUNKED = false: a group's candidates in LDS at once, keys [nkeys >= gs * max_fanout] and s_log [nlog >= max_fanout];
+// CHUNKED = true: streamed through keys [kChunkKeys] (cap fresh ones per round) and s_log [kChunkLog], as beam_step_chunked_kernel.
+// LDS: the plain kernels' sums with gs in K's place for the keys: one-shot 8 * nkeys + 4 * max_fanout + 8 * K * Tmax + ~3 KB
+// (K = 20, G = 5, fan-out 255: 8 + 1 + 1.9 + 3 = 14 KB against the plain step's 72 KB), chunked 32 + 8 + 8 * K * Tmax / 1 024 + 3 KB.
+template <int NTHR, bool CHUNKED, typename... UI>
+__global__ __launch_bounds__(NTHR) void beam_group_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
+                                                              const float* __restrict__ lse, int V, int cur_len, int nkeys, int nlog,
+                                                              int cap, int rows_per_user, const p16* __restrict__ hd,
+                                                              const p16* __restrict__ emb, int d, const int32_t* __restrict__ rowpos,
+                                                              int pieces, const float* __restrict__ emb32, int G, float lam, UI... ui) {
+  constexpr bool FILT = filtered<UI...>();
+  constexpr int MAXN = CHUNKED ? kChunkKeys : kOneShotMaxKeys;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nkeys]
+  float* s_log = reinterpret_cast<float*>(keys + nkeys);                   // [nlog] (a multiple of 4)
+  int* new_seq = reinterpret_cast<int*>(s_log + nlog);                     // [K][Tmax] + [Tmax][K]
+  int* new_anc = new_seq + st.K * st.Tmax;
+  __shared__ StepShared sh;
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0, items_ptr(ui...), lam};
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int K = st.K, gs = K / G;
+  step_setup(a, sh, b, tid, 0);
+  if (!sh.isdone) flag_nonfinite_lse(a, sh, b, tid);
+  int P = 64;
+  while (P < 2 * gs) P <<= 1;
+  if (nkeys > MAXN) nkeys = MAXN;  // (the launcher's job, as cap below)
+  const bool shared0 = logits == nullptr && rows_per_user == 1;
+  const int cnt0 = sh.pre[1];  // shared0: the fan-out of the one node every beam stands on
+  bool have_log = false;       // shared0: s_log holds all cnt0 logits (uniform over the workgroup)
+
+  for (int g = 0; g < G; ++g) {
+    const int k0 = g * gs, nprev = k0;
+    const int c0 = sh.pre[k0];
+    int Cg = sh.pre[k0 + gs] - c0;
+    if (!sh.isdone) {
+      if constexpr (!CHUNKED) {
+        if (Cg > nkeys || (shared0 && cnt0 > nlog)) {  // (a Trie wider than its max_fanout says: the plain step's error 2)
+          if (tid == 0) st.error[0] = 2;
+          Cg = 0;
+        }
+        int NC = 64;
+        while (NC < Cg) NC <<= 1;
+        for (int i = Cg + tid; i < NC; i += NTHR) keys[i] = 0ull;
+        if (Cg > 0) {
+          if (logits != nullptr) {
+            dense_window<NTHR, FILT, true>(a, sh, keys, b, tid, c0, Cg, Cg, nprev);
+          } else if (!shared0) {
+            sparse_window<NTHR, FILT, true>(a, sh, keys, s_log, b, tid, c0, Cg, false, nprev);
+          } else {
+            if (!have_log) {
+              sparse_window<NTHR, FILT>(a, sh, keys, s_log, b, tid, 0, cnt0, true);
+              have_log = true;
+              gram_sync();
+            }
+            shared0_keys<NTHR, FILT, true>(a, sh, keys, s_log, b, tid, 0, cnt0, k0, gs, nprev);
+          }
+        }
+        gram_sync();
+        flag_nonfinite_keys<NTHR, FILT>(a, keys, Cg, tid);
+        gram_sync();
+        top_p_select<NTHR, MAXN>(keys, NC, P, tid);
+      } else {
+        int cp = cap;
+        if (cp > nkeys - P) cp = nkeys - P;
+        if (cp < 1) cp = 1;
+        unsigned long long* kw = keys + P;
+        for (int i = tid; i < P; i += NTHR) keys[i] = 0ull;  // nothing carried yet
+        auto merge = [&](int n) {
+          int na = 2 * P;  // the power of two >= P + n
+          while (na < P + n) na <<= 1;
+          for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
+          gram_sync();
+          flag_nonfinite_keys<NTHR, FILT>(a, kw, n, tid);
+          gram_sync();
+          top_p_select<NTHR, MAXN>(keys, na, P, tid);
+        };
+        if (logits != nullptr) {
+          for (int o = 0; o < Cg; o += cp) {
+            const int n = Cg - o < cp ? Cg - o : cp;
+            dense_window<NTHR, FILT, true>(a, sh, kw, b, tid, c0 + o, n, n, nprev);
+            merge(n);
+          }
+        } else if (!shared0) {
+          for (int o = 0; o < Cg; o += cp) {
+            const int n = Cg - o < cp ? Cg - o : cp;
+            sparse_window<NTHR, FILT, true>(a, sh, kw, s_log, b, tid, c0 + o, n, false, nprev);
+            merge(n);
+          }
+        } else {
+          const int njmax = cp < nlog ? cp : nlog;
+          const bool single = cnt0 <= njmax;  // every logit fits s_log: computed for the first group, kept for the others
+          for (int j0 = 0; j0 < cnt0; j0 += njmax) {
+            const int nj = cnt0 - j0 < njmax ? cnt0 - j0 : njmax;
+            if (!(single && have_log)) {
+              sparse_window<NTHR, FILT>(a, sh, kw, s_log, b, tid, j0, nj, true);
+              gram_sync();
+            }
+            const int kgmax = cp / nj;  // >= 1
+            for (int kk = 0; kk < gs; kk += kgmax) {
+              const int kg = gs - kk < kgmax ? gs - kk : kgmax;
+              shared0_keys<NTHR, FILT, true>(a, sh, kw, s_log, b, tid, j0, nj, k0 + kk, kg, nprev);
+              merge(kg * nj);
+            }
+          }
+          have_log = true;
+        }
+      }
+    }
+    step_rank<NTHR, FILT>(a, sh, keys, b, tid, k0, gs, Cg);
+    if (tid == 0) sh.isdone = st.done[b];  // (this group may have finished the user: the later ones are padded)
+    gram_sync();
+  }
+  step_advance<NTHR>(a, sh, new_seq, new_anc, b, tid);
+}
+
 // The sparse logits of a search step, computed by MANY workgroups (a handful of users: beam_step_kernel's one workgroup per user pulls
 // up to K * fan-out fp32 lm_head rows -- 15 MB at K = 20, fan-out 255 -- through ONE CU, 70 us on average and up to 290 us of a one-user
 // step).  Workgroup (chunk, user) recomputes the user's candidate list exactly as beam_step_kernel does (beams in order, each beam's
@@ -1116,7 +1275,7 @@ extern "C" int gram_beam_init(const gram_beam_state_t* st, const gram_trie_t* tr
   if (int e = check_state(st)) return e;
   if (!tr) return GRAM_E_ARG;
   const int R = st->B * st->K;
-  hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, *st, *tr, start_token);
+  hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, *st, *tr, start_token, st->K);
   GRAM_CHECK_LAUNCH();
   return 0;
 }
@@ -1206,6 +1365,87 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
         rowpos, pieces, emb32, pre, ui...);
   };
   return items ? launch(*items) : launch();
+}
+
+// the (K, G, lambda) of a group search: G groups of K / G beams, a finite penalty >= 0
+static int check_groups(int K, int num_groups, float diversity_penalty) {
+  if (num_groups < 1 || num_groups > K || K % num_groups != 0) return GRAM_E_ARG;
+  if (!(diversity_penalty >= 0.f && diversity_penalty < INFINITY)) return GRAM_E_ARG;
+  return 0;
+}
+
+extern "C" int gram_beam_init_groups(const gram_beam_state_t* st, const gram_trie_t* tr, int start_token, int num_groups, void* stream) {
+  if (int e = check_state(st)) return e;
+  if (!tr || num_groups < 1 || num_groups > st->K || st->K % num_groups != 0) return GRAM_E_ARG;
+  const int R = st->B * st->K;
+  hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, *st, *tr, start_token,
+                     st->K / num_groups);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+// The group step (beam_group_step_kernel): which form runs is decided as for the plain step, with a group's gs * max_fanout
+// candidates in the place of K * max_fanout.  (The small-batch sparse_logits_kernel is not used: the group step computes its logits
+// itself at every batch size.)
+static int launch_group_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V, int cur_len,
+                             int rows_per_user, const void* hd, const void* emb, const float* emb32, int d, const int32_t* rowpos,
+                             int pieces, int num_groups, float diversity_penalty, const gram_user_items_t* items, void* stream) {
+  if (int e = check_state(st)) return e;
+  if (int e = check_groups(st->K, num_groups, diversity_penalty)) return e;
+  if (items)
+    if (int e = check_items(items)) return e;
+  if (!tr || !lse || cur_len < 1 || cur_len >= st->Tmax || V < 2 || (rows_per_user != 1 && rows_per_user != st->K)) return GRAM_E_ARG;
+  if (rowpos && rows_per_user != st->K) return GRAM_E_ARG;
+  if (!logits && (!hd || (!emb && !emb32) || d < 64 || (d & 63))) return GRAM_E_ARG;
+  if (pieces < 1 || pieces > GRAM_MAX_PIECES || (pieces > 1 && !emb32)) return GRAM_E_ARG;
+  if (tr->max_fanout < 0 || (long long)st->K * V > INT32_MAX || tr->max_fanout > V) return GRAM_E_ARG;
+  const int gs = st->K / num_groups;
+  const long long need = (long long)gs * tr->max_fanout;
+  int nc = 64;
+  while (nc < need && nc < kOneShotMaxKeys) nc <<= 1;
+  const int nlog_one = (tr->max_fanout + 3) / 4 * 4;
+  const size_t seq_bytes = (size_t)2 * st->K * st->Tmax * 4;
+  const size_t smem_one = (size_t)nc * 8 + (size_t)nlog_one * 4 + seq_bytes;
+  const bool chunked = g_beam_chunked == 1 || need > kOneShotMaxKeys || smem_one > 152 * 1024;
+  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
+  static const int wide_max_b = getenv("GRAM_BEAM_WIDE_MAXB") ? atoi(getenv("GRAM_BEAM_WIDE_MAXB")) : 128;
+  const bool wide = st->B <= wide_max_b;
+  int P = 64;
+  while (P < 2 * gs) P <<= 1;
+  int cap = kChunkKeys - P;
+  if (g_beam_chunk_cap > 0 && g_beam_chunk_cap < cap) cap = g_beam_chunk_cap;
+  const int nkeys = chunked ? kChunkKeys : nc, nlog = chunked ? kChunkLog : nlog_one;
+  const size_t smem = chunked ? (size_t)kChunkKeys * 8 + (size_t)kChunkLog * 4 + seq_bytes : smem_one;
+  auto launch = [&](auto form, auto... ui) {
+    constexpr bool CH = decltype(form)::value;
+    return launch_step_pair<beam_group_step_kernel<256, CH, decltype(ui)...>, beam_group_step_kernel<1024, CH, decltype(ui)...>>(
+        wide, st->B, smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nkeys, nlog, cap, rows_per_user, (const p16*)hd,
+        (const p16*)emb, d, rowpos, pieces, emb32, num_groups, diversity_penalty, ui...);
+  };
+  if (chunked) return items ? launch(std::true_type{}, *items) : launch(std::true_type{});
+  return items ? launch(std::false_type{}, *items) : launch(std::false_type{});
+}
+
+extern "C" int gram_beam_step_groups(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
+                                     int cur_len, int rows_per_user, int num_groups, float diversity_penalty, void* stream) {
+  if (int e = check_state(st)) return e;
+  if (int e = check_groups(st->K, num_groups, diversity_penalty)) return e;
+  if (!logits) return GRAM_E_ARG;
+  return launch_group_step(st, tr, logits, lse, V, cur_len, rows_per_user, nullptr, nullptr, nullptr, 0, nullptr, 1, num_groups,
+                           diversity_penalty, nullptr, stream);
+}
+
+extern "C" int gram_beam_step_groups_sparse(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
+                                            const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V,
+                                            int cur_len, int rows_per_user, const int32_t* rowpos, int pieces, int num_groups,
+                                            float diversity_penalty, const gram_user_items_t* items, void* stream) {
+  if (int e = check_state(st)) return e;
+  if (int e = check_groups(st->K, num_groups, diversity_penalty)) return e;
+  if (!hidden_bf16) return GRAM_E_ARG;
+  // pieces == 1 reads lm_head_bf16, two pieces (or no lm_head_bf16) lm_head_f32: as gram_sample_step
+  const bool use32 = pieces > 1 || !lm_head_bf16;
+  return launch_group_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, use32 ? nullptr : lm_head_bf16,
+                           use32 ? lm_head_f32 : nullptr, d, rowpos, pieces, num_groups, diversity_penalty, items, stream);
 }
 
 extern "C" int gram_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,

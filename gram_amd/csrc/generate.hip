@@ -536,11 +536,20 @@ int decode_step(const gram_model* m, const Workspace& w, const int32_t* tokens, 
   return lm_head(m, w, R, logits, lse_part, st);
 }
 
+// the search mode of gram_generate_groups (NULL everywhere else: the plain search)
+struct GroupMode {
+  int num_groups;
+  float diversity_penalty;
+};
+
 // the search step on the hidden states decode_step left in w.dec.h (rowpos: live-row step, else NULL; items: per-user item filters of
-// gram_generate_items, else NULL)
+// gram_generate_items, else NULL; grp: the group step, else NULL)
 int search_step(const gram_model* m, const Workspace& w, const gram_trie_t* trie, int cur_len, int rows_per_user, const int32_t* rowpos,
-                const gram_user_items_t* items, void* st) {
+                const gram_user_items_t* items, void* st, const GroupMode* grp = nullptr) {
   const gram_model_desc_t& c = m->d;
+  if (grp)
+    return gram_beam_step_groups_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
+                                        rows_per_user, rowpos, w.pieces, grp->num_groups, grp->diversity_penalty, items, st);
   if (items) {
     if (w.pieces > 1)
       return gram_beam_step_sparse_split_items(&w.beam, trie, w.dec.h, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len, rows_per_user,
@@ -922,9 +931,12 @@ namespace {
 // launch cost, and a captured train cannot take the live-row step, whose row counts travel through the host -- and removed in round 4.)
 int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                   int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
-                  const gram_trie_tail_t* tail, int64_t* sequences, float* scores, void* stream) {
+                  const gram_trie_tail_t* tail, const GroupMode* grp, int64_t* sequences, float* scores, void* stream) {
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
-  TRY(gram_beam_init(&w.beam, trie, /*decoder_start_token_id=*/0, stream));
+  // grp: group beam search (gram_generate_groups): its init and its search step, the same loop (a -inf beam has no node, so
+  // gram_live_rows' liveness test holds unchanged); the caller passes no tail
+  if (grp) TRY(gram_beam_init_groups(&w.beam, trie, /*decoder_start_token_id=*/0, grp->num_groups, stream));
+  else TRY(gram_beam_init(&w.beam, trie, /*decoder_start_token_id=*/0, stream));
   if (K == 1) {  // HF: num_beams == 1 -> greedy_search (raw logits, no hypotheses, no scores)
     for (int t = 0; t + 1 < max_length; ++t) {
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, 1, B, max_length, t, w.logits, nullptr, nullptr, stream));
@@ -996,7 +1008,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
                             stream));
             TRY(gram_lse_combine(w.lse_part, w.lse, counts[0], m->d.vocab / 64, stream));
           }  // else: no beam can be extended; the search step below reads no decoder row
-          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream));
+          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream, grp));
           continue;
         }
       }
@@ -1004,7 +1016,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, Kt, B * K, max_length, t, nullptr, w.lse_part, nullptr,
                       stream));
       TRY(gram_lse_combine(w.lse_part, w.lse, B * Kt, m->d.vocab / 64, stream));
-      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream));
+      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream, grp));
     }
     TRY(gram_beam_finalize(&w.beam, nret, max_length, sequences, scores, w.width, stream));
   }
@@ -1032,7 +1044,7 @@ static int read_width_and_error(const Workspace& w, int32_t* width_host, void* s
 static int generate_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                          int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp,
                          const gram_user_items_t* items, const gram_trie_tail_t* tail, void* workspace, int64_t workspace_bytes,
-                         int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
+                         int64_t* sequences, float* scores, int32_t* width_host, void* stream, const GroupMode* grp = nullptr) {
   TRY(check_shapes(m, B, N, L, K, max_length));
   TRY(check_compaction(comp, B, N));
   if (!trie || nret < 1 || nret > K || !sequences || (!scores && K != 1)) return GRAM_E_ARG;
@@ -1052,7 +1064,7 @@ static int generate_call(const gram_model_t* m, const int64_t* input_ids, const 
     }
   }
   w.beam.length_penalty = length_penalty;
-  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, sequences, scores, stream));
+  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, grp, sequences, scores, stream));
   return read_width_and_error(w, width_host, stream);
 }
 
@@ -1088,6 +1100,22 @@ extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_i
     return GRAM_E_ARG;
   return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
                        workspace_bytes, sequences, scores, width_host, stream);
+}
+
+// group beam search: gram_generate_ex's call with the group init and the group step; items may be NULL
+extern "C" int gram_generate_groups(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
+                                    int nret, int max_length, float length_penalty, const gram_trie_t* trie,
+                                    const gram_compaction_t* comp, int num_groups, float diversity_penalty,
+                                    const gram_user_items_t* items, void* workspace, int64_t workspace_bytes, int64_t* sequences,
+                                    float* scores, int32_t* width_host, void* stream) {
+  if (K < 2 || num_groups < 1 || num_groups > K || K % num_groups != 0 || !(diversity_penalty >= 0.f && diversity_penalty < INFINITY))
+    return GRAM_E_ARG;
+  if (items && (!items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
+                items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW)))
+    return GRAM_E_ARG;
+  const GroupMode grp{num_groups, diversity_penalty};
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
+                       workspace_bytes, sequences, scores, width_host, stream, &grp);
 }
 
 // ---- Trie-constrained sampling (gram_sample) ------------------------------------------------------------------------

@@ -1202,7 +1202,7 @@ class GRAM(nn.Module):
     def generate(self, input_ids, attention_mask, max_length, prefix_allowed_tokens_fn=None, num_beams=1,
                  num_return_sequences=None, output_scores=True, return_dict_in_generate=True, length_penalty=1.0,
                  exclude_items=None, allowed_items=None, candidates=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
-                 uniforms=None, generator=None, **unused):
+                 uniforms=None, generator=None, num_beam_groups=1, diversity_penalty=0.0, **unused):
         """GRAM.generate (gram.py:74-107) with the kwargs single_runner_gram.py:641-651 passes.
 
         input_ids (B,N,L) int64, attention_mask (B,N,L) bool on the model's device.  Returns a
@@ -1227,13 +1227,27 @@ class GRAM(nn.Module):
         ``sequences_scores=None`` (as HF's ``sample``), ``sequence_logprobs`` (B*R,) = the model's log-probability of each row (what
         ``score_sequences`` returns for it) and ``sample_logprobs`` (B*R,) = its log-probability under the warped distribution it was
         drawn from.  ``exclude_items`` / ``allowed_items`` work as for beam search.  A row's draw depends on its user, its uniforms and
-        the parameters only, not on the batch or on R.  Without ``do_sample`` the five sampling arguments are ignored, as before."""
+        the parameters only, not on the batch or on R.  Without ``do_sample`` the five sampling arguments are ignored, as before.
+
+        Group (diverse) beam search: ``num_beam_groups`` = G > 1, a divisor of ``num_beams``, with ``diversity_penalty`` >= 0 -- HF
+        4.26's ``group_beam_search`` with the Hamming diversity penalty: the beams are G groups searched one
+        after the other in every step, and a token costs a group ``diversity_penalty`` for every beam of the earlier groups that
+        chose it in that step, which spreads a user's list over different branches of the Trie.  Returns ``sequences`` and
+        ``sequences_scores`` as beam search does; the scores include the penalties, as in HF.  The penalty acts per step, not per
+        sequence, so two groups can return the SAME sequence: ``sequence_items`` then maps both rows to the same item.
+        ``exclude_items`` / ``allowed_items`` work as for beam search.  G = 1 is plain beam search (and refuses a non-zero
+        ``diversity_penalty``, as before)."""
         if prefix_allowed_tokens_fn is None:
             raise NotImplementedError("unconstrained generation is not on GRAM's scoring path (a Trie is always passed)")
         # HF kwargs that would change the search: refuse the ones this path does not implement instead of ignoring them
         neutral = {"do_sample": False, "early_stopping": False, "num_beam_groups": 1, "repetition_penalty": 1.0,
                    "no_repeat_ngram_size": 0, "diversity_penalty": 0.0, "use_cache": True, "temperature": 1.0, "top_k": 50,
                    "top_p": 1.0, "min_length": 0, "pad_token_id": 0, "eos_token_id": 1, "decoder_start_token_id": 0}
+        G = 1 if num_beam_groups is None else int(num_beam_groups)
+        if G == 1:  # (one group is the plain search: the two arguments are judged by name like every other HF keyword)
+            unused = dict(unused, num_beam_groups=num_beam_groups, diversity_penalty=diversity_penalty)
+        else:  # (every refusal of the group search, before anything touches the device)
+            lam = self._group_args(int(num_beams), G, diversity_penalty, do_sample, prefix_allowed_tokens_fn, num_return_sequences)
         if not do_sample:  # (greedy and beam search ignore the sampling arguments, by name as they always did)
             unused = dict(unused, **{k: v for k, v in (("uniforms", uniforms), ("generator", generator)) if v is not None})
         for k, v in unused.items():
@@ -1313,7 +1327,7 @@ class GRAM(nn.Module):
         # the tail pass (gram_generate_tail; taken by size, GRAM_TAIL_PASS=0 switches it off: gram_tail_pass_wanted): where the Trie has a tail inside this call's
         # steps, the workspace grows by the forest's rows (gram_workspace_bytes_tail); a device that cannot hold them decodes step by
         # step -- the same results
-        d_tail, tail_steps = self._tail_plan(prefix_allowed_tokens_fn, K, int(max_length), filtered)
+        d_tail, tail_steps = self._tail_plan(prefix_allowed_tokens_fn, K, int(max_length), filtered) if G == 1 else (0, 0)
         tail = tail_steps > 0 and _lib.load().gram_tail_pass_wanted(handle, B, N, Lp) == 1
         ws = self._tail_workspace(handle, B, N, Lp, K, int(max_length), tail_steps) if tail else None
         tail = ws is not None
@@ -1325,7 +1339,12 @@ class GRAM(nn.Module):
         from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
         args = (ids, mask, int(handle), ws, t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len), K, nret, int(max_length),
                 float(length_penalty), *self._comp_args(comp))
-        if filtered:
+        if G > 1:  # group beam search (gram_generate_groups): the same arguments, no tail pass
+            lists = ()
+            if filtered:
+                lists = (*flat.leaf_ranges_on(dev), flat.item_ranks_on(dev, candidates)[1], items, allow)
+            seqs, scores, width = torch.ops.gram.generate_groups(*args[:13], G, lam, *args[13:], *lists)
+        elif filtered:
             leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
             seqs, scores, width = torch.ops.gram.generate_items(*args, leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items,
                                                                 allow)
@@ -1339,6 +1358,25 @@ class GRAM(nn.Module):
         if not return_dict_in_generate:
             return seqs
         return GenerateOutput(sequences=seqs, sequences_scores=scores)
+
+    def _group_args(self, K: int, G: int, diversity_penalty, do_sample, fn, num_return_sequences) -> float:
+        """The arguments of ``generate(num_beam_groups=G > 1)``, or the refusal; returns the penalty.  Everything is checked on the
+        host, before the model is packed or a tensor is moved."""
+        if do_sample:
+            raise ValueError("generate(num_beam_groups > 1) is a beam search: it does not go with do_sample=True (as in HF)")
+        if G < 1 or G > K or K % G:
+            raise ValueError(f"generate: num_beam_groups must be a divisor of num_beams (got num_beams={K}, num_beam_groups={G})")
+        try:
+            lam = float(0.0 if diversity_penalty is None else diversity_penalty)
+        except (TypeError, ValueError):
+            raise ValueError(f"generate: diversity_penalty must be a number (got {diversity_penalty!r})") from None
+        if not (0.0 <= lam < float("inf")):
+            raise ValueError(f"generate: diversity_penalty must be a finite number >= 0 (got {diversity_penalty!r}); 0.0 adds no penalty")
+        if not 1 <= int(num_return_sequences or K) <= K:
+            raise ValueError(f"generate: num_return_sequences must lie in [1, num_beams] (got {num_return_sequences!r})")
+        if self._closure_trie(fn) is None:
+            raise NotImplementedError("generate(num_beam_groups > 1) needs the Trie closure form of prefix_allowed_tokens_fn")
+        return lam
 
     def _sample_args(self, B: int, max_length: int, num_beams, num_return_sequences, temperature, top_k, top_p, uniforms, fn):
         """The arguments of ``generate(do_sample=True)`` as (R, temperature, top_k, top_p), or the refusal: everything is checked on

@@ -8,6 +8,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
     torch.ops.gram.generate          GRAM.generate's whole path (gram_generate_ex) -- what ``GRAM.generate`` calls
     torch.ops.gram.generate_items    the same path with per-user item filters (gram_user_items_prepare + gram_generate_items) --
                                      ``GRAM.generate(exclude_items= / allowed_items=)``
+    torch.ops.gram.generate_groups   group (diverse) beam search, with or without the per-user item filters (gram_generate_groups) --
+                                     ``GRAM.generate(num_beam_groups=, diversity_penalty=)``
     torch.ops.gram.sample            Trie-constrained sampling, R draws per user with their log-probabilities (gram_sample) --
                                      ``GRAM.generate(do_sample=True)``
     torch.ops.gram.sample_items      the same with per-user item filters (gram_user_items_prepare + gram_sample_items)
@@ -207,6 +209,64 @@ def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, works
 def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
       cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
+    return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
+
+
+# ---------------------------------------------------------------------------------------------- group (diverse) beam search
+def _check_groups(op: str, num_beams: int, num_beam_groups: int, diversity_penalty: float) -> None:
+    """The (K, G, penalty) of a group search, or a ``ValueError`` in ``op``'s name (what gram_generate_groups answers with GRAM_E_ARG)"""
+    K, G, lam = int(num_beams), int(num_beam_groups), float(diversity_penalty)
+    if not 2 <= K <= _lib.GRAM_MAX_BEAMS or G < 1 or G > K or K % G:
+        raise ValueError(f"{op}: need 2 <= num_beams <= {_lib.GRAM_MAX_BEAMS} and num_beam_groups a divisor of it "
+                         f"(got num_beams={K}, num_beam_groups={G})")
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError(f"{op}: diversity_penalty must be a finite number >= 0 (got {diversity_penalty!r})")
+
+
+@torch.library.custom_op("gram::generate_groups", mutates_args=("workspace",), device_types="cuda")
+def generate_groups(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                    trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
+                    num_return_sequences: int, max_length: int, length_penalty: float, num_beam_groups: int, diversity_penalty: float,
+                    comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor],
+                    cache_x: Optional[Tensor], n_cached: int, cache_L: int, leaf_lo: Optional[Tensor] = None,
+                    leaf_hi: Optional[Tensor] = None, item_rank: Optional[Tensor] = None, items: Optional[Tensor] = None,
+                    allow: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """Group (diverse) beam search, HF ``group_beam_search`` on the Trie (gram_generate_groups): ``generate``'s inputs and outputs,
+    ``workspace`` of gram_workspace_bytes, plus num_beam_groups (a divisor of num_beams >= 2) and diversity_penalty (finite, >= 0).
+    The optional tail leaf_lo / leaf_hi / item_rank / items / allow is ``generate_items``'s: given (all four tensors), every user
+    searches its own view of the Trie, the lists validated and prepared the same way."""
+    _check_groups("generate_groups", num_beams, num_beam_groups, diversity_penalty)
+    if not 1 <= num_return_sequences <= num_beams:
+        raise ValueError("generate_groups: need 1 <= num_return_sequences <= num_beams")
+    lists = (leaf_lo, leaf_hi, item_rank, items)
+    if any(t is not None for t in lists):
+        if any(t is None for t in lists):
+            raise ValueError("generate_groups: leaf_lo, leaf_hi, item_rank and items come together")
+        trie, comp, ui, _keep = _user_items("generate_groups", input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node,
+                                            trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot, cache_x,
+                                            n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
+        ui_ref = C.byref(ui)
+    else:
+        if input_ids.dim() != 3:
+            raise ValueError("generate_groups: input_ids must be (B, N, L)")
+        dev = input_ids.device
+        _check("input_ids", input_ids, torch.int64)
+        _check("attention_mask", attention_mask, torch.uint8, tuple(input_ids.shape), dev)
+        for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                               ("trie_child_node", trie_child_node, (trie_child_tok.numel(),))):
+            _check(name, t, torch.int32, shape, dev)
+        trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+        comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
+        ui_ref = None
+    with torch.cuda.device(input_ids.device):
+        return _search(_lib.load().gram_generate_groups, "gram_generate_groups", input_ids, attention_mask, handle, workspace, trie, comp,
+                       num_beams, num_return_sequences, max_length, length_penalty, int(num_beam_groups), float(diversity_penalty), ui_ref)
+
+
+@generate_groups.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
+      trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, num_beam_groups, diversity_penalty, comp_map,
+      comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L, leaf_lo=None, leaf_hi=None, item_rank=None, items=None, allow=False):
     return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
 
 

@@ -602,6 +602,43 @@ int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const u
                         const gram_user_items_t* items_host, void* workspace, int64_t workspace_bytes, int64_t* sequences,
                         float* scores, int32_t* width_host, void* stream);
 
+/* ---- Group (diverse) beam search: HF 4.26 `group_beam_search` + HammingDiversityLogitsProcessor on a Trie ----------
+ * K beams = num_groups groups of gs = K / num_groups; group g owns beams [g gs, (g + 1) gs) of every user.  The state is the plain
+ * search's gram_beam_state_t: ONE hypothesis heap of capacity K and one done flag per user, shared by its groups.
+ * One step, for every user and for g = 0 .. num_groups - 1 in order:
+ *   a done user's group gets score 0 and token pad; otherwise candidate (beam k of the group, child token v of its Trie node) scores
+ *     s = logit[row k][v] - lse[row k];  s = s - diversity_penalty * c_v;  s = s + beam_scores[k]       (fp32, one rounding each),
+ *   c_v = the beams of groups 0 .. g - 1 of this user whose token chosen in THIS step is v (nothing is subtracted where c_v = 0 or
+ *   the penalty is 0); the best 2 gs of the group's candidates, ties to the lower k * V + v, padded with -inf fillers on the
+ *   group's first beam, go through BeamSearchScorer.process with group size gs (EOS at rank < gs -> the user's heap; the other
+ *   candidates fill the group's gs slots; fewer than gs is error 1), and done |= heap.is_done(the group's best score, cur_len) --
+ *   so a user can finish at group g of a step: its later groups are padded in the same step.
+ * Then all K rows advance at once.  gram_beam_finalize is the plain search's.  num_groups == 1 with diversity_penalty == 0 is the
+ * plain step bit for bit.  GRAM_E_ARG, before any launch: num_groups < 1, > K or not a divisor of K; a penalty that is negative or
+ * not finite. */
+/* gram_beam_init for a group search: the first beam of every GROUP starts at score 0, the others at -1e9. */
+int gram_beam_init_groups(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, int start_token, int num_groups,
+                          void* stream);
+/* One group step on dense logits f32 [B * rows_per_user][V] (as gram_beam_step; for tests on given logits). */
+int gram_beam_step_groups(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const float* logits, const float* lse, int V,
+                          int cur_len, int rows_per_user, int num_groups, float diversity_penalty, void* stream);
+/* One group step on hidden states (the sparse logits of gram_beam_step_sparse).  lm_head_bf16 / lm_head_f32 / pieces as in
+ * gram_sample_step; rowpos as in gram_beam_step_sparse_live (NULL: rows in place); items_host: per-user item filters or NULL.
+ * A group's candidates are held in LDS up to 16 384 of them and streamed through the 4 096-key array beyond (or under
+ * gram_debug_set_beam_chunked(1) / gram_debug_set_beam_chunk_capacity): the same results bit for bit. */
+int gram_beam_step_groups_sparse(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
+                                 const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                                 int rows_per_user, const int32_t* rowpos, int pieces, int num_groups, float diversity_penalty,
+                                 const gram_user_items_t* items_host, void* stream);
+/* generate(num_beam_groups = num_groups, diversity_penalty): gram_generate_ex's arguments, workspace (gram_workspace_bytes) and
+ * launch train -- encoder, bank, the shared step-0 row, the live-row compaction -- with gram_beam_init_groups and the group step in
+ * the search's place; the tail pass is not taken.  items_host: per-user item filters (as gram_generate_items) or NULL.
+ * sequences_scores include the accumulated penalties, as in HF; two groups can return the same sequence.  K >= 2. */
+int gram_generate_groups(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
+                         int max_length, float length_penalty, const gram_trie_t* trie_host, const gram_compaction_t* compaction_host,
+                         int num_groups, float diversity_penalty, const gram_user_items_t* items_host, void* workspace,
+                         int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream);
+
 /* ---- Trie-constrained sampling: HF 4.26 `sample` restated for a Trie ------------------------------------------------
  * The state is a gram_beam_state_t with K = R samples per user; nothing is ever reordered, so anc keeps the identity gram_beam_init
  * wrote (except slot 0 at the compact step 0, below).  Sampling leaves the hypothesis heap unused and keeps its per-row "finished"

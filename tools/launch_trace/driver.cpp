@@ -39,6 +39,7 @@ struct Case {
   int max_S;                  // != 0: gram_model_set_max_fused_len first (the long cross-attention at every S; the model takes 40 passages)
   int tail_rows;              // != 0: gram_generate_tail with d_tail = 2 and two steps left; gram_tail_forest reports this many rows
   int forest_attn;            // 1: gram_debug_set_tail_forest_attn(1) first (0: the default -- forests this small keep the level train)
+  int groups;                 // != 0: gram_generate_groups with this many beam groups and diversity_penalty = 0.5
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -112,6 +113,8 @@ const Case kCases[] = {
     {"generate_tail_forest_p2_tables", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, true, 0, false, 0, 0, 11, 1},
     {"generate_tail_forest_p1", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 11, 1},
     {"generate_tail_forest_cut", GENERATE, 2, 1, 2, 3, 32, 4, 3, SOME, false, false, false, false, 0, false, 0, 0, 11, 1},
+    // gram_generate_groups (2 groups of 2 beams): the train of generate_p2 with the group init and the group step in the search's place
+    {"generate_groups_p2", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 0, 0, 2},
 };
 
 gram_model_t* make_model(int pieces, int fold, int max_passages) {
@@ -187,6 +190,9 @@ int run(const Case& c) {
   void* io[5] = {fake(), fake(), fake(), fake(), fake()};  // the remaining inputs and outputs of the entry, in its argument order
   switch (c.entry) {
     case GENERATE:
+      if (c.groups)
+        return gram_generate_groups(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, c.groups, 0.5f, nullptr, g_ws,
+                                    g_ws_bytes, (int64_t*)io[0], (float*)io[1], &width, st);
       if (c.items) {
         const gram_user_items_t items{fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), 64, GRAM_ITEMS_EXCLUDE};
         return gram_generate_items(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, &items, g_ws, g_ws_bytes,

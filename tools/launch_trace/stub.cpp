@@ -181,6 +181,15 @@ int gram_xattn_passage_scores(const float* acc, const uint8_t* mask, float* scor
 }
 int gram_lse_combine(const float* lse_part, float* lse, int M, int nblk, void* st) { REC(lse_part, lse, M, nblk, st); }
 int gram_beam_init(const gram_beam_state_t* s, const gram_trie_t* trie, int start, void* st) { REC(s, trie, start, st); }
+int gram_beam_init_groups(const gram_beam_state_t* s, const gram_trie_t* trie, int start, int num_groups, void* st) {
+  REC(s, trie, start, num_groups, st);
+}
+int gram_beam_step_groups_sparse(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, const float* lm32,
+                                 int d, const float* lse, int V, int cur_len, int rows_per_user, const int32_t* rowpos, int pieces,
+                                 int num_groups, float diversity_penalty, const gram_user_items_t* items, void* st) {
+  if (!items) REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, num_groups, diversity_penalty, (const void*)items, st);
+  REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, num_groups, diversity_penalty, items, st);
+}
 int gram_beam_step_sparse(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, int d, const float* lse,
                           int V, int cur_len, int rows_per_user, void* st) {
   REC(s, trie, hidden, lm16, d, lse, V, cur_len, rows_per_user, st);
