@@ -52,6 +52,7 @@ STAGES = ("enc_attn", "enc_ffn", "bank_k", "bank_v", "dec_self", "dec_cross", "d
 vp = C.c_void_p
 i32 = C.c_int32
 i64 = C.c_int64
+u64 = C.c_uint64
 f32 = C.c_float
 
 
@@ -301,6 +302,20 @@ SIGNATURES = {
                               C.POINTER(SampleParams), vp, vp, i64, vp, vp, vp, C.POINTER(i32), vp]),
     "gram_sample_items": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Trie), C.POINTER(Compaction),
                                     C.POINTER(UserItems), C.POINTER(SampleParams), vp, vp, i64, vp, vp, vp, C.POINTER(i32), vp]),
+    # sampling without replacement (stochastic beam search)
+    "gram_sbs_init": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), C.c_int, u64, vp, vp, vp, vp, vp]),
+    "gram_sbs_step": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                f32, u64, vp, vp, vp, vp]),
+    "gram_sbs_step_items": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      f32, u64, vp, vp, vp, C.POINTER(UserItems), vp]),
+    "gram_sbs_finalize": (C.c_int, [C.POINTER(BeamState), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gram_sbs_capacity": (C.c_int, []),
+    "gram_debug_set_sbs_capacity": (C.c_int, [C.c_int]),
+    "gram_workspace_bytes_sbs": (i64, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "gram_generate_sbs": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Trie), C.POINTER(Compaction),
+                                    f32, u64, vp, vp, i64, vp, vp, vp, vp, C.POINTER(i32), vp]),
+    "gram_generate_sbs_items": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Trie), C.POINTER(Compaction),
+                                          C.POINTER(UserItems), f32, u64, vp, vp, i64, vp, vp, vp, vp, C.POINTER(i32), vp]),
 }
 
 # the `_f16` aliases (gram_hip.h): same signatures as the `_bf16` names

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "prof.h"
 #include "sparse_dot.h"
+#include "step_dev.h"
 #include "trie_dev.h"
 
 namespace {
@@ -95,47 +96,8 @@ __global__ void beam_init_kernel(gram_beam_state_t st, gram_trie_t tr, int start
 
 // ---- the search step, in pieces shared by its two kernels: beam_step_kernel (every candidate of a user in LDS at once) and
 // beam_step_chunked_kernel (candidates streamed through a fixed key array).  Both build the same keys with the same arithmetic, run
-// the same top-P selection and finish with the same code, so they return the same bits wherever both can run.
-
-// the step's operands (the kernels' parameters, handed on by reference)
-struct StepArgs {
-  const gram_beam_state_t& st;
-  const gram_trie_t& tr;
-  const float* __restrict__ logits;
-  const float* __restrict__ lse;
-  int V, cur_len, rows_per_user;
-  const p16* __restrict__ hd;
-  const p16* __restrict__ emb;
-  int d;
-  const int32_t* __restrict__ rowpos;
-  int pieces;
-  const float* __restrict__ emb32;
-  const float* __restrict__ pre;
-  int pre_stride;
-  const gram_user_items_t* ui;  // per-user item filter (the FILT instantiations only; nullptr otherwise)
-  float lam = 0.f;              // diversity penalty (the group step only)
-};
-
-// (the per-user item filters -- filtered(), items_ptr(), node_alive() -- are trie_dev.h's, shared with the sampling step)
-template <bool FILT>
-__device__ __forceinline__ bool child_alive(const StepArgs& a, int b, int edge) {
-  if constexpr (FILT) return node_alive(*a.ui, b, a.tr.child_node[edge]);
-  else return true;
-}
-
-// the step's small per-user tables (static LDS, ~3 KB)
-struct StepShared {
-  int pre[GRAM_MAX_BEAMS + 1];
-  int C, NC, isdone;
-  float sel_score[GRAM_MAX_BEAMS];
-  int sel_tok[GRAM_MAX_BEAMS], sel_par[GRAM_MAX_BEAMS], sel_node[GRAM_MAX_BEAMS];
-  int edge[2 * GRAM_MAX_BEAMS];
-  int off[GRAM_MAX_BEAMS], cnt[GRAM_MAX_BEAMS], lr[GRAM_MAX_BEAMS];
-};
-
-__device__ __forceinline__ unsigned long long cand_key(float sc, int k, int V, int tok) {
-  return ((unsigned long long)f2ord(sc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)(k * V + tok));
-}
+// the same top-P selection and finish with the same code, so they return the same bits wherever both can run.  (Their operands and
+// tables, the candidate key, the selection and the advance are step_dev.h's, shared with the stochastic beam search of sbs.hip.)
 
 // The Hamming diversity term of a group step: lp = logit - lse of a candidate with token tok, sel_tok[0, nprev) the
 // tokens the earlier groups of this user chose in this step.  fp32, one rounding per operation (no contraction into an FMA): the
@@ -323,57 +285,6 @@ __device__ __forceinline__ void flag_nonfinite_lse(const StepArgs& a, const Step
   }
 }
 
-// Only the best 2K candidates are looked at (topk(2K) in beam_search), in descending order: a bitonic TOP-P
-// selection, P = the power of two >= 2K.  Sort every P-block (directions alternating, as in a full bitonic sort
-// stopped at stage P), then halve the array round by round: a descending block followed by an ascending one is a
-// bitonic sequence, so the elementwise maxima of the pair are a bitonic block that holds the pair's P largest keys;
-// re-sort it (log2 P merge stages) and go on until one block is left.  ~3x fewer compare-exchanges than sorting
-// all NC keys; keys are unique (flat index in the low word), so the result is the full sort's prefix: keys[0, min(NC, P)) descending.
-// NC: a power of two, 64 <= NC <= MAXN.  Ends behind a barrier.
-template <int NTHR, int MAXN>
-__device__ __forceinline__ void top_p_select(unsigned long long* keys, int NC, int P, int tid) {
-  const int top = NC < P ? NC : P;
-  auto stage = [&](int n, int kk, int j) {
-    for (int i = tid; i < n; i += NTHR) {
-      const int ixj = i ^ j;
-      if (ixj > i) {
-        const unsigned long long a = keys[i], c = keys[ixj];
-        const bool desc = (i & kk) == 0;
-        if (desc ? (a < c) : (a > c)) {
-          keys[i] = c;
-          keys[ixj] = a;
-        }
-      }
-    }
-    gram_sync();
-  };
-  for (int kk = 2; kk <= top; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) stage(NC, kk, j);
-  for (int n = NC; n > P; n >>= 1) {
-    // blocks (2q, 2q+1) -> block q of the half-size array; every thread reads its pairs before anyone writes
-    const int half = n >> 1;
-    constexpr int NMX = MAXN / 2 / NTHR;  // half / NTHR <= MAXN / 2 / NTHR; statically indexed: stays in registers
-    unsigned long long mx[NMX];
-#pragma unroll
-    for (int c = 0; c < NMX; ++c) {
-      const int o = tid + c * NTHR;
-      if (o < half) {
-        const int q = o / P, i = o - q * P;
-        const unsigned long long a = keys[(2 * q) * P + i], b2 = keys[(2 * q + 1) * P + i];
-        mx[c] = a > b2 ? a : b2;
-      }
-    }
-    gram_sync();
-#pragma unroll
-    for (int c = 0; c < NMX; ++c) {
-      const int o = tid + c * NTHR;
-      if (o < half) keys[o] = mx[c];
-    }
-    gram_sync();
-    for (int j = P >> 1; j > 0; j >>= 1) stage(half, P, j);  // bitonic blocks -> sorted, directions alternating again
-  }
-}
-
 // Everything behind the selection: keys[0, min(C, 2K)) hold the user's best candidates in descending order (C = sh.C of them in
 // all).  BeamSearchScorer.process on one thread, then the sequences / ancestor table / per-row state are advanced through
 // new_seq [K][Tmax] / new_anc [Tmax][K] (LDS).  FILT: the zero keys of dead candidates sort last, so the ranking ends at the first
@@ -470,41 +381,6 @@ __device__ __forceinline__ void step_rank(const StepArgs& a, StepShared& sh, con
     }
   }
   gram_sync();
-}
-
-// advance sequences / ancestor table / per-row state of all K rows from sel_* (read old -> LDS -> write)
-template <int NTHR>
-__device__ __forceinline__ void step_advance(const StepArgs& a, const StepShared& sh, int* new_seq, int* new_anc, int b, int tid) {
-  const gram_beam_state_t& st = a.st;
-  const int K = st.K, T = st.Tmax, R = st.B * K, cur_len = a.cur_len;
-  const int row0 = b * K;
-  const int t = cur_len - 1;  // decode step whose K/V were just written
-  for (int idx = tid; idx < K * T; idx += NTHR) {
-    const int j = idx / T, p = idx - j * T;
-    int v = 0;
-    if (p < cur_len) v = st.seq[(size_t)(row0 + sh.sel_par[j]) * T + p];
-    else if (p == cur_len) v = sh.sel_tok[j];
-    new_seq[idx] = v;
-  }
-  for (int idx = tid; idx < T * K; idx += NTHR) {
-    const int p = idx / K, j = idx - p * K;
-    int v;
-    if (p < t) v = st.anc[(size_t)p * R + row0 + sh.sel_par[j]];
-    else if (p == t) v = a.rows_per_user == 1 ? b : row0 + sh.sel_par[j];  // compact step: slot t holds one row per user
-    else v = row0 + j;
-    new_anc[idx] = v;
-  }
-  gram_sync();
-  for (int idx = tid; idx < K * T; idx += NTHR) st.seq[(size_t)row0 * T + idx] = new_seq[idx];
-  for (int idx = tid; idx < T * K; idx += NTHR) {
-    const int p = idx / K, j = idx - p * K;
-    st.anc[(size_t)p * R + row0 + j] = new_anc[idx];
-  }
-  if (tid < K) {
-    st.beam_scores[row0 + tid] = sh.sel_score[tid];
-    st.tokens[row0 + tid] = sh.sel_tok[tid];
-    st.node[row0 + tid] = sh.sel_node[tid];
-  }
 }
 
 // the plain search: one group of K beams over the user's C = sh.C candidates

@@ -1223,6 +1223,98 @@ extern "C" int gram_sample_items(const gram_model_t* m, const int64_t* input_ids
                      sequences, seq_logprobs, sample_logprobs, width_host, stream);
 }
 
+// ---- sampling without replacement (gram_generate_sbs) --------------------------------------------------------------
+namespace {
+
+// Behind carve_sample's layout (whose two accumulators are phi and the model's log-probability here): the rows' path words and,
+// where a user's candidates exceed what the step holds on chip, 2 * max_fanout words per row instead of the sampling step's max_fanout.
+struct SbsScratch {
+  SampleScratch s;
+  uint64_t* path;  // [B * R]
+  int64_t bytes;
+};
+SbsScratch carve_sbs(Workspace& w, void* ws, int B, int R, int max_fanout) {
+  SbsScratch x{};
+  x.s = carve_sample(w, ws, B, R, /*max_fanout=*/0);
+  Carve cv(ws);
+  cv.off = x.s.bytes;
+  const int64_t rows = (int64_t)B * R;
+  x.path = cv.take<uint64_t>(rows);
+  if ((int64_t)R * max_fanout > gram_sbs_capacity()) {
+    w.beam.cand_logits_users = (int32_t)rows;
+    w.beam.cand_logits_stride = 2 * (int64_t)max_fanout;
+    w.beam.cand_logits = cv.take<float>(rows * 2 * max_fanout);
+  }
+  x.bytes = (cv.off + 255) & ~(int64_t)255;
+  return x;
+}
+
+// sample_body's train -- the same encode_call / decode_step / gram_lse_combine launches -- with the stochastic beam search's init,
+// step and finalize.  Rows are reordered, so the step advances the ancestor table as the beam search does.
+int sbs_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R, int max_length,
+             const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items, float temperature, uint64_t seed,
+             const int64_t* user_keys, void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs,
+             float* sample_logprobs, float* perturbed, int32_t* width_host, void* stream) {
+  TRY(check_shapes(m, B, N, L, R, max_length));
+  TRY(check_compaction(comp, B, N));
+  if (!trie || !user_keys || !sequences || !seq_logprobs || !sample_logprobs || !perturbed || !mask || (!comp && !input_ids) ||
+      trie->max_fanout > INT32_MAX / 2 || !sample_shape_ok(B, R, 2 * trie->max_fanout))
+    return GRAM_E_ARG;
+  if (!(temperature > 0.f) || !(temperature < 3.0e38f)) return GRAM_E_ARG;
+  Workspace w = carve(m, workspace, B, N, L, R, max_length);
+  const SbsScratch x = carve_sbs(w, workspace, B, R, trie->max_fanout);
+  if (!workspace || workspace_bytes < x.bytes) return GRAM_E_WORKSPACE;
+  memset(g_tail_last, 0, sizeof(g_tail_last));  // (gram_debug_tail_last speaks of the last generate call of any kind)
+  const gram_model_desc_t& c = m->d;
+  TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
+  TRY(gram_sbs_init(&w.beam, trie, /*decoder_start_token_id=*/0, seed, user_keys, x.s.sample_lp, x.s.model_lp, x.path, stream));
+  for (int t = 0; t + 1 < max_length; ++t) {
+    const int Kt = t == 0 ? 1 : R;
+    TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, Kt, B * R, max_length, t, nullptr, w.lse_part, nullptr, stream));
+    TRY(gram_lse_combine(w.lse_part, w.lse, B * Kt, c.vocab / 64, stream));
+    const void* const lm16 = w.pieces > 1 ? nullptr : c.lm_head_bf16;  // (the search step's operands: search_step)
+    if (items)
+      TRY(gram_sbs_step_items(&w.beam, trie, w.dec.h, lm16, c.lm_head_f32, c.d_model, w.lse, c.vocab, t + 1, Kt, w.pieces, temperature,
+                              seed, x.s.sample_lp, x.s.model_lp, x.path, items, stream));
+    else
+      TRY(gram_sbs_step(&w.beam, trie, w.dec.h, lm16, c.lm_head_f32, c.d_model, w.lse, c.vocab, t + 1, Kt, w.pieces, temperature, seed,
+                        x.s.sample_lp, x.s.model_lp, x.path, stream));
+  }
+  TRY(gram_sbs_finalize(&w.beam, max_length, x.s.model_lp, x.s.sample_lp, sequences, seq_logprobs, sample_logprobs, perturbed, w.width,
+                        stream));
+  return read_width_and_error(w, width_host, stream);
+}
+
+}  // namespace
+
+extern "C" int64_t gram_workspace_bytes_sbs(const gram_model_t* m, int B, int N, int L, int R, int max_length, int max_fanout) {
+  if (check_shapes(m, B, N, L, R, max_length) || max_fanout < 0 || max_fanout > INT32_MAX / 2 || !sample_shape_ok(B, R, 2 * max_fanout))
+    return GRAM_E_ARG;
+  Workspace w = carve(m, nullptr, B, N, L, R, max_length);
+  return carve_sbs(w, nullptr, B, R, max_fanout).bytes;
+}
+
+extern "C" int gram_generate_sbs(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R,
+                                 int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, float temperature, uint64_t seed,
+                                 const int64_t* user_keys, void* workspace, int64_t workspace_bytes, int64_t* sequences,
+                                 float* seq_logprobs, float* sample_logprobs, float* perturbed_scores, int32_t* width_host,
+                                 void* stream) {
+  return sbs_call(m, input_ids, mask, B, N, L, R, max_length, trie, comp, nullptr, temperature, seed, user_keys, workspace,
+                  workspace_bytes, sequences, seq_logprobs, sample_logprobs, perturbed_scores, width_host, stream);
+}
+
+extern "C" int gram_generate_sbs_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R,
+                                       int max_length, const gram_trie_t* trie, const gram_compaction_t* comp,
+                                       const gram_user_items_t* items, float temperature, uint64_t seed, const int64_t* user_keys,
+                                       void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs,
+                                       float* sample_logprobs, float* perturbed_scores, int32_t* width_host, void* stream) {
+  if (!items || !items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
+      items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW))
+    return GRAM_E_ARG;
+  return sbs_call(m, input_ids, mask, B, N, L, R, max_length, trie, comp, items, temperature, seed, user_keys, workspace, workspace_bytes,
+                  sequences, seq_logprobs, sample_logprobs, perturbed_scores, width_host, stream);
+}
+
 // ---- teacher-forced decoder pass (gram_teacher_forced) -----------------------------------------------------------------------------
 namespace {
 

@@ -1202,7 +1202,8 @@ class GRAM(nn.Module):
     def generate(self, input_ids, attention_mask, max_length, prefix_allowed_tokens_fn=None, num_beams=1,
                  num_return_sequences=None, output_scores=True, return_dict_in_generate=True, length_penalty=1.0,
                  exclude_items=None, allowed_items=None, candidates=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
-                 uniforms=None, generator=None, num_beam_groups=1, diversity_penalty=0.0, **unused):
+                 uniforms=None, generator=None, num_beam_groups=1, diversity_penalty=0.0, replacement=True, seed=None,
+                 user_keys=None, **unused):
         """GRAM.generate (gram.py:74-107) with the kwargs single_runner_gram.py:641-651 passes.
 
         input_ids (B,N,L) int64, attention_mask (B,N,L) bool on the model's device.  Returns a
@@ -1229,6 +1230,21 @@ class GRAM(nn.Module):
         drawn from.  ``exclude_items`` / ``allowed_items`` work as for beam search.  A row's draw depends on its user, its uniforms and
         the parameters only, not on the batch or on R.  Without ``do_sample`` the five sampling arguments are ignored, as before.
 
+        Sampling WITHOUT replacement: ``do_sample=True, replacement=False`` returns ``num_return_sequences`` = R <= 64 DISTINCT items
+        per user, in the order of sampling without replacement (Plackett-Luce) from p(item | user) restricted to the Trie at
+        ``temperature`` -- stochastic beam search (Kool et al. 2019): a slate for exploration traffic,
+        negatives, or importance-weighted estimators over the catalogue.  ``top_k`` (other than None / 0 / the default 50, which is
+        not applied) and ``top_p`` < 1 are a ``NotImplementedError`` -- truncation together with exact without-replacement sampling
+        is not defined here -- and ``uniforms=`` is a ``ValueError``: the randomness is counter-based, a function of ``seed`` (an
+        int; without it one int64 is drawn from ``generator`` or the global torch RNG on the CPU), the user's entry of ``user_keys``
+        ((B,) int64, default ``arange(B)``) and the token prefix.  Pass STABLE user ids as ``user_keys``: a user's draw then does not
+        depend on its place in the batch, on the batch's other users or on R (the rows of R' < R are the first R' rows of R).
+        Returns ``sequences`` (B*R, width) user-major, largest perturbed score first, ``sequences_scores=None``,
+        ``sequence_logprobs`` (the model's, as above), ``sample_logprobs`` (each item's log-probability under the Trie-renormalised
+        distribution) and ``perturbed_scores`` (its Gumbel-perturbed log-probability G; the R-th largest is the threshold of the
+        importance weights).  A user with fewer than R items (``exclude_items`` / ``allowed_items`` work as for sampling) gets rows
+        of the start token followed by padding with -inf in all three, and no error.
+
         Group (diverse) beam search: ``num_beam_groups`` = G > 1, a divisor of ``num_beams``, with ``diversity_penalty`` >= 0 -- HF
         4.26's ``group_beam_search`` with the Hamming diversity penalty: the beams are G groups searched one
         after the other in every step, and a token costs a group ``diversity_penalty`` for every beam of the earlier groups that
@@ -1249,7 +1265,12 @@ class GRAM(nn.Module):
         else:  # (every refusal of the group search, before anything touches the device)
             lam = self._group_args(int(num_beams), G, diversity_penalty, do_sample, prefix_allowed_tokens_fn, num_return_sequences)
         if not do_sample:  # (greedy and beam search ignore the sampling arguments, by name as they always did)
-            unused = dict(unused, **{k: v for k, v in (("uniforms", uniforms), ("generator", generator)) if v is not None})
+            unused = dict(unused, **{k: v for k, v in (("uniforms", uniforms), ("generator", generator), ("seed", seed),
+                                                       ("user_keys", user_keys)) if v is not None})
+            if not replacement:
+                unused = dict(unused, replacement=replacement)
+        elif replacement:
+            unused = dict(unused, **{k: v for k, v in (("seed", seed), ("user_keys", user_keys)) if v is not None})
         for k, v in unused.items():
             if k in neutral:
                 if v is not None and v != neutral[k] and k not in ("temperature", "top_k", "top_p"):
@@ -1263,6 +1284,8 @@ class GRAM(nn.Module):
         if do_sample:  # (every refusal of the sampling path, before anything touches the device)
             sampling = self._sample_args(input_ids.shape[0], int(max_length), num_beams, num_return_sequences, temperature, top_k, top_p,
                                          uniforms, prefix_allowed_tokens_fn)
+            if not replacement:
+                seed, user_keys = self._distinct_args(input_ids.shape[0], top_k, top_p, uniforms, seed, user_keys, generator)
         self._check_passage_len(input_ids.shape[-1])
         self._check_fused_len(input_ids.shape[1], input_ids.shape[2])
         handle = self._pack()
@@ -1297,6 +1320,29 @@ class GRAM(nn.Module):
             items = self._user_item_lists(allowed_items if allow else exclude_items, allow, B, flat, candidates, dev)
         comp, harvest_plan = self._plan(ids, mask, B, N, Lp)
         _ctrie, (t_off, t_tok, t_node) = flat.to_device(dev)
+        if do_sample and not replacement:
+            # stochastic beam search: ONE custom op over the C ABI (gram_amd/ops.py -> gram_generate_sbs / gram_generate_sbs_items)
+            R, tau = sampling[:2]
+            need = int(lib.gram_workspace_bytes_sbs(handle, B, N, Lp, R, int(max_length), int(flat.max_fanout)))
+            if need < 0:
+                raise _lib.GramHipError(f"unsupported problem size B={B} N={N} L={Lp} num_return_sequences={R} max_length={max_length}")
+            ws = self._ensure_workspace(need)
+            from .. import ops as _ops  # noqa: F401  (registers torch.ops.gram.*)
+            args = (ids, mask, int(handle), ws, t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len), R, int(max_length),
+                    tau, seed, user_keys.to(dev).contiguous(), *self._comp_args(comp))
+            if filtered:
+                leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
+                out = torch.ops.gram.sample_distinct_items(*args, leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items, allow)
+            else:
+                out = torch.ops.gram.sample_distinct(*args)
+            seqs, model_lp, sample_lp, perturbed, width = out
+            if harvest_plan is not None:
+                self._harvest_from_workspace(harvest_plan, ws, handle, B, N, Lp, R, int(max_length))
+            seqs = seqs[:, : int(width[0])]
+            if not return_dict_in_generate:
+                return seqs
+            return GenerateOutput(sequences=seqs, sequences_scores=None, sequence_logprobs=model_lp, sample_logprobs=sample_lp,
+                                  perturbed_scores=perturbed)
         if do_sample:
             # HF's sample on the Trie: ONE custom op over the C ABI (gram_amd/ops.py -> gram_sample / gram_sample_items)
             R, tau, k_top, p_top = sampling
@@ -1404,6 +1450,29 @@ class GRAM(nn.Module):
                 raise ValueError(f"generate(do_sample=True): uniforms must be a float32 tensor of shape {want} = (B, "
                                  f"num_return_sequences, max_length - 1), got {got}")
         return R, tau, k_top, p_top
+
+    @staticmethod
+    def _distinct_args(B: int, top_k, top_p, uniforms, seed, user_keys, generator):
+        """What ``generate(do_sample=True, replacement=False)`` asks beyond ``_sample_args``, as (seed in [-2^63, 2^63), user_keys int64
+        (B,) on the CPU), or the refusal: everything is checked on the host."""
+        what = "generate(do_sample=True, replacement=False)"
+        if uniforms is not None:
+            raise ValueError(f"{what} takes no uniforms: its randomness is counter-based, pass seed= (and user_keys=)")
+        if top_k not in (None, 0, 50) or float(top_p) != 1.0:
+            raise NotImplementedError(f"{what}: top_k / top_p truncation together with exact sampling without replacement is not "
+                                      f"defined here (got top_k={top_k!r}, top_p={top_p!r}); leave them at their defaults")
+        if seed is None:
+            seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device="cpu",
+                                     generator=generator if generator is not None and generator.device.type == "cpu" else None))
+        elif isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"{what}: seed must be an int (got {seed!r})")
+        seed = (int(seed) + 2 ** 63) % 2 ** 64 - 2 ** 63  # (the 64-bit Philox key, as a signed word)
+        if user_keys is None:
+            user_keys = torch.arange(B, dtype=torch.int64)
+        elif (not isinstance(user_keys, torch.Tensor) or user_keys.dtype != torch.int64 or tuple(user_keys.shape) != (B,)):
+            got = (tuple(user_keys.shape), user_keys.dtype) if isinstance(user_keys, torch.Tensor) else type(user_keys).__name__
+            raise ValueError(f"{what}: user_keys must be an int64 tensor of shape ({B},) = (B,), got {got}")
+        return seed, user_keys.detach()
 
     @staticmethod
     def _user_item_lists(lists, allow: bool, B: int, flat: FlatTrie, candidates, device="cpu") -> torch.Tensor:

@@ -13,6 +13,9 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
     torch.ops.gram.sample            Trie-constrained sampling, R draws per user with their log-probabilities (gram_sample) --
                                      ``GRAM.generate(do_sample=True)``
     torch.ops.gram.sample_items      the same with per-user item filters (gram_user_items_prepare + gram_sample_items)
+    torch.ops.gram.sample_distinct   sampling WITHOUT replacement, R distinct items per user (stochastic beam search, gram_generate_sbs)
+                                     -- ``GRAM.generate(do_sample=True, replacement=False)``
+    torch.ops.gram.sample_distinct_items  the same with per-user item filters (gram_user_items_prepare + gram_generate_sbs_items)
     torch.ops.gram.teacher_forced    the teacher-forced decoder pass (gram_teacher_forced) -- ``GRAM.forward(labels=...)`` and
                                      ``GRAM.score_sequences``
     torch.ops.gram.teacher_forced_attn  the same pass with its cross-attention probabilities (gram_teacher_forced_ex) --
@@ -355,6 +358,94 @@ def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_t
       num_return_sequences, max_length, temperature, top_k, top_p, uniforms, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
       cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
     return _sample_fake(input_ids, num_return_sequences, max_length)
+
+
+# ---------------------------------------------------------------------------------------------- sampling without replacement
+def _sample_distinct(fn, what: str, input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie: _lib.Trie,
+                     comp: Optional[_lib.Compaction], num_return_sequences: int, max_length: int, temperature: float, seed: int,
+                     user_keys: Tensor, *extra) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The checks, the outputs and the C call ``fn`` (gram_generate_sbs, or gram_generate_sbs_items with its lists in ``extra``) of
+    the two ``sample_distinct`` ops, and their return value."""
+    if input_ids.dim() != 3:
+        raise ValueError(f"{what}: input_ids must be (B, N, L)")
+    B, N, L = input_ids.shape
+    R, dev = num_return_sequences, input_ids.device
+    if not 1 <= R <= _lib.GRAM_MAX_BEAMS or not 2 <= max_length <= _lib.GRAM_MAX_DEC_LEN:
+        raise ValueError(f"{what}: need 1 <= num_return_sequences <= {_lib.GRAM_MAX_BEAMS} and 2 <= max_length <= {_lib.GRAM_MAX_DEC_LEN}")
+    if not 0 < temperature < float("inf"):
+        raise ValueError(f"{what}: need a finite temperature > 0")
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    _check("user_keys", user_keys, torch.int64, (B,), dev)
+    seqs = torch.empty(B * R, max_length, dtype=torch.int64, device=dev)
+    model_lp, sample_lp, perturbed = (torch.empty(B * R, dtype=torch.float32, device=dev) for _ in range(3))
+    width = C.c_int32(0)
+    with torch.cuda.device(dev):
+        rc = fn(handle, input_ids.data_ptr(), attention_mask.data_ptr(), B, N, L, R, max_length, C.byref(trie), _ref(comp), *extra,
+                float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, user_keys.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                seqs.data_ptr(), model_lp.data_ptr(), sample_lp.data_ptr(), perturbed.data_ptr(), C.byref(width), _stream(input_ids))
+    _lib.check(rc, what)
+    return seqs, model_lp, sample_lp, perturbed, torch.tensor([width.value], dtype=torch.int32)
+
+
+def _sample_distinct_fake(input_ids, num_return_sequences, max_length):
+    rows = input_ids.shape[0] * num_return_sequences
+    f = dict(dtype=torch.float32)
+    return (input_ids.new_empty(rows, max_length), input_ids.new_empty(rows, **f), input_ids.new_empty(rows, **f),
+            input_ids.new_empty(rows, **f), torch.empty(1, dtype=torch.int32))
+
+
+@torch.library.custom_op("gram::sample_distinct", mutates_args=("workspace",), device_types="cuda")
+def sample_distinct(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                    trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int,
+                    num_return_sequences: int, max_length: int, temperature: float, seed: int, user_keys: Tensor,
+                    comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor],
+                    cache_x: Optional[Tensor], n_cached: int, cache_L: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Sampling without replacement on the Trie, stochastic beam search (gram_generate_sbs): R = num_return_sequences DISTINCT items per
+    user in Plackett-Luce order.  input_ids / attention_mask / handle / the Trie / comp_* / cache_* as ``generate``; ``workspace`` a u8
+    scratch tensor of gram_workspace_bytes_sbs; temperature > 0; ``seed`` the 64-bit Philox key (taken modulo 2^64); user_keys i64 (B,):
+    a user's draw depends on (seed, its key, the model's logits) only.  Returns (sequences i64 (B*R, max_length) user-major in
+    descending order of the perturbed score, the model's log-probability of each row f32 (B*R), its log-probability under the
+    Trie-renormalised distribution f32 (B*R), its perturbed score f32 (B*R), width i32 (1,)); a user with fewer than R items gets rows
+    of the start token and padding with -inf in all three."""
+    for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),))):
+        _check(name, t, torch.int32, shape, input_ids.device)
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
+    return _sample_distinct(_lib.load().gram_generate_sbs, "gram_generate_sbs", input_ids, attention_mask, handle, workspace, trie, comp,
+                            num_return_sequences, max_length, temperature, seed, user_keys)
+
+
+@sample_distinct.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len,
+      num_return_sequences, max_length, temperature, seed, user_keys, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
+      cache_L):
+    return _sample_distinct_fake(input_ids, num_return_sequences, max_length)
+
+
+@torch.library.custom_op("gram::sample_distinct_items", mutates_args=("workspace",), device_types="cuda")
+def sample_distinct_items(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                          trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int,
+                          num_return_sequences: int, max_length: int, temperature: float, seed: int, user_keys: Tensor,
+                          comp_map: Optional[Tensor], comp_ids: Optional[Tensor], comp_mask: Optional[Tensor],
+                          cache_slot: Optional[Tensor], cache_x: Optional[Tensor], n_cached: int, cache_L: int, leaf_lo: Tensor,
+                          leaf_hi: Tensor, item_rank: Tensor, items: Tensor,
+                          allow: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``sample_distinct`` (same inputs, same outputs) with every user drawing from its own view of the Trie: the lists of
+    ``generate_items`` (leaf_lo / leaf_hi / item_rank / items / allow), prepared the same way, then gram_generate_sbs_items."""
+    trie, comp, ui, _keep = _user_items("sample_distinct_items", input_ids, attention_mask, trie_child_off, trie_child_tok,
+                                        trie_child_node, trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot,
+                                        cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
+    return _sample_distinct(_lib.load().gram_generate_sbs_items, "gram_generate_sbs_items", input_ids, attention_mask, handle, workspace,
+                            trie, comp, num_return_sequences, max_length, temperature, seed, user_keys, C.byref(ui))
+
+
+@sample_distinct_items.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len,
+      num_return_sequences, max_length, temperature, seed, user_keys, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
+      cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
+    return _sample_distinct_fake(input_ids, num_return_sequences, max_length)
 
 
 # ---------------------------------------------------------------------------------------------- teacher-forced pass

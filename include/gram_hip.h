@@ -707,6 +707,64 @@ int gram_sample_items(const gram_model_t* m, const int64_t* input_ids, const uin
                       const gram_sample_params_t* params_host, const float* uniforms, void* workspace, int64_t workspace_bytes,
                       int64_t* sequences, float* seq_logprobs, float* sample_logprobs, int32_t* width_host, void* stream);
 
+/* ---- Sampling without replacement: stochastic beam search (Kool, van Hoof, Welling, ICML 2019) on a Trie ------------
+ * R DISTINCT items per user, in the order of sampling without replacement (Plackett-Luce) from the distribution gram_sample draws from
+ * with top_k and top_p off: p(child) = softmax over the row's (alive) children of y = z / temperature.  The state is a
+ * gram_beam_state_t with K = R rows per user; rows ARE reordered, as in beam search.  Per row, beside the state's own arrays:
+ *   beam_scores[row]  G, the perturbed score (-inf: a dead row);      hyp_len[row] (row < B * R) > 0: finished at that length;
+ *   sample_logprob    phi, the log-probability of the prefix under that distribution;      model_logprob   sum of z - lse[row];
+ *   path              a 64-bit word that names the prefix to the random number generator.
+ * Uniforms are Philox4x32-10 words with key (seed low word, seed high word): root w = philox(user_key low, user_key high, 0, 0),
+ * path = (w0, w1), u = ((w2 >> 8) + 0.5) 2^-24, phi = 0, G = -log(-log u); the child with token tok chosen at the step that writes
+ * position cur_len: w = philox(path low, path high, tok, cur_len), path = (w0, w1), u from w2.  So a draw depends on (seed, user key,
+ * token prefix) only.  One step, for every live row (G = T) over its alive children in token order, fp32:
+ *   lse_k = log sum exp y;  phi_c = phi + (y_c - lse_k);  G~_c = phi_c - log(-log u_c);  Z = max_c G~_c;
+ *   v = (T - G~_c) + log1p(-exp(G~_c - Z));  G_c = (T - max(0, v)) - log1p(exp(-|v|)), and G_c = T exactly where G~_c = Z.
+ * A finished row is one candidate, itself; a dead row none.  The R candidates with the largest G become the new rows in descending
+ * order of G (ties: the lower row * V + token); sequences, ancestors, node and the four words move with them; a row that takes EOS is
+ * finished; fewer than R candidates leave dead rows (no error).  The sum's order is fixed by a row's own alive children (sbs.hip), so
+ * a user's rows do not depend on B, on the other users or on where the candidates are held, and the rows of R' < R are the first R'
+ * rows of R.  Non-finite logits, lse or scores are error 4. */
+/* gram_beam_init, then the root words: row 0 of every user live, the others dead.  user_keys i64 [B] (device). */
+int gram_sbs_init(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, int start_token, uint64_t seed,
+                  const int64_t* user_keys, float* sample_logprob, float* model_logprob, uint64_t* path, void* stream);
+/* One step (cur_len = tokens already in each row); operands as gram_sample_step.  rows_per_user = R, or 1 at step 0 (hidden and lse
+ * hold one row per user).  A user's candidates are held on chip up to 4 096 of them; where R * max_fanout exceeds
+ * gram_sbs_capacity() st->cand_logits must hold f32 [B * R][cand_logits_stride >= 2 * max_fanout] (GRAM_E_ARG otherwise) -- the same
+ * results bit for bit. */
+int gram_sbs_step(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16, const void* lm_head_bf16,
+                  const float* lm_head_f32, int d, const float* lse, int V, int cur_len, int rows_per_user, int pieces,
+                  float temperature, uint64_t seed, float* sample_logprob, float* model_logprob, uint64_t* path, void* stream);
+/* gram_sbs_step with per-user item filters: bit for bit the unfiltered step on the Trie of the user's alive items. */
+int gram_sbs_step_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
+                        const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                        int rows_per_user, int pieces, float temperature, uint64_t seed, float* sample_logprob, float* model_logprob,
+                        uint64_t* path, const gram_user_items_t* items_host, void* stream);
+/* sequences i64 [B * R][max_length], seq_logprobs (model), sample_logprobs (phi), perturbed_scores (G) f32 [B * R]; a dead row is the
+ * start token followed by pad with -inf in all three; NaN / +inf anywhere is error 4; *out_width as gram_sample_finalize. */
+int gram_sbs_finalize(const gram_beam_state_t* st_host, int max_length, const float* model_logprob, const float* sample_logprob,
+                      int64_t* sequences, float* seq_logprobs, float* sample_logprobs, float* perturbed_scores, int32_t* out_width,
+                      void* stream);
+/* Candidates of a user the step holds on chip (4 096, or what gram_debug_set_sbs_capacity lowered it to). */
+int gram_sbs_capacity(void);
+/* TEST hook: lowers that capacity (0 = the default).  Results do not depend on it.  Process-wide. */
+int gram_debug_set_sbs_capacity(int candidates);
+/* Bytes of scratch gram_generate_sbs needs: gram_workspace_bytes(m, B, N, L, R, max_length) plus, behind it, the three per-row arrays
+ * and, where R * max_fanout exceeds gram_sbs_capacity(), the streamed candidates [B * R][2 * max_fanout]. */
+int64_t gram_workspace_bytes_sbs(const gram_model_t* m, int B, int N, int L, int R, int max_length, int max_fanout);
+/* generate(do_sample=True, replacement=False, num_return_sequences=R): gram_sample's launch train with gram_sbs_init / gram_sbs_step /
+ * gram_sbs_finalize in the sampling step's place (step 0 on one decoder row per user; finished and dead rows keep being decoded). */
+int gram_generate_sbs(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R, int max_length,
+                      const gram_trie_t* trie_host, const gram_compaction_t* compaction_host, float temperature, uint64_t seed,
+                      const int64_t* user_keys, void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs,
+                      float* sample_logprobs, float* perturbed_scores, int32_t* width_host, void* stream);
+/* gram_generate_sbs with per-user item filters (as gram_generate_items). */
+int gram_generate_sbs_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int R,
+                            int max_length, const gram_trie_t* trie_host, const gram_compaction_t* compaction_host,
+                            const gram_user_items_t* items_host, float temperature, uint64_t seed, const int64_t* user_keys,
+                            void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs, float* sample_logprobs,
+                            float* perturbed_scores, int32_t* width_host, void* stream);
+
 /* ---- the tail pass: the chain-like lower levels of the Trie decoded in one pass per user forest ---------------------
  * Once a user's beams stand on prefixes of length d_tail (start token counted), every decoder state the remaining search steps can
  * ask for belongs to a known forest: the beams' nodes and their descendants that have children.  gram_generate_tail builds that

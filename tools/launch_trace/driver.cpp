@@ -23,7 +23,7 @@ T* fake() {
   return (T*)g_next;
 }
 
-enum Entry { GENERATE, ENCODE_FUSED, ENCODE_PASSAGES, DECODE_STEP, TEACHER_FORCED, SCORE_TRIE };
+enum Entry { GENERATE, ENCODE_FUSED, ENCODE_PASSAGES, DECODE_STEP, TEACHER_FORCED, SCORE_TRIE, SBS };
 enum Live { OFF, NONE, SOME, ALL };  // live rows off, or on with gram_live_rows reporting no row, some rows, every row
 struct Case {
   const char* name;
@@ -115,6 +115,11 @@ const Case kCases[] = {
     {"generate_tail_forest_cut", GENERATE, 2, 1, 2, 3, 32, 4, 3, SOME, false, false, false, false, 0, false, 0, 0, 11, 1},
     // gram_generate_groups (2 groups of 2 beams): the train of generate_p2 with the group init and the group step in the search's place
     {"generate_groups_p2", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 0, 0, 2},
+    // gram_generate_sbs / gram_generate_sbs_items (K = 4 rows per user): the encoder and the decode steps of generate_live_off with
+    // the stochastic beam search's init, step and finalize in the search's place, step 0 on one decoder row per user; the three
+    // per-row arrays lie behind gram_workspace_bytes
+    {"generate_sbs_p2", SBS, 2, 1, 2, 3, 32, 4, 4},
+    {"generate_sbs_p1_items", SBS, 1, 1, 2, 3, 32, 4, 4, OFF, false, false, false, false, 0, true},
 };
 
 gram_model_t* make_model(int pieces, int fold, int max_passages) {
@@ -173,6 +178,10 @@ int run(const Case& c) {
     g_ws_bytes = gram_workspace_bytes_trie(m, B, N, L, K * T);
     trace_line("gram_workspace_bytes_trie", g_ws_bytes);
   }
+  if (c.entry == SBS) {
+    g_ws_bytes = gram_workspace_bytes_sbs(m, B, N, L, K, T, trie.max_fanout);
+    trace_line("gram_workspace_bytes_sbs", g_ws_bytes);
+  }
   gram_trie_tail_t tail{nullptr, 2, 2};
   if (c.tail_rows) {
     tail.sub_rows = fake<int32_t>();  // (only here: the other cases' fake addresses stay what their goldens recorded)
@@ -203,6 +212,18 @@ int run(const Case& c) {
                                   (int64_t*)io[0], (float*)io[1], &width, st);
       return gram_generate_ex(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, g_ws, g_ws_bytes, (int64_t*)io[0],
                               (float*)io[1], &width, st);
+    case SBS: {
+      const int64_t* user_keys = fake<int64_t>();  // (only here: the other cases' fake addresses stay what their goldens recorded)
+      float* perturbed = fake<float>();
+      const uint64_t seed = 0x0123456789abcdefull;
+      if (c.items) {
+        const gram_user_items_t items{fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), 64, GRAM_ITEMS_EXCLUDE};
+        return gram_generate_sbs_items(m, ids, mask, B, N, L, K, T, &trie, c.comp ? &comp : nullptr, &items, 0.5f, seed, user_keys, g_ws,
+                                       g_ws_bytes, (int64_t*)io[0], (float*)io[1], (float*)io[2], perturbed, &width, st);
+      }
+      return gram_generate_sbs(m, ids, mask, B, N, L, K, T, &trie, c.comp ? &comp : nullptr, 0.5f, seed, user_keys, g_ws, g_ws_bytes,
+                               (int64_t*)io[0], (float*)io[1], (float*)io[2], perturbed, &width, st);
+    }
     case ENCODE_FUSED:
       return gram_encode_fused(m, ids, mask, B, N, L, g_ws, g_ws_bytes, K, T, io[0], st);
     case ENCODE_PASSAGES:

@@ -240,6 +240,26 @@ int gram_sample_finalize(const gram_beam_state_t* s, int max_length, const float
                          float* seq_logprobs, float* sample_logprobs, int32_t* width, void* st) {
   REC(s, max_length, model_lp, sample_lp, sequences, seq_logprobs, sample_logprobs, width, st);
 }
+int gram_sbs_capacity(void) { return 4096; }  // the product default (a query, not a launch -- nothing recorded)
+int gram_sbs_init(const gram_beam_state_t* s, const gram_trie_t* trie, int start, uint64_t seed, const int64_t* user_keys, float* sample_lp,
+                  float* model_lp, uint64_t* path, void* st) {
+  REC(s, trie, start, (int64_t)seed, user_keys, sample_lp, model_lp, path, st);
+}
+int gram_sbs_step(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, const float* lm32, int d,
+                  const float* lse, int V, int cur_len, int rows_per_user, int pieces, float temperature, uint64_t seed, float* sample_lp,
+                  float* model_lp, uint64_t* path, void* st) {
+  REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, pieces, temperature, (int64_t)seed, sample_lp, model_lp, path, st);
+}
+int gram_sbs_step_items(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, const float* lm32, int d,
+                        const float* lse, int V, int cur_len, int rows_per_user, int pieces, float temperature, uint64_t seed,
+                        float* sample_lp, float* model_lp, uint64_t* path, const gram_user_items_t* items, void* st) {
+  REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, pieces, temperature, (int64_t)seed, sample_lp, model_lp, path, items,
+      st);
+}
+int gram_sbs_finalize(const gram_beam_state_t* s, int max_length, const float* model_lp, const float* sample_lp, int64_t* sequences,
+                      float* seq_logprobs, float* sample_logprobs, float* perturbed, int32_t* width, void* st) {
+  REC(s, max_length, model_lp, sample_lp, sequences, seq_logprobs, sample_logprobs, perturbed, width, st);
+}
 int gram_live_rows(const gram_beam_state_t* s, const gram_trie_t* trie, const gram_live_rows_t* out, void* st) {
   // the scripted counts of this call: {live rows, users owning one}, two entries of g_live_script per call
   for (int i = 0; i < 2; ++i) {
