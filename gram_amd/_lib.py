@@ -289,6 +289,14 @@ SIGNATURES = {
                                                vp, C.c_int, C.c_int, f32, C.POINTER(UserItems), vp]),
     "gram_generate_groups": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
                                        C.POINTER(Compaction), C.c_int, f32, C.POINTER(UserItems), vp, i64, vp, vp, C.POINTER(i32), vp]),
+    # beam search with per-item score biases
+    "gram_item_bias_table": (C.c_int, [vp, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.POINTER(Trie), C.c_int, C.c_int, vp, vp]),
+    "gram_beam_step_bias": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, C.c_int, C.c_int, C.c_int, vp, i64,
+                                      C.POINTER(UserItems), vp]),
+    "gram_beam_step_bias_sparse": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                             vp, C.c_int, vp, i64, C.POINTER(UserItems), vp]),
+    "gram_generate_bias": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
+                                     C.POINTER(Compaction), vp, i64, C.POINTER(UserItems), vp, i64, vp, vp, C.POINTER(i32), vp]),
     # Trie-constrained sampling
     "gram_sample_step": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(SampleParams), vp, C.c_int, vp, vp, vp]),

@@ -110,7 +110,9 @@ __device__ __forceinline__ float diversity(const StepArgs& a, const StepShared& 
 
 // per beam: first child edge, child count, hidden-state row; then the prefix sums of the counts: candidate ci of the user is child
 // ci - pre[k] of beam k, pre[k] <= ci < pre[k + 1].  nc_max > 0: more candidates than that is error 2 (the one-shot kernel's key array)
-__device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, int b, int tid, int nc_max) {
+// BIAS: the potential of every beam's own node goes to par[k] (0 for a beam that left the Trie: it has no candidates)
+template <bool BIAS = false>
+__device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, int b, int tid, int nc_max, float* par = nullptr) {
   const gram_beam_state_t& st = a.st;
   const gram_trie_t& tr = a.tr;
   const int K = st.K, row0 = b * K;
@@ -126,6 +128,7 @@ __device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, in
     sh.off[tid] = o0;
     sh.cnt[tid] = cnt;
     sh.lr[tid] = a.rowpos ? a.rowpos[row0 + tid] : row0 + tid;  // live-row step: hidden/lse are indexed by compact row
+    if constexpr (BIAS) par[tid] = nd >= 0 ? a.phi[(size_t)b * a.phi_stride + nd] : 0.f;
     if (tid == 0) sh.isdone = done;
   }
   gram_sync();
@@ -153,7 +156,8 @@ __device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, in
 // FILT: a candidate whose child node is not alive for the user gets the zero key ("nothing", below every real key) and no dot product;
 // the shared step-0 row computes every child's logit and leaves the test to shared0_keys.
 // GRP (the group step): the diversity term over the nprev tokens chosen so far goes between the log-probability and the beam score.
-template <int NTHR, bool FILT, bool GRP = false>
+// BIAS (the biased step): the edge term (edge_bias, step_dev.h) goes there instead.
+template <int NTHR, bool FILT, bool GRP = false, bool BIAS = false>
 __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, float* s_log, int b, int tid,
                                               int c0, int n, bool shared0, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
@@ -207,6 +211,10 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
         } else {
           float sc;
           if constexpr (GRP) sc = diversity(a, sh, nprev, tok2[w], acc2[w] - a.lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
+          else if constexpr (BIAS)
+            sc = dead2[w] ? 0.f
+                          : __fadd_rn(edge_bias(a, b, k2[w], sh.off[k2[w]] + (c0 + i2[w] - sh.pre[k2[w]]), acc2[w] - a.lse[lr2[w]]),
+                                      st.beam_scores[row0 + k2[w]]);
           else sc = (acc2[w] - a.lse[lr2[w]]) + st.beam_scores[row0 + k2[w]];
           kw[i2[w]] = dead2[w] ? 0ull : cand_key(sc, k2[w], V, tok2[w]);
         }
@@ -218,7 +226,7 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
 // step 0's shared row: the keys of beams [k0, k0 + kg) x children [j0, j0 + nj) of the shared node, from the nj logits that
 // sparse_window left in s_log: kw[(k - k0) * nj + (j - j0)].  (k0 = j0 = 0, kg = K, nj = the node's fan-out: the user's whole list
 // in its flat-index order)
-template <int NTHR, bool FILT, bool GRP = false>
+template <int NTHR, bool FILT, bool GRP = false, bool BIAS = false>
 __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared& sh, unsigned long long* kw, const float* s_log, int b,
                                              int tid, int j0, int nj, int k0, int kg, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
@@ -232,13 +240,14 @@ __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared
     const int tok = tr.child_tok[off0 + j0 + jj];
     float sc;
     if constexpr (GRP) sc = diversity(a, sh, nprev, tok, s_log[jj] - a.lse[b]) + st.beam_scores[row0 + k];
+    else if constexpr (BIAS) sc = __fadd_rn(edge_bias(a, b, k, off0 + j0 + jj, s_log[jj] - a.lse[b]), st.beam_scores[row0 + k]);
     else sc = (s_log[jj] - a.lse[b]) + st.beam_scores[row0 + k];
     kw[i] = child_alive<FILT>(a, b, off0 + j0 + jj) ? cand_key(sc, k, a.V, tok) : 0ull;
   }
 }
 
 // DENSE mode, gather: log_softmax at the allowed tokens + running beam score.  Candidates [c0, c0 + n) -> kw[0, n); kw[n, npad) = 0
-template <int NTHR, bool FILT, bool GRP = false>
+template <int NTHR, bool FILT, bool GRP = false, bool BIAS = false>
 __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, int b, int tid, int c0, int n,
                                              int npad, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
@@ -257,6 +266,7 @@ __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared
       const int lr = a.rows_per_user == 1 ? b : r;
       float sc;
       if constexpr (GRP) sc = diversity(a, sh, nprev, tok, a.logits[(size_t)lr * V + tok] - a.lse[lr]) + st.beam_scores[r];
+      else if constexpr (BIAS) sc = __fadd_rn(edge_bias(a, b, k, e, a.logits[(size_t)lr * V + tok] - a.lse[lr]), st.beam_scores[r]);
       else sc = (a.logits[(size_t)lr * V + tok] - a.lse[lr]) + st.beam_scores[r];
       key = child_alive<FILT>(a, b, e) ? cand_key(sc, k, V, tok) : 0ull;
     }
@@ -396,14 +406,14 @@ constexpr int kOneShotMaxKeys = 16384;  // K * max_fanout the one-shot kernel ta
 // ONE-SHOT form: all of a user's candidates in LDS at once (K * max_fanout <= 16 384 and the LDS sum below within the CU's 160 KB).
 // NTHR threads per workgroup (= per user): 256 for batches that fill the chip with workgroups; 1 024 for small batches, where one user's
 // sparse logits (a trip computes NTHR / 4 candidates' dot products, each on its 8 lanes) and sort stages are the step's latency.
-// UI: the per-user item filter (filtered(), above)
+// UI: the per-user item filter (filtered(), above) and / or the biased step's potentials (StepBias, step_dev.h: BIAS)
 template <int NTHR, typename... UI>
 __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
                                                         const float* __restrict__ lse, int V, int cur_len, int nc_max, int rows_per_user,
                                                         const p16* __restrict__ hd, const p16* __restrict__ emb, int d,
                                                         const int32_t* __restrict__ rowpos, int pieces,
                                                         const float* __restrict__ emb32, const float* __restrict__ pre, UI... ui) {
-  constexpr bool FILT = filtered<UI...>();
+  constexpr bool FILT = filtered<UI...>(), BIAS = biased<UI...>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nc_max]
   float* s_log = reinterpret_cast<float*>(keys + nc_max);                   // [max_fanout, rounded up to 4] shared step-0 logits
@@ -411,26 +421,32 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
   int* new_seq = reinterpret_cast<int*>(smem + (size_t)nc_max * 8 + ((size_t)tr.max_fanout * 4 + 15) / 16 * 16);
   int* new_anc = new_seq + st.K * st.Tmax;
   __shared__ StepShared sh;
-  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max, items_ptr(ui...)};
+  float* par = nullptr;  // BIAS: the potentials of the K beams' own nodes
+  if constexpr (BIAS) {
+    __shared__ float s_par[GRAM_MAX_BEAMS];
+    par = s_par;
+  }
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max, items_ptr(ui...),
+                   0.f, bias_of(ui...).phi, bias_of(ui...).stride, par};
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int K = st.K;
-  step_setup(a, sh, b, tid, nc_max);
+  step_setup<BIAS>(a, sh, b, tid, nc_max, par);
   const int C = sh.C, NC = sh.NC;
   const bool isdone = sh.isdone != 0;
 
   if (!isdone && logits == nullptr) {
     for (int ci = C + tid; ci < NC; ci += NTHR) keys[ci] = 0ull;
     const bool shared0 = rows_per_user == 1;
-    sparse_window<NTHR, FILT>(a, sh, keys, s_log, b, tid, 0, shared0 ? sh.pre[1] : C, shared0);
+    sparse_window<NTHR, FILT, false, BIAS>(a, sh, keys, s_log, b, tid, 0, shared0 ? sh.pre[1] : C, shared0);
     if (shared0) {
       gram_sync();
-      shared0_keys<NTHR, FILT>(a, sh, keys, s_log, b, tid, 0, sh.pre[1], 0, K);
+      shared0_keys<NTHR, FILT, false, BIAS>(a, sh, keys, s_log, b, tid, 0, sh.pre[1], 0, K);
     }
     gram_sync();
   }
   if (!isdone && logits != nullptr) {
-    dense_window<NTHR, FILT>(a, sh, keys, b, tid, 0, C, NC);
+    dense_window<NTHR, FILT, false, BIAS>(a, sh, keys, b, tid, 0, C, NC);
     gram_sync();
   }
   if (!isdone) {
@@ -469,18 +485,24 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
                                                                 int rows_per_user, const p16* __restrict__ hd,
                                                                 const p16* __restrict__ emb, int d, const int32_t* __restrict__ rowpos,
                                                                 int pieces, const float* __restrict__ emb32, UI... ui) {
-  constexpr bool FILT = filtered<UI...>();
+  constexpr bool FILT = filtered<UI...>(), BIAS = biased<UI...>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [kChunkKeys]
   float* s_log = reinterpret_cast<float*>(keys + kChunkKeys);              // [kChunkLog]
   int* new_seq = reinterpret_cast<int*>(s_log + kChunkLog);                // [K][Tmax] + [Tmax][K], as in the one-shot kernel
   int* new_anc = new_seq + st.K * st.Tmax;
   __shared__ StepShared sh;
-  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0, items_ptr(ui...)};
+  float* par = nullptr;  // (as in the one-shot kernel)
+  if constexpr (BIAS) {
+    __shared__ float s_par[GRAM_MAX_BEAMS];
+    par = s_par;
+  }
+  const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0, items_ptr(ui...),
+                   0.f, bias_of(ui...).phi, bias_of(ui...).stride, par};
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int K = st.K;
-  step_setup(a, sh, b, tid, 0);
+  step_setup<BIAS>(a, sh, b, tid, 0, par);
   const int C = sh.C;
   const bool isdone = sh.isdone != 0;
 
@@ -504,13 +526,13 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
     if (logits != nullptr) {
       for (int c0 = 0; c0 < C; c0 += cap) {
         const int n = C - c0 < cap ? C - c0 : cap;
-        dense_window<NTHR, FILT>(a, sh, kw, b, tid, c0, n, n);
+        dense_window<NTHR, FILT, false, BIAS>(a, sh, kw, b, tid, c0, n, n);
         merge(n);
       }
     } else if (rows_per_user != 1) {
       for (int c0 = 0; c0 < C; c0 += cap) {
         const int n = C - c0 < cap ? C - c0 : cap;
-        sparse_window<NTHR, FILT>(a, sh, kw, s_log, b, tid, c0, n, false);
+        sparse_window<NTHR, FILT, false, BIAS>(a, sh, kw, s_log, b, tid, c0, n, false);
         merge(n);
       }
     } else {
@@ -518,12 +540,12 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
       const int njmax = cap < kChunkLog ? cap : kChunkLog;
       for (int j0 = 0; j0 < cnt0; j0 += njmax) {
         const int nj = cnt0 - j0 < njmax ? cnt0 - j0 : njmax;
-        sparse_window<NTHR, FILT>(a, sh, kw, s_log, b, tid, j0, nj, true);
+        sparse_window<NTHR, FILT, false, BIAS>(a, sh, kw, s_log, b, tid, j0, nj, true);
         gram_sync();
         const int kgmax = cap / nj;  // >= 1
         for (int k0 = 0; k0 < K; k0 += kgmax) {
           const int kg = K - k0 < kgmax ? K - k0 : kgmax;
-          shared0_keys<NTHR, FILT>(a, sh, kw, s_log, b, tid, j0, nj, k0, kg);
+          shared0_keys<NTHR, FILT, false, BIAS>(a, sh, kw, s_log, b, tid, j0, nj, k0, kg);
           merge(kg * nj);
         }
       }
@@ -1187,10 +1209,11 @@ static int launch_step_pair(bool wide, int B, size_t smem, hipStream_t stream, c
 }
 
 // items != nullptr: the step's form with per-user item filters (the <NTHR, gram_user_items_t> instantiations of the step kernels);
-// nullptr: exactly the launches of before
+// nullptr: exactly the launches of before.  bias != nullptr: the biased form (the <NTHR, [gram_user_items_t,] StepBias> instantiations)
 static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                             int cur_len, int rows_per_user, const void* hd, const void* emb, int d, const int32_t* rowpos,
-                            void* stream, int pieces = 1, const float* emb32 = nullptr, const gram_user_items_t* items = nullptr) {
+                            void* stream, int pieces = 1, const float* emb32 = nullptr, const gram_user_items_t* items = nullptr,
+                            const StepBias* bias = nullptr) {
   if (int e = check_state(st)) return e;
   if (!tr || !lse || cur_len < 1 || cur_len >= st->Tmax || V < 2 || (rows_per_user != 1 && rows_per_user != st->K)) return GRAM_E_ARG;
   if (!logits && (!hd || (!emb && !emb32) || d < 64 || (d & 63))) return GRAM_E_ARG;
@@ -1222,6 +1245,7 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
           wide, st->B, smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d,
           rowpos, pieces, emb32, ui...);
     };
+    if (bias) return items ? launch(*items, *bias) : launch(*bias);
     return items ? launch(*items) : launch();
   }
   // a handful of users: the sparse logits by their own kernel over many CUs (sparse_logits_kernel), the search step reads them
@@ -1240,7 +1264,40 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
         wide, st->B, smem_one, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nc, rows_per_user, (const p16*)hd, (const p16*)emb, d,
         rowpos, pieces, emb32, pre, ui...);
   };
+  if (bias) return items ? launch(*items, *bias) : launch(*bias);
   return items ? launch(*items) : launch();
+}
+
+// the potentials of a biased step: present, and one row for all users or a row of at least n_nodes entries per user
+static int check_bias(const gram_trie_t* tr, const float* phi, int64_t phi_stride) {
+  if (!tr || !phi || (phi_stride != 0 && phi_stride < tr->n_nodes)) return GRAM_E_ARG;
+  return 0;
+}
+
+extern "C" int gram_beam_step_bias(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
+                                   int cur_len, int rows_per_user, const float* phi, int64_t phi_stride,
+                                   const gram_user_items_t* items, void* stream) {
+  if (int e = check_bias(tr, phi, phi_stride)) return e;
+  if (items)
+    if (int e = check_items(items)) return e;
+  if (!logits) return GRAM_E_ARG;
+  const StepBias bias{phi, (long long)phi_stride};
+  return launch_beam_step(st, tr, logits, lse, V, cur_len, rows_per_user, nullptr, nullptr, 0, nullptr, stream, 1, nullptr, items, &bias);
+}
+
+extern "C" int gram_beam_step_bias_sparse(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
+                                          const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                                          int rows_per_user, const int32_t* rowpos, int pieces, const float* phi, int64_t phi_stride,
+                                          const gram_user_items_t* items, void* stream) {
+  if (int e = check_bias(tr, phi, phi_stride)) return e;
+  if (items)
+    if (int e = check_items(items)) return e;
+  if (!hidden_bf16 || !st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
+  // pieces == 1 reads lm_head_bf16, two pieces (or no lm_head_bf16) lm_head_f32: as gram_beam_step_groups_sparse
+  const bool use32 = pieces > 1 || !lm_head_bf16;
+  const StepBias bias{phi, (long long)phi_stride};
+  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, use32 ? nullptr : lm_head_bf16, d, rowpos, stream,
+                          pieces, use32 ? lm_head_f32 : nullptr, items, &bias);
 }
 
 // the (K, G, lambda) of a group search: G groups of K / G beams, a finite penalty >= 0

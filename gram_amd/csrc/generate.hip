@@ -542,11 +542,20 @@ struct GroupMode {
   float diversity_penalty;
 };
 
+// the search mode of gram_generate_bias (NULL everywhere else): the caller's potentials (gram_item_bias_table) and their row stride
+struct BiasMode {
+  const float* phi;
+  int64_t stride;
+};
+
 // the search step on the hidden states decode_step left in w.dec.h (rowpos: live-row step, else NULL; items: per-user item filters of
-// gram_generate_items, else NULL; grp: the group step, else NULL)
+// gram_generate_items, else NULL; grp: the group step, else NULL; bias: the biased step, else NULL)
 int search_step(const gram_model* m, const Workspace& w, const gram_trie_t* trie, int cur_len, int rows_per_user, const int32_t* rowpos,
-                const gram_user_items_t* items, void* st, const GroupMode* grp = nullptr) {
+                const gram_user_items_t* items, void* st, const GroupMode* grp = nullptr, const BiasMode* bias = nullptr) {
   const gram_model_desc_t& c = m->d;
+  if (bias)
+    return gram_beam_step_bias_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
+                                      rows_per_user, rowpos, w.pieces, bias->phi, bias->stride, items, st);
   if (grp)
     return gram_beam_step_groups_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
                                         rows_per_user, rowpos, w.pieces, grp->num_groups, grp->diversity_penalty, items, st);
@@ -931,10 +940,12 @@ namespace {
 // launch cost, and a captured train cannot take the live-row step, whose row counts travel through the host -- and removed in round 4.)
 int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                   int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
-                  const gram_trie_tail_t* tail, const GroupMode* grp, int64_t* sequences, float* scores, void* stream) {
+                  const gram_trie_tail_t* tail, const GroupMode* grp, const BiasMode* bias, int64_t* sequences, float* scores,
+                  void* stream) {
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
   // grp: group beam search (gram_generate_groups): its init and its search step, the same loop (a -inf beam has no node, so
   // gram_live_rows' liveness test holds unchanged); the caller passes no tail
+  // bias: the biased search (gram_generate_bias): the plain init and the biased search step, the same loop; no tail either
   if (grp) TRY(gram_beam_init_groups(&w.beam, trie, /*decoder_start_token_id=*/0, grp->num_groups, stream));
   else TRY(gram_beam_init(&w.beam, trie, /*decoder_start_token_id=*/0, stream));
   if (K == 1) {  // HF: num_beams == 1 -> greedy_search (raw logits, no hypotheses, no scores)
@@ -1008,7 +1019,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
                             stream));
             TRY(gram_lse_combine(w.lse_part, w.lse, counts[0], m->d.vocab / 64, stream));
           }  // else: no beam can be extended; the search step below reads no decoder row
-          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream, grp));
+          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream, grp, bias));
           continue;
         }
       }
@@ -1016,7 +1027,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, Kt, B * K, max_length, t, nullptr, w.lse_part, nullptr,
                       stream));
       TRY(gram_lse_combine(w.lse_part, w.lse, B * Kt, m->d.vocab / 64, stream));
-      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream, grp));
+      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream, grp, bias));
     }
     TRY(gram_beam_finalize(&w.beam, nret, max_length, sequences, scores, w.width, stream));
   }
@@ -1044,7 +1055,8 @@ static int read_width_and_error(const Workspace& w, int32_t* width_host, void* s
 static int generate_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                          int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp,
                          const gram_user_items_t* items, const gram_trie_tail_t* tail, void* workspace, int64_t workspace_bytes,
-                         int64_t* sequences, float* scores, int32_t* width_host, void* stream, const GroupMode* grp = nullptr) {
+                         int64_t* sequences, float* scores, int32_t* width_host, void* stream, const GroupMode* grp = nullptr,
+                         const BiasMode* bias = nullptr) {
   TRY(check_shapes(m, B, N, L, K, max_length));
   TRY(check_compaction(comp, B, N));
   if (!trie || nret < 1 || nret > K || !sequences || (!scores && K != 1)) return GRAM_E_ARG;
@@ -1064,7 +1076,7 @@ static int generate_call(const gram_model_t* m, const int64_t* input_ids, const 
     }
   }
   w.beam.length_penalty = length_penalty;
-  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, grp, sequences, scores, stream));
+  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, grp, bias, sequences, scores, stream));
   return read_width_and_error(w, width_host, stream);
 }
 
@@ -1091,13 +1103,17 @@ extern "C" int gram_generate_tail(const gram_model_t* m, const int64_t* input_id
                        workspace_bytes, sequences, scores, width_host, stream);
 }
 
+// the per-user lists of the beam-search entries that take them (gram_user_items_t): every array present, stride and mode in range
+static bool items_ok(const gram_user_items_t* items) {
+  return items && items->leaf_lo && items->leaf_hi && items->ranks && items->count && items->stride >= 1 &&
+         items->stride <= GRAM_MAX_USER_ITEMS && (items->mode == GRAM_ITEMS_EXCLUDE || items->mode == GRAM_ITEMS_ALLOW);
+}
+
 extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
                                    int nret, int max_length, float length_penalty, const gram_trie_t* trie,
                                    const gram_compaction_t* comp, const gram_user_items_t* items, void* workspace,
                                    int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
-  if (!items || !items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
-      items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW))
-    return GRAM_E_ARG;
+  if (!items_ok(items)) return GRAM_E_ARG;
   return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
                        workspace_bytes, sequences, scores, width_host, stream);
 }
@@ -1110,12 +1126,24 @@ extern "C" int gram_generate_groups(const gram_model_t* m, const int64_t* input_
                                     float* scores, int32_t* width_host, void* stream) {
   if (K < 2 || num_groups < 1 || num_groups > K || K % num_groups != 0 || !(diversity_penalty >= 0.f && diversity_penalty < INFINITY))
     return GRAM_E_ARG;
-  if (items && (!items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
-                items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW)))
-    return GRAM_E_ARG;
+  if (items && !items_ok(items)) return GRAM_E_ARG;
   const GroupMode grp{num_groups, diversity_penalty};
   return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
                        workspace_bytes, sequences, scores, width_host, stream, &grp);
+}
+
+// beam search with per-item score biases: gram_generate_ex's call with the biased search step; items may be NULL.
+// The potentials are the caller's tensor (gram_item_bias_table): the workspace is gram_generate_ex's.
+extern "C" int gram_generate_bias(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
+                                  int nret, int max_length, float length_penalty, const gram_trie_t* trie,
+                                  const gram_compaction_t* comp, const float* phi, int64_t phi_stride, const gram_user_items_t* items,
+                                  void* workspace, int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host,
+                                  void* stream) {
+  if (K < 2 || !trie || !phi || (phi_stride != 0 && phi_stride < trie->n_nodes)) return GRAM_E_ARG;
+  if (items && !items_ok(items)) return GRAM_E_ARG;
+  const BiasMode bias{phi, phi_stride};
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
+                       workspace_bytes, sequences, scores, width_host, stream, nullptr, &bias);
 }
 
 // ---- Trie-constrained sampling (gram_sample) ------------------------------------------------------------------------

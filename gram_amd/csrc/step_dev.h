@@ -26,7 +26,38 @@ struct StepArgs {
   int pre_stride;
   const gram_user_items_t* ui;  // per-user item filter (the FILT instantiations only; nullptr otherwise)
   float lam = 0.f;              // diversity penalty (the group step only)
+  // per-item score biases (the BIAS instantiations only): the potentials f32 [rows][n_nodes], the stride between a
+  // user's rows (0: one row shared by all users) and the K beams' own potentials in LDS (step_setup<true> fills them)
+  const float* __restrict__ phi = nullptr;
+  long long phi_stride = 0;
+  const float* phi_par = nullptr;
 };
+
+// The biased step's operand, the LAST element of a step kernel's trailing pack (behind the item filter, if any): the unbiased
+// instantiations carry none of it.
+struct StepBias {
+  const float* phi;
+  long long stride;
+};
+template <typename... UI>
+constexpr bool biased() {
+  static_assert(StepPack<UI...>::value, "a step kernel's trailing pack (trie_dev.h)");
+  return (false || ... || std::is_same_v<UI, StepBias>);
+}
+__device__ __forceinline__ const gram_user_items_t* items_ptr(const StepBias&) { return nullptr; }
+__device__ __forceinline__ const gram_user_items_t* items_ptr(const gram_user_items_t& u, const StepBias&) { return &u; }
+__device__ __forceinline__ StepBias bias_of() { return {nullptr, 0}; }
+__device__ __forceinline__ StepBias bias_of(const gram_user_items_t&) { return {nullptr, 0}; }
+__device__ __forceinline__ StepBias bias_of(const StepBias& s) { return s; }
+__device__ __forceinline__ StepBias bias_of(const gram_user_items_t&, const StepBias& s) { return s; }
+
+// The edge term of a biased step: lp = logit - lse of the candidate that moves beam k of user b along `edge`, to
+// which the difference of the potentials of the edge's two ends is added.  fp32, one rounding per operation (no contraction), as
+// diversity() in beam.hip writes its term; the caller adds the beam score.
+__device__ __forceinline__ float edge_bias(const StepArgs& a, int b, int k, int edge, float lp) {
+  const float pc = a.phi[(size_t)b * a.phi_stride + a.tr.child_node[edge]];
+  return __fadd_rn(lp, __fsub_rn(pc, a.phi_par[k]));
+}
 
 // (the per-user item filters -- filtered(), items_ptr(), node_alive() -- are trie_dev.h's, shared with the sampling step)
 template <bool FILT>

@@ -33,13 +33,19 @@ __device__ int find_child(const gram_trie_t& tr, int node, int tok) {
 // ---- per-user item filters (gram_user_items_t).  FILT is a compile-time property of the step kernels: the unfiltered instantiations
 // carry none of this.  node_alive below is the ONE definition of "alive" that the search step's key builders, its ranked walk and
 // filler loop, the greedy step and the sampling step all share.
-// A step kernel's filter is its trailing parameter pack UI: nothing (unfiltered: the parameter list and the code of a kernel without
-// the pack) or one gram_user_items_t (FILT).
+// A step kernel's filter is in its trailing parameter pack UI: nothing (unfiltered: the parameter list and the code of a kernel
+// without the pack) or one gram_user_items_t (FILT).  (The search step's pack can end with one more operand, step_dev.h's StepBias.)
+struct StepBias;  // (defined in step_dev.h)
+template <typename... UI>
+struct StepPack : std::false_type {};  // the packs a step kernel may carry, exactly:
+template <> struct StepPack<> : std::true_type {};
+template <> struct StepPack<gram_user_items_t> : std::true_type {};
+template <> struct StepPack<StepBias> : std::true_type {};
+template <> struct StepPack<gram_user_items_t, StepBias> : std::true_type {};
 template <typename... UI>
 constexpr bool filtered() {
-  static_assert(sizeof...(UI) == 0 || (sizeof...(UI) == 1 && (std::is_same_v<UI, gram_user_items_t> && ...)),
-                "a step kernel's trailing pack is empty or one gram_user_items_t");
-  return sizeof...(UI) != 0;
+  static_assert(StepPack<UI...>::value, "a step kernel's trailing pack is empty, one gram_user_items_t, one StepBias, or the two in that order");
+  return (false || ... || std::is_same_v<UI, gram_user_items_t>);
 }
 __device__ __forceinline__ const gram_user_items_t* items_ptr() { return nullptr; }
 __device__ __forceinline__ const gram_user_items_t* items_ptr(const gram_user_items_t& u) { return &u; }

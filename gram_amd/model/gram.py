@@ -1203,7 +1203,7 @@ class GRAM(nn.Module):
                  num_return_sequences=None, output_scores=True, return_dict_in_generate=True, length_penalty=1.0,
                  exclude_items=None, allowed_items=None, candidates=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  uniforms=None, generator=None, num_beam_groups=1, diversity_penalty=0.0, replacement=True, seed=None,
-                 user_keys=None, **unused):
+                 user_keys=None, item_bias=None, bias_lookahead=True, **unused):
         """GRAM.generate (gram.py:74-107) with the kwargs single_runner_gram.py:641-651 passes.
 
         input_ids (B,N,L) int64, attention_mask (B,N,L) bool on the model's device.  Returns a
@@ -1252,7 +1252,23 @@ class GRAM(nn.Module):
         ``sequences_scores`` as beam search does; the scores include the penalties, as in HF.  The penalty acts per step, not per
         sequence, so two groups can return the SAME sequence: ``sequence_items`` then maps both rows to the same item.
         ``exclude_items`` / ``allowed_items`` work as for beam search.  G = 1 is plain beam search (and refuses a non-zero
-        ``diversity_penalty``, as before)."""
+        ``diversity_penalty``, as before).
+
+        Per-item score biases: ``item_bias`` = T, a finite float32 tensor on any device of shape (len(candidates),) -- one bias per
+        item, shared by all users -- or (B, len(candidates)), with ``num_beams`` >= 2 and ``candidates`` as for the item filters
+        (DESIGN.md section 4.11): boosts and demotions, a popularity correction, a soft penalty for seen items, a second model's
+        scores.  The search runs on log p + T: a returned item's ``sequences_scores`` is (its sum of log-probabilities +
+        T[item]) / length^length_penalty up to fp32 rounding, and the list is the one beam search finds for that score -- not a
+        re-ranking of the unbiased list.  Two candidates that spell one sequence share a leaf: the bias of the first counts.  With
+        ``bias_lookahead=True`` (the default) every step already sees the best bias still reachable below a Trie node (each edge adds
+        the difference of the two nodes' potentials, which telescopes to T[item] at the leaf), so a boosted item is not pruned
+        before its last token and the running scores never rise along a path; ``False`` adds each bias at its item's last token
+        only.  A beam cut off by a ``max_length`` shorter than its item carries the optimistic potential of its node.  Biased calls
+        decode step by step (no tail pass).  ``exclude_items`` / ``allowed_items`` compose: the look-ahead is taken over the shared
+        Trie and ignores them, the returned scores do not change.  The potentials are a float32 (rows, n_nodes) tensor with rows = 1
+        or B, allocated per call NEXT TO the workspace: ``max_users_per_call`` does not know of it (n_nodes * 4 bytes per user with
+        a per-user bias).  ``do_sample=True``, ``num_beam_groups`` > 1, ``num_beams`` = 1 and the callback form of
+        ``prefix_allowed_tokens_fn`` are a ``NotImplementedError``.  ``bias_lookahead`` is ignored without ``item_bias``."""
         if prefix_allowed_tokens_fn is None:
             raise NotImplementedError("unconstrained generation is not on GRAM's scoring path (a Trie is always passed)")
         # HF kwargs that would change the search: refuse the ones this path does not implement instead of ignoring them
@@ -1281,6 +1297,9 @@ class GRAM(nn.Module):
                 warnings.warn(f"gram_amd.GRAM.generate ignores the keyword argument {k!r}")
         if input_ids.dim() != 3:
             raise ValueError("input_ids must be (B, N, L)")
+        biased = item_bias is not None
+        if biased:  # (every refusal of the biased search, before anything touches the device)
+            item_bias = self._bias_args(item_bias, input_ids.shape[0], int(num_beams), G, do_sample, prefix_allowed_tokens_fn, candidates)
         if do_sample:  # (every refusal of the sampling path, before anything touches the device)
             sampling = self._sample_args(input_ids.shape[0], int(max_length), num_beams, num_return_sequences, temperature, top_k, top_p,
                                          uniforms, prefix_allowed_tokens_fn)
@@ -1373,7 +1392,7 @@ class GRAM(nn.Module):
         # the tail pass (gram_generate_tail; taken by size, GRAM_TAIL_PASS=0 switches it off: gram_tail_pass_wanted): where the Trie has a tail inside this call's
         # steps, the workspace grows by the forest's rows (gram_workspace_bytes_tail); a device that cannot hold them decodes step by
         # step -- the same results
-        d_tail, tail_steps = self._tail_plan(prefix_allowed_tokens_fn, K, int(max_length), filtered) if G == 1 else (0, 0)
+        d_tail, tail_steps = self._tail_plan(prefix_allowed_tokens_fn, K, int(max_length), filtered) if G == 1 and not biased else (0, 0)
         tail = tail_steps > 0 and _lib.load().gram_tail_pass_wanted(handle, B, N, Lp) == 1
         ws = self._tail_workspace(handle, B, N, Lp, K, int(max_length), tail_steps) if tail else None
         tail = ws is not None
@@ -1390,6 +1409,13 @@ class GRAM(nn.Module):
             if filtered:
                 lists = (*flat.leaf_ranges_on(dev), flat.item_ranks_on(dev, candidates)[1], items, allow)
             seqs, scores, width = torch.ops.gram.generate_groups(*args[:13], G, lam, *args[13:], *lists)
+        elif biased:  # per-item score biases (gram_item_bias_table, then gram_generate_bias): the same arguments, no tail pass
+            leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
+            phi = torch.ops.gram.item_bias_table(item_bias.to(dev).contiguous(), flat.leaf_items_on(dev, candidates), leaf_lo, leaf_hi,
+                                                 t_off, t_tok, t_node, int(flat.max_fanout), int(flat.min_seq_len),
+                                                 0, bool(bias_lookahead))  # (0: the start token the search begins with)
+            lists = (leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items, allow) if filtered else ()
+            seqs, scores, width = torch.ops.gram.generate_bias(*args[:13], phi, *args[13:], *lists)
         elif filtered:
             leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
             seqs, scores, width = torch.ops.gram.generate_items(*args, leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items,
@@ -1423,6 +1449,30 @@ class GRAM(nn.Module):
         if self._closure_trie(fn) is None:
             raise NotImplementedError("generate(num_beam_groups > 1) needs the Trie closure form of prefix_allowed_tokens_fn")
         return lam
+
+    def _bias_args(self, item_bias, B: int, K: int, G: int, do_sample, fn, candidates) -> torch.Tensor:
+        """The arguments of ``generate(item_bias=T)``, or the refusal; returns T as (rows, len(candidates)), rows = 1 or B.
+        Everything is checked on the host, before the model is packed or a tensor is moved."""
+        if do_sample:
+            raise NotImplementedError("generate(item_bias=) is a beam search: biased sampling (do_sample=True) is not implemented")
+        if G > 1:
+            raise NotImplementedError("generate(item_bias=) with num_beam_groups > 1 is not implemented")
+        if K == 1:
+            raise NotImplementedError("generate(item_bias=) with num_beams=1 (greedy search) is not implemented: "
+                                      "use num_beams=2, num_return_sequences=1")
+        if self._closure_trie(fn) is None:
+            raise NotImplementedError("generate(item_bias=) needs the Trie closure form of prefix_allowed_tokens_fn")
+        if candidates is None:
+            raise ValueError("generate: item_bias holds one bias per entry of `candidates` (the sequences the Trie was built from): pass it")
+        n = len(candidates)
+        if not isinstance(item_bias, torch.Tensor) or item_bias.dtype != torch.float32 or \
+                tuple(item_bias.shape) not in ((n,), (B, n)) or n < 1:
+            got = (tuple(item_bias.shape), item_bias.dtype) if isinstance(item_bias, torch.Tensor) else type(item_bias).__name__
+            raise ValueError(f"generate: item_bias must be a float32 tensor of shape ({n},) = (len(candidates),) or ({B}, {n}) = "
+                             f"(B, len(candidates)), got {got}")
+        if not bool(torch.isfinite(item_bias).all()):
+            raise ValueError("generate: item_bias must be finite (to rule an item out, use exclude_items)")
+        return item_bias.detach().reshape(-1, n)
 
     def _sample_args(self, B: int, max_length: int, num_beams, num_return_sequences, temperature, top_k, top_p, uniforms, fn):
         """The arguments of ``generate(do_sample=True)`` as (R, temperature, top_k, top_p), or the refusal: everything is checked on

@@ -10,6 +10,9 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
                                      ``GRAM.generate(exclude_items= / allowed_items=)``
     torch.ops.gram.generate_groups   group (diverse) beam search, with or without the per-user item filters (gram_generate_groups) --
                                      ``GRAM.generate(num_beam_groups=, diversity_penalty=)``
+    torch.ops.gram.item_bias_table   the potentials of per-item score biases over the Trie (gram_item_bias_table)
+    torch.ops.gram.generate_bias     beam search with those potentials in every step, with or without the per-user item filters
+                                     (gram_generate_bias) -- ``GRAM.generate(item_bias=)``
     torch.ops.gram.sample            Trie-constrained sampling, R draws per user with their log-probabilities (gram_sample) --
                                      ``GRAM.generate(do_sample=True)``
     torch.ops.gram.sample_items      the same with per-user item filters (gram_user_items_prepare + gram_sample_items)
@@ -270,6 +273,93 @@ def generate_groups(input_ids: Tensor, attention_mask: Tensor, handle: int, work
 def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, num_beam_groups, diversity_penalty, comp_map,
       comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L, leaf_lo=None, leaf_hi=None, item_rank=None, items=None, allow=False):
+    return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
+
+
+# ---------------------------------------------------------------------------------------------- per-item score biases
+@torch.library.custom_op("gram::item_bias_table", mutates_args=(), device_types="cuda")
+def item_bias_table(item_bias: Tensor, leaf_item: Tensor, leaf_lo: Tensor, leaf_hi: Tensor, trie_child_off: Tensor,
+                    trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, start_token: int,
+                    lookahead: bool) -> Tensor:
+    """The potentials of a biased search (gram_item_bias_table): item_bias f32 (rows, n_items), leaf_item i32
+    (n_leaves,) the candidate of every leaf rank (``FlatTrie.leaf_items``), leaf_lo / leaf_hi i32 (n_nodes,) and the Trie's CSR
+    arrays.  Returns phi f32 (rows, n_nodes): a leaf's entry is its item's bias, an internal node's the largest entry below it
+    (``lookahead``) or 0, the root's and the start node's 0.  Finite values are the caller's business (``GRAM.generate`` checks)."""
+    dev = item_bias.device
+    if item_bias.dim() != 2 or item_bias.shape[0] < 1 or item_bias.shape[1] < 1:
+        raise ValueError("item_bias_table: item_bias must be (rows, n_items)")
+    n_nodes = trie_child_off.numel() - 1
+    _check("item_bias", item_bias, torch.float32)
+    for name, t, shape in (("leaf_item", leaf_item, (None,)), ("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),)), ("leaf_lo", leaf_lo, (n_nodes,)),
+                           ("leaf_hi", leaf_hi, (n_nodes,))):
+        _check(name, t, torch.int32, shape, dev)
+    rows, n_items = item_bias.shape
+    if n_nodes < 1 or leaf_item.numel() < 1 or rows > 65535:
+        raise ValueError("item_bias_table: need a Trie with at least one leaf and at most 65535 rows of biases")
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+    phi = torch.empty(rows, n_nodes, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gram_item_bias_table(item_bias.data_ptr(), n_items, rows, n_items, leaf_item.data_ptr(), leaf_item.numel(),
+                                                    leaf_lo.data_ptr(), leaf_hi.data_ptr(), C.byref(trie), int(start_token),
+                                                    1 if lookahead else 0, phi.data_ptr(), _stream(item_bias)), "gram_item_bias_table")
+    return phi
+
+
+@item_bias_table.register_fake
+def _(item_bias, leaf_item, leaf_lo, leaf_hi, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len,
+      start_token, lookahead):
+    return item_bias.new_empty(item_bias.shape[0], trie_child_off.numel() - 1)
+
+
+@torch.library.custom_op("gram::generate_bias", mutates_args=("workspace",), device_types="cuda")
+def generate_bias(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                  trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
+                  num_return_sequences: int, max_length: int, length_penalty: float, phi: Tensor, comp_map: Optional[Tensor],
+                  comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor],
+                  n_cached: int, cache_L: int, leaf_lo: Optional[Tensor] = None, leaf_hi: Optional[Tensor] = None,
+                  item_rank: Optional[Tensor] = None, items: Optional[Tensor] = None,
+                  allow: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """Beam search with per-item score biases (gram_generate_bias): ``generate``'s inputs and outputs,
+    ``workspace`` of gram_workspace_bytes, plus phi f32 (1, n_nodes) -- shared by all users -- or (B, n_nodes), the potentials
+    ``item_bias_table`` returns; num_beams >= 2.  The optional tail leaf_lo / leaf_hi / item_rank / items / allow is
+    ``generate_items``'s: given (all four tensors), every user searches its own view of the Trie."""
+    if not 2 <= num_beams <= _lib.GRAM_MAX_BEAMS or not 1 <= num_return_sequences <= num_beams:
+        raise ValueError(f"generate_bias: need 2 <= num_beams <= {_lib.GRAM_MAX_BEAMS} and 1 <= num_return_sequences <= num_beams")
+    if input_ids.dim() != 3:
+        raise ValueError("generate_bias: input_ids must be (B, N, L)")
+    dev = input_ids.device
+    n_nodes = trie_child_off.numel() - 1
+    if phi.dim() != 2 or phi.shape[0] not in (1, input_ids.shape[0]):
+        raise ValueError(f"generate_bias: phi must be (1, n_nodes) or (B, n_nodes), got {tuple(phi.shape)}")
+    _check("phi", phi, torch.float32, (None, n_nodes), dev)
+    lists = (leaf_lo, leaf_hi, item_rank, items)
+    if any(t is not None for t in lists):
+        if any(t is None for t in lists):
+            raise ValueError("generate_bias: leaf_lo, leaf_hi, item_rank and items come together")
+        trie, comp, ui, _keep = _user_items("generate_bias", input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node,
+                                            trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot, cache_x,
+                                            n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
+        ui_ref = C.byref(ui)
+    else:
+        _check("input_ids", input_ids, torch.int64)
+        _check("attention_mask", attention_mask, torch.uint8, tuple(input_ids.shape), dev)
+        for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                               ("trie_child_node", trie_child_node, (trie_child_tok.numel(),))):
+            _check(name, t, torch.int32, shape, dev)
+        trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+        comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
+        ui_ref = None
+    with torch.cuda.device(dev):
+        return _search(_lib.load().gram_generate_bias, "gram_generate_bias", input_ids, attention_mask, handle, workspace, trie, comp,
+                       num_beams, num_return_sequences, max_length, length_penalty, phi.data_ptr(),
+                       0 if phi.shape[0] == 1 else n_nodes, ui_ref)
+
+
+@generate_bias.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
+      trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, phi, comp_map, comp_ids, comp_mask, cache_slot,
+      cache_x, n_cached, cache_L, leaf_lo=None, leaf_hi=None, item_rank=None, items=None, allow=False):
     return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
 
 

@@ -487,6 +487,29 @@ class FlatTrie:
             raise ValueError(f"item_ranks: candidate {int(np.nonzero(bad)[0][0])} does not end on a leaf of the Trie")
         return self.leaf_ranges()[0][node].astype(np.int32)
 
+    def leaf_items(self, candidates: Sequence[Sequence[int]]) -> np.ndarray:
+        """int32 [n_leaves]: for every leaf rank (:meth:`leaf_ranges`), the index into `candidates` of the candidate that names the
+        leaf -- :meth:`node_items`' rule: the first of the candidates that spell its sequence -- and -1 for a leaf that none of
+        them spells.  What ``gram_item_bias_table`` gathers a row of per-item biases through."""
+        lo, hi = self.leaf_ranges()
+        item = self.node_items(candidates)
+        out = np.full(int(hi[0]), -1, dtype=np.int32)
+        leaf = (np.diff(self.child_off) == 0) & (np.arange(self.n_nodes) > 0)
+        out[lo[leaf]] = item[leaf]
+        return out
+
+    def leaf_items_on(self, device, candidates: Sequence[Sequence[int]]):
+        """Device copy of :meth:`leaf_items` for this candidate list, built once per (list object, device)."""
+        import torch
+
+        key = ("leaf_items", str(device), id(candidates), len(candidates))
+        hit = self._device.get(key)
+        if hit is None or hit[0] is not candidates:
+            hit = (candidates, torch.from_numpy(self.leaf_items(candidates)).to(device))
+            self._device = {k: v for k, v in self._device.items() if not (isinstance(k, tuple) and k[0] == "leaf_items")}
+            self._device[key] = hit
+        return hit[1]
+
     # host-side walk with the same arrays the device uses (for tests)
     def get(self, prefix: Sequence[int]) -> List[int]:
         node = 0

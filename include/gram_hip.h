@@ -639,6 +639,44 @@ int gram_generate_groups(const gram_model_t* m, const int64_t* input_ids, const 
                          int num_groups, float diversity_penalty, const gram_user_items_t* items_host, void* workspace,
                          int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream);
 
+/* ---- Beam search with per-item score biases: generate(item_bias=) -------------------------------------------------
+ * Every item carries a bias T[r][item], r = 0 (one row shared by all users) or the user.  The biases are pushed up the Trie as
+ * POTENTIALS phi f32 [rows][n_nodes]: a leaf's potential is its item's bias, an internal node's the largest potential below it
+ * (lookahead) or 0, the root's and the start node's 0.  The candidate that moves beam k from its node p along a Trie edge to child c
+ * then scores, fp32 with one rounding per operation,
+ *     s = (logit - lse) + (phi[r][c] - phi[r][p]);   s = s + beam_scores[k]
+ * and everything else is the plain search on these scores.  Along a path the edge terms telescope: a finished item's sum is its
+ * sum of log-probabilities + T[r][item].
+ *
+ * gram_item_bias_table: the potentials, one launch.  bias f32: row r at bias + r * bias_stride, n_items entries (rows == 1: the
+ * stride is not read); leaf_item i32 [n_leaves]: the candidate that names the leaf of every leaf rank (a value outside [0, n_items):
+ * the leaf carries no bias); leaf_lo / leaf_hi i32 [n_nodes]: the leaf-rank range below every node (gram_user_items_t's tables);
+ * start_token: the root's child under it is the start node; lookahead != 0: internal nodes take the max, else 0.  Writes
+ * phi[rows][trie->n_nodes].  The max is taken over a total order of the floats (-0 below +0): the same bits in any order. */
+int gram_item_bias_table(const float* bias, int64_t bias_stride, int rows, int n_items, const int32_t* leaf_item, int n_leaves,
+                         const int32_t* leaf_lo, const int32_t* leaf_hi, const gram_trie_t* trie_host, int start_token, int lookahead,
+                         float* phi, void* stream);
+/* One biased step on dense logits f32 [B * rows_per_user][V] (as gram_beam_step; for tests on given logits).  phi_stride: elements
+ * between the rows of two users, >= n_nodes, or 0: one row shared by all users.  items_host: per-user item filters or NULL. */
+int gram_beam_step_bias(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const float* logits, const float* lse, int V,
+                        int cur_len, int rows_per_user, const float* phi, int64_t phi_stride, const gram_user_items_t* items_host,
+                        void* stream);
+/* One biased step on hidden states (the sparse logits of gram_beam_step_sparse).  lm_head_bf16 / lm_head_f32 / pieces as in
+ * gram_beam_step_groups_sparse; rowpos as in gram_beam_step_sparse_live (NULL: rows in place); items_host: per-user item filters
+ * or NULL.  The one-shot and the chunked form are chosen as for gram_beam_step_sparse and return the same bits. */
+int gram_beam_step_bias_sparse(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
+                               const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                               int rows_per_user, const int32_t* rowpos, int pieces, const float* phi, int64_t phi_stride,
+                               const gram_user_items_t* items_host, void* stream);
+/* generate(item_bias=): gram_generate_ex's arguments, workspace (gram_workspace_bytes) and step-wise launch train -- encoder, bank,
+ * the shared step-0 row, the live-row compaction -- with the biased step in the search step's place; the tail pass is not taken.
+ * phi / phi_stride: the caller's potentials (gram_item_bias_table), read by every step.  items_host: per-user item filters (as
+ * gram_generate_items) or NULL; the potentials are over the shared Trie and ignore them.  K >= 2. */
+int gram_generate_bias(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
+                       int max_length, float length_penalty, const gram_trie_t* trie_host, const gram_compaction_t* compaction_host,
+                       const float* phi, int64_t phi_stride, const gram_user_items_t* items_host, void* workspace,
+                       int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream);
+
 /* ---- Trie-constrained sampling: HF 4.26 `sample` restated for a Trie ------------------------------------------------
  * The state is a gram_beam_state_t with K = R samples per user; nothing is ever reordered, so anc keeps the identity gram_beam_init
  * wrote (except slot 0 at the compact step 0, below).  Sampling leaves the hypothesis heap unused and keeps its per-row "finished"

@@ -40,6 +40,7 @@ struct Case {
   int tail_rows;              // != 0: gram_generate_tail with d_tail = 2 and two steps left; gram_tail_forest reports this many rows
   int forest_attn;            // 1: gram_debug_set_tail_forest_attn(1) first (0: the default -- forests this small keep the level train)
   int groups;                 // != 0: gram_generate_groups with this many beam groups and diversity_penalty = 0.5
+  int bias;                   // != 0: gram_generate_bias; 1: one row of potentials shared by all users, 2: a row of 40 per user
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -120,6 +121,10 @@ const Case kCases[] = {
     // per-row arrays lie behind gram_workspace_bytes
     {"generate_sbs_p2", SBS, 2, 1, 2, 3, 32, 4, 4},
     {"generate_sbs_p1_items", SBS, 1, 1, 2, 3, 32, 4, 4, OFF, false, false, false, false, 0, true},
+    // gram_generate_bias: the train of generate_p2_items (per-user potentials, item filters) and of generate_live_off (one shared
+    // row) with the biased step in the search step's place
+    {"generate_bias_p2_items", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, true, 0, 0, 0, 0, 0, 2},
+    {"generate_bias_p1", GENERATE, 1, 1, 2, 3, 32, 4, 4, OFF, false, false, false, false, 0, false, 0, 0, 0, 0, 0, 1},
 };
 
 gram_model_t* make_model(int pieces, int fold, int max_passages) {
@@ -199,6 +204,14 @@ int run(const Case& c) {
   void* io[5] = {fake(), fake(), fake(), fake(), fake()};  // the remaining inputs and outputs of the entry, in its argument order
   switch (c.entry) {
     case GENERATE:
+      if (c.bias) {
+        // (the filter's tables first, as in the items case below: the addresses of generate_p2_items; the potentials behind them)
+        const gram_user_items_t items{c.items ? fake<int32_t>() : nullptr, c.items ? fake<int32_t>() : nullptr,
+                                      c.items ? fake<int32_t>() : nullptr, c.items ? fake<int32_t>() : nullptr, 64, GRAM_ITEMS_EXCLUDE};
+        return gram_generate_bias(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, fake<float>(),
+                                  c.bias == 2 ? trie.n_nodes : 0, c.items ? &items : nullptr, g_ws, g_ws_bytes, (int64_t*)io[0],
+                                  (float*)io[1], &width, st);
+      }
       if (c.groups)
         return gram_generate_groups(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, c.groups, 0.5f, nullptr, g_ws,
                                     g_ws_bytes, (int64_t*)io[0], (float*)io[1], &width, st);

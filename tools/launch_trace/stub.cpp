@@ -190,6 +190,12 @@ int gram_beam_step_groups_sparse(const gram_beam_state_t* s, const gram_trie_t* 
   if (!items) REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, num_groups, diversity_penalty, (const void*)items, st);
   REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, num_groups, diversity_penalty, items, st);
 }
+int gram_beam_step_bias_sparse(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, const float* lm32,
+                               int d, const float* lse, int V, int cur_len, int rows_per_user, const int32_t* rowpos, int pieces,
+                               const float* phi, int64_t phi_stride, const gram_user_items_t* items, void* st) {
+  if (!items) REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, phi, phi_stride, (const void*)items, st);
+  REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, phi, phi_stride, items, st);
+}
 int gram_beam_step_sparse(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, int d, const float* lse,
                           int V, int cur_len, int rows_per_user, void* st) {
   REC(s, trie, hidden, lm16, d, lse, V, cur_len, rows_per_user, st);
