@@ -96,6 +96,11 @@ class UserItems(C.Structure):
     _fields_ = [("leaf_lo", vp), ("leaf_hi", vp), ("ranks", vp), ("count", vp), ("stride", i32), ("mode", i32)]
 
 
+class UserMask(C.Structure):
+    """gram_user_mask_t: per-user item masks of a search, a bitset over the leaf ranks with running counts (device pointers)"""
+    _fields_ = [("leaf_lo", vp), ("leaf_hi", vp), ("words", vp), ("stride", i64), ("n_leaves", i32)]
+
+
 class SampleParams(C.Structure):
     """gram_sample_params_t: temperature > 0, top_k >= 0 (0 = off), top_p in (0, 1] (1 = off)"""
     _fields_ = [("temperature", f32), ("top_k", i32), ("top_p", f32)]
@@ -208,6 +213,14 @@ SIGNATURES = {
     "gram_greedy_step_items": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, C.c_int, C.c_int, C.POINTER(UserItems), vp]),
     "gram_generate_items": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
                                       C.POINTER(Compaction), C.POINTER(UserItems), vp, i64, vp, vp, C.POINTER(i32), vp]),
+    # per-user item masks
+    "gram_user_mask_words": (i64, [C.c_int]),
+    "gram_user_mask_prepare": (C.c_int, [vp, i64, C.c_int, C.c_int, vp, C.c_int, vp, i64, vp, vp]),
+    "gram_beam_step_sparse_mask": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+                                             C.c_int, C.POINTER(UserMask), vp]),
+    "gram_greedy_step_mask": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), vp, C.c_int, C.c_int, C.POINTER(UserMask), vp]),
+    "gram_generate_mask": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.POINTER(Trie),
+                                     C.POINTER(Compaction), C.POINTER(UserMask), vp, i64, vp, vp, C.POINTER(i32), vp]),
     "gram_encode_passages": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, i64, vp, vp]),
     "gram_gather_passage_x": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "gram_live_rows": (C.c_int, [C.POINTER(BeamState), C.POINTER(Trie), C.POINTER(LiveRows), vp]),

@@ -157,7 +157,7 @@ __device__ __forceinline__ void step_setup(const StepArgs& a, StepShared& sh, in
 // the shared step-0 row computes every child's logit and leaves the test to shared0_keys.
 // GRP (the group step): the diversity term over the nprev tokens chosen so far goes between the log-probability and the beam score.
 // BIAS (the biased step): the edge term (edge_bias, step_dev.h) goes there instead.
-template <int NTHR, bool FILT, bool GRP = false, bool BIAS = false>
+template <int NTHR, int FILT, bool GRP = false, bool BIAS = false>
 __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, float* s_log, int b, int tid,
                                               int c0, int n, bool shared0, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
@@ -173,8 +173,8 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
       while (sh.pre[k + 1] <= ci) ++k;
     const int tok = tr.child_tok[sh.off[k] + (ci - sh.pre[k])];
     kw[i] = ((unsigned long long)(uint32_t)k << 32) | (unsigned long long)(uint32_t)tok;
-    if constexpr (FILT)
-      if (!shared0 && !child_alive<true>(a, b, sh.off[k] + (ci - sh.pre[k]))) kw[i] |= 1ull << 63;  // (k <= 64: the bit is free)
+    if constexpr (FILT != kFilterNone)
+      if (!shared0 && !child_alive<FILT>(a, b, sh.off[k] + (ci - sh.pre[k]))) kw[i] |= 1ull << 63;  // (k <= 64: the bit is free)
   }
   gram_sync();
   auto dot = [&](bool act, int lr, int tok, int ci) -> float {
@@ -192,7 +192,7 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
       act2[w] = i2[w] < n;
       unsigned long long kt = act2[w] ? kw[i2[w]] : 0ull;
       dead2[w] = false;
-      if constexpr (FILT) {
+      if constexpr (FILT != kFilterNone) {
         dead2[w] = (kt >> 63) != 0;
         kt &= ~(1ull << 63);
       }
@@ -226,7 +226,7 @@ __device__ __forceinline__ void sparse_window(const StepArgs& a, const StepShare
 // step 0's shared row: the keys of beams [k0, k0 + kg) x children [j0, j0 + nj) of the shared node, from the nj logits that
 // sparse_window left in s_log: kw[(k - k0) * nj + (j - j0)].  (k0 = j0 = 0, kg = K, nj = the node's fan-out: the user's whole list
 // in its flat-index order)
-template <int NTHR, bool FILT, bool GRP = false, bool BIAS = false>
+template <int NTHR, int FILT, bool GRP = false, bool BIAS = false>
 __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared& sh, unsigned long long* kw, const float* s_log, int b,
                                              int tid, int j0, int nj, int k0, int kg, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
@@ -247,7 +247,7 @@ __device__ __forceinline__ void shared0_keys(const StepArgs& a, const StepShared
 }
 
 // DENSE mode, gather: log_softmax at the allowed tokens + running beam score.  Candidates [c0, c0 + n) -> kw[0, n); kw[n, npad) = 0
-template <int NTHR, bool FILT, bool GRP = false, bool BIAS = false>
+template <int NTHR, int FILT, bool GRP = false, bool BIAS = false>
 __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared& sh, unsigned long long* kw, int b, int tid, int c0, int n,
                                              int npad, int nprev = 0) {
   const gram_beam_state_t& st = a.st;
@@ -279,10 +279,10 @@ __device__ __forceinline__ void dense_window(const StepArgs& a, const StepShared
 // all its candidates into -inf / NaN -- either way the search would go on and return an ordinary-looking ranking without them.
 // -inf candidates are legitimate (HF's -inf refills of finished beams).  Every candidate's key passes through here before the
 // selection can drop it.  FILT: the zero key of a dead candidate is no score (a real key's low word is never 0) and is passed over.
-template <int NTHR, bool FILT>
+template <int NTHR, int FILT>
 __device__ __forceinline__ void flag_nonfinite_keys(const StepArgs& a, const unsigned long long* kw, int n, int tid) {
   for (int i = tid; i < n; i += NTHR) {
-    if constexpr (FILT)
+    if constexpr (FILT != kFilterNone)
       if (kw[i] == 0ull) continue;
     const uint32_t o = (uint32_t)(kw[i] >> 32);
     if (o >= 0xff800000u || o < 0x007fffffu) a.st.error[0] = 4;  // f2ord(+inf) = 0xff800000, f2ord(-inf) = 0x007fffff
@@ -304,7 +304,7 @@ __device__ __forceinline__ void flag_nonfinite_lse(const StepArgs& a, const Step
 // group search: keys[0, min(C, 2 kn)) are THEIR best candidates (C of them in all), their slots of sel_* are filled,
 // "beam 0" of the filler rule is beam k0, EOS candidates go to the user's one heap of capacity K and the done test runs against it.
 // step_advance then moves all K rows at once.
-template <int NTHR, bool FILT>
+template <int NTHR, int FILT>
 __device__ __forceinline__ void step_rank(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int b, int tid, int k0, int kn,
                                           int C) {
   const gram_beam_state_t& st = a.st;
@@ -318,7 +318,7 @@ __device__ __forceinline__ void step_rank(const StepArgs& a, StepShared& sh, con
   if (!isdone) {
     for (int rank = tid; rank < 2 * kn; rank += NTHR) {
       int e = -1;
-      if (rank < C && (!FILT || keys[rank] != 0ull)) {
+      if (rank < C && (FILT == kFilterNone || keys[rank] != 0ull)) {
         const unsigned long long key = keys[rank];
         const uint32_t flat = 0xffffffffu - (uint32_t)(key & 0xffffffffull);
         const int k = (int)(flat / (uint32_t)V), tok = (int)(flat % (uint32_t)V);
@@ -346,7 +346,7 @@ __device__ __forceinline__ void step_rank(const StepArgs& a, StepShared& sh, con
       for (int rank = 0; rank < 2 * kn && j < kn; ++rank) {
         float sc;
         int k, tok;
-        const bool real = rank < C && (!FILT || keys[rank] != 0ull);
+        const bool real = rank < C && (FILT == kFilterNone || keys[rank] != 0ull);
         if (real) {
           const unsigned long long key = keys[rank];
           sc = ord2f((uint32_t)(key >> 32));
@@ -354,10 +354,10 @@ __device__ __forceinline__ void step_rank(const StepArgs& a, StepShared& sh, con
           k = (int)(flat / (uint32_t)V);
           tok = (int)(flat % (uint32_t)V);
         } else {
-          if constexpr (FILT) {
+          if constexpr (FILT != kFilterNone) {
             for (; ftok < V; ++ftok) {
               const int fe = find_child(tr, node0, ftok);
-              if (fe < 0 || !child_alive<true>(a, b, fe)) break;
+              if (fe < 0 || !child_alive<FILT>(a, b, fe)) break;
             }
           } else {
             while (ftok < V && find_child(tr, node0, ftok) >= 0) ++ftok;
@@ -394,7 +394,7 @@ __device__ __forceinline__ void step_rank(const StepArgs& a, StepShared& sh, con
 }
 
 // the plain search: one group of K beams over the user's C = sh.C candidates
-template <int NTHR, bool FILT>
+template <int NTHR, int FILT>
 __device__ __forceinline__ void step_finish(const StepArgs& a, StepShared& sh, const unsigned long long* keys, int* new_seq, int* new_anc,
                                             int b, int tid) {
   step_rank<NTHR, FILT>(a, sh, keys, b, tid, 0, a.st.K, sh.C);
@@ -406,14 +406,16 @@ constexpr int kOneShotMaxKeys = 16384;  // K * max_fanout the one-shot kernel ta
 // ONE-SHOT form: all of a user's candidates in LDS at once (K * max_fanout <= 16 384 and the LDS sum below within the CU's 160 KB).
 // NTHR threads per workgroup (= per user): 256 for batches that fill the chip with workgroups; 1 024 for small batches, where one user's
 // sparse logits (a trip computes NTHR / 4 candidates' dot products, each on its 8 lanes) and sort stages are the step's latency.
-// UI: the per-user item filter (filtered(), above) and / or the biased step's potentials (StepBias, step_dev.h: BIAS)
+// UI: the per-user item filter (the lists or the mask: filter_kind(), trie_dev.h) and / or the biased step's potentials (StepBias,
+// step_dev.h: BIAS)
 template <int NTHR, typename... UI>
 __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
                                                         const float* __restrict__ lse, int V, int cur_len, int nc_max, int rows_per_user,
                                                         const p16* __restrict__ hd, const p16* __restrict__ emb, int d,
                                                         const int32_t* __restrict__ rowpos, int pieces,
                                                         const float* __restrict__ emb32, const float* __restrict__ pre, UI... ui) {
-  constexpr bool FILT = filtered<UI...>(), BIAS = biased<UI...>();
+  constexpr int FILT = filter_kind<UI...>();
+  constexpr bool BIAS = biased<UI...>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [nc_max]
   float* s_log = reinterpret_cast<float*>(keys + nc_max);                   // [max_fanout, rounded up to 4] shared step-0 logits
@@ -427,7 +429,7 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
     par = s_par;
   }
   const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, pre, nc_max, items_ptr(ui...),
-                   0.f, bias_of(ui...).phi, bias_of(ui...).stride, par};
+                   0.f, bias_of(ui...).phi, bias_of(ui...).stride, par, mask_ptr(ui...)};
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int K = st.K;
@@ -485,7 +487,8 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
                                                                 int rows_per_user, const p16* __restrict__ hd,
                                                                 const p16* __restrict__ emb, int d, const int32_t* __restrict__ rowpos,
                                                                 int pieces, const float* __restrict__ emb32, UI... ui) {
-  constexpr bool FILT = filtered<UI...>(), BIAS = biased<UI...>();
+  constexpr int FILT = filter_kind<UI...>();
+  constexpr bool BIAS = biased<UI...>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [kChunkKeys]
   float* s_log = reinterpret_cast<float*>(keys + kChunkKeys);              // [kChunkLog]
@@ -498,7 +501,7 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
     par = s_par;
   }
   const StepArgs a{st, tr, logits, lse, V, cur_len, rows_per_user, hd, emb, d, rowpos, pieces, emb32, nullptr, 0, items_ptr(ui...),
-                   0.f, bias_of(ui...).phi, bias_of(ui...).stride, par};
+                   0.f, bias_of(ui...).phi, bias_of(ui...).stride, par, mask_ptr(ui...)};
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int K = st.K;
@@ -832,7 +835,7 @@ __global__ void beam_finalize_kernel(gram_beam_state_t st, int nret, int max_len
 // Trie children (first maximum wins, like torch.argmax on the -inf-masked row; no children -> index 0),
 // finished users emit pad.  done[b] doubles as HF's (1 - unfinished_sequences); n_hyps[b] records the
 // sequence length at which the user finished (0 = still running) for the final width.
-// UI (filtered(), above): the argmax runs over the children that are alive for the user (node_alive).
+// UI (the lists or the mask: filter_kind(), trie_dev.h): the argmax runs over the children that are alive for the user (node_alive).
 template <typename... UI>
 __global__ void greedy_step_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits, int V, int cur_len, UI... ui) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -847,8 +850,11 @@ __global__ void greedy_step_kernel(gram_beam_state_t st, gram_trie_t tr, const f
       float best = -INFINITY;
       bool any = false;
       for (int e = lo; e < hi; ++e) {
-        if constexpr (filtered<UI...>())
+        if constexpr (filter_kind<UI...>() == kFilterMask) {
+          if (!node_alive(*mask_ptr(ui...), b, tr.child_node[e])) continue;
+        } else if constexpr (filtered<UI...>()) {
           if (!node_alive(*items_ptr(ui...), b, tr.child_node[e])) continue;
+        }
         const int c = tr.child_tok[e];
         const float v = logits[(size_t)b * V + c];
         // children are sorted by token: strict > keeps the first maximum; a -inf logit at a lower index than
@@ -930,6 +936,60 @@ __global__ __launch_bounds__(256) void user_items_prepare_kernel(const int32_t* 
       if (pos < stride) ranks[(size_t)b * stride + pos] = s[i];
       ++pos;
     }
+}
+
+// A call's item mask -> every user's records (gram_user_mask_prepare).  One workgroup per user walks the leaf ranks
+// once, kMaskPassLeaves per pass: a lane per leaf (coalesced leaf_item reads, one byte of the user's mask row each), a wave's 64-bit
+// ballot is two words of the bitset, and a wave takes four ballots in a row, so that its 256 gathers are in flight together.  The
+// waves' popcounts meet in LDS (double-buffered: one barrier per pass); every wave adds the earlier waves' to the total carried from
+// the passes before and writes its eight records.  No atomics, and no word depends on the geometry.  The pass that holds rank
+// n_leaves writes the last record (n_leaves / 32: the one a count up to hi = n_leaves reads); records from stride's surplus on are
+// never touched.
+constexpr int kMaskPassLeaves = 1024;
+__global__ __launch_bounds__(256) void user_mask_prepare_kernel(const uint8_t* __restrict__ mask, long long mask_stride, int n_items,
+                                                                const int32_t* __restrict__ leaf_item, int n_leaves,
+                                                                uint32_t* __restrict__ words, long long stride,
+                                                                int32_t* __restrict__ count) {
+  __shared__ int s_cnt[2][4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint8_t* __restrict__ row = mask + (size_t)b * mask_stride;
+  uint2* __restrict__ rec = reinterpret_cast<uint2*>(words) + (size_t)b * stride;
+  const int W = n_leaves / 32 + 1;
+  int total = 0;
+  for (int base = 0, pass = 0; base <= n_leaves; base += kMaskPassLeaves, ++pass) {
+    const int r0 = base + wave * (kMaskPassLeaves / 4);
+    unsigned long long m[4];
+    int c = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = r0 + q * 64 + lane;
+      bool keep = false;
+      if (r < n_leaves) {
+        const int it = leaf_item[r];
+        if (it >= 0 && it < n_items) keep = row[it] != 0;
+      }
+      m[q] = __ballot(keep);
+      c += __popcll(m[q]);
+    }
+    if (lane == 0) s_cnt[pass & 1][wave] = c;
+    gram_sync();
+    int before = total;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int n = s_cnt[pass & 1][w];
+      if (w < wave) before += n;
+      total += n;
+    }
+    const int w0 = r0 >> 5;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t lo = (uint32_t)m[q], hi = (uint32_t)(m[q] >> 32);
+      if (lane == 2 * q && w0 + lane < W) rec[w0 + lane] = make_uint2(lo, (uint32_t)before);
+      if (lane == 2 * q + 1 && w0 + lane < W) rec[w0 + lane] = make_uint2(hi, (uint32_t)(before + __popc(lo)));
+      before += __popcll(m[q]);
+    }
+  }
+  if (tid == 0) count[b] = total;
 }
 
 __global__ void greedy_finalize_kernel(gram_beam_state_t st, int max_length, int64_t* __restrict__ sequences,
@@ -1209,11 +1269,12 @@ static int launch_step_pair(bool wide, int B, size_t smem, hipStream_t stream, c
 }
 
 // items != nullptr: the step's form with per-user item filters (the <NTHR, gram_user_items_t> instantiations of the step kernels);
-// nullptr: exactly the launches of before.  bias != nullptr: the biased form (the <NTHR, [gram_user_items_t,] StepBias> instantiations)
+// nullptr: exactly the launches of before.  bias != nullptr: the biased form (the <NTHR, [gram_user_items_t,] StepBias> instantiations).
+// um != nullptr (alone): the step's form with per-user item masks (the <NTHR, gram_user_mask_t> instantiations)
 static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                             int cur_len, int rows_per_user, const void* hd, const void* emb, int d, const int32_t* rowpos,
                             void* stream, int pieces = 1, const float* emb32 = nullptr, const gram_user_items_t* items = nullptr,
-                            const StepBias* bias = nullptr) {
+                            const StepBias* bias = nullptr, const gram_user_mask_t* um = nullptr) {
   if (int e = check_state(st)) return e;
   if (!tr || !lse || cur_len < 1 || cur_len >= st->Tmax || V < 2 || (rows_per_user != 1 && rows_per_user != st->K)) return GRAM_E_ARG;
   if (!logits && (!hd || (!emb && !emb32) || d < 64 || (d & 63))) return GRAM_E_ARG;
@@ -1245,6 +1306,7 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
           wide, st->B, smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d,
           rowpos, pieces, emb32, ui...);
     };
+    if (um) return launch(*um);
     if (bias) return items ? launch(*items, *bias) : launch(*bias);
     return items ? launch(*items) : launch();
   }
@@ -1264,6 +1326,7 @@ static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, 
         wide, st->B, smem_one, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nc, rows_per_user, (const p16*)hd, (const p16*)emb, d,
         rowpos, pieces, emb32, pre, ui...);
   };
+  if (um) return launch(*um);
   if (bias) return items ? launch(*items, *bias) : launch(*bias);
   return items ? launch(*items) : launch();
 }
@@ -1437,6 +1500,31 @@ extern "C" int gram_user_items_prepare(const int32_t* item_rank, int n_items, co
   return 0;
 }
 
+extern "C" int64_t gram_user_mask_words(int n_leaves) { return n_leaves < 1 ? GRAM_E_ARG : (int64_t)n_leaves / 32 + 1; }
+
+extern "C" int gram_user_mask_prepare(const uint8_t* mask, int64_t mask_stride, int B, int n_items, const int32_t* leaf_item, int n_leaves,
+                                      uint32_t* words, int64_t stride, int32_t* count, void* stream) {
+  if (!mask || !leaf_item || !words || !count || B < 1 || n_items < 1 || mask_stride < n_items || n_leaves < 1 || n_leaves > (1 << 24) ||
+      stride < gram_user_mask_words(n_leaves) || (reinterpret_cast<uintptr_t>(words) & 7))
+    return GRAM_E_ARG;
+  hipLaunchKernelGGL(user_mask_prepare_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, mask, (long long)mask_stride, n_items, leaf_item,
+                     n_leaves, words, (long long)stride, count);
+  GRAM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int gram_beam_step_sparse_mask(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
+                                          const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                                          int rows_per_user, const int32_t* rowpos, int pieces, const gram_user_mask_t* mask,
+                                          void* stream) {
+  if (int e = check_mask(mask)) return e;
+  if (!hidden_bf16 || !st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
+  // pieces == 1 reads lm_head_bf16, two pieces (or no lm_head_bf16) lm_head_f32: as gram_beam_step_groups_sparse
+  const bool use32 = pieces > 1 || !lm_head_bf16;
+  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, use32 ? nullptr : lm_head_bf16, d, rowpos, stream,
+                          pieces, use32 ? lm_head_f32 : nullptr, nullptr, nullptr, mask);
+}
+
 extern "C" int gram_live_rows(const gram_beam_state_t* st, const gram_trie_t* tr, const gram_live_rows_t* out, void* stream) {
   if (int e = check_state(st)) return e;
   if (!tr || !out || !out->rows || !out->rowpos || !out->users || !out->tokens || !out->counts) return GRAM_E_ARG;
@@ -1488,7 +1576,7 @@ extern "C" int gram_tail_rowpos(const gram_beam_state_t* st, const gram_trie_t* 
   return 0;
 }
 
-// what the two greedy entry points share: the state checks and the launch.  ui: nothing, or the lists (checked by the caller)
+// what the greedy entry points share: the state checks and the launch.  ui: nothing, the lists or the mask (checked by the caller)
 template <typename... UI>
 static int launch_greedy_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, int V, int cur_len, void* stream,
                               const UI&... ui) {
@@ -1510,6 +1598,12 @@ extern "C" int gram_greedy_step_items(const gram_beam_state_t* st, const gram_tr
                                       const gram_user_items_t* items, void* stream) {
   if (int e = check_items(items)) return e;
   return launch_greedy_step(st, tr, logits, V, cur_len, stream, *items);
+}
+
+extern "C" int gram_greedy_step_mask(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, int V, int cur_len,
+                                     const gram_user_mask_t* mask, void* stream) {
+  if (int e = check_mask(mask)) return e;
+  return launch_greedy_step(st, tr, logits, V, cur_len, stream, *mask);
 }
 
 extern "C" int gram_greedy_finalize(const gram_beam_state_t* st, int max_length, int64_t* sequences, int32_t* out_width,

@@ -549,10 +549,15 @@ struct BiasMode {
 };
 
 // the search step on the hidden states decode_step left in w.dec.h (rowpos: live-row step, else NULL; items: per-user item filters of
-// gram_generate_items, else NULL; grp: the group step, else NULL; bias: the biased step, else NULL)
+// gram_generate_items, else NULL; grp: the group step, else NULL; bias: the biased step, else NULL; umask: per-user item masks of
+// gram_generate_mask, else NULL -- they come alone)
 int search_step(const gram_model* m, const Workspace& w, const gram_trie_t* trie, int cur_len, int rows_per_user, const int32_t* rowpos,
-                const gram_user_items_t* items, void* st, const GroupMode* grp = nullptr, const BiasMode* bias = nullptr) {
+                const gram_user_items_t* items, void* st, const GroupMode* grp = nullptr, const BiasMode* bias = nullptr,
+                const gram_user_mask_t* umask = nullptr) {
   const gram_model_desc_t& c = m->d;
+  if (umask)
+    return gram_beam_step_sparse_mask(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
+                                      rows_per_user, rowpos, w.pieces, umask, st);
   if (bias)
     return gram_beam_step_bias_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
                                       rows_per_user, rowpos, w.pieces, bias->phi, bias->stride, items, st);
@@ -941,7 +946,7 @@ namespace {
 int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                   int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
                   const gram_trie_tail_t* tail, const GroupMode* grp, const BiasMode* bias, int64_t* sequences, float* scores,
-                  void* stream) {
+                  void* stream, const gram_user_mask_t* umask = nullptr) {
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
   // grp: group beam search (gram_generate_groups): its init and its search step, the same loop (a -inf beam has no node, so
   // gram_live_rows' liveness test holds unchanged); the caller passes no tail
@@ -951,7 +956,8 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
   if (K == 1) {  // HF: num_beams == 1 -> greedy_search (raw logits, no hypotheses, no scores)
     for (int t = 0; t + 1 < max_length; ++t) {
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, 1, B, max_length, t, w.logits, nullptr, nullptr, stream));
-      if (items) TRY(gram_greedy_step_items(&w.beam, trie, w.logits, m->d.vocab, t + 1, items, stream));
+      if (umask) TRY(gram_greedy_step_mask(&w.beam, trie, w.logits, m->d.vocab, t + 1, umask, stream));
+      else if (items) TRY(gram_greedy_step_items(&w.beam, trie, w.logits, m->d.vocab, t + 1, items, stream));
       else TRY(gram_greedy_step(&w.beam, trie, w.logits, m->d.vocab, t + 1, stream));
     }
     TRY(gram_greedy_finalize(&w.beam, max_length, sequences, w.width, stream));
@@ -1019,7 +1025,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
                             stream));
             TRY(gram_lse_combine(w.lse_part, w.lse, counts[0], m->d.vocab / 64, stream));
           }  // else: no beam can be extended; the search step below reads no decoder row
-          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream, grp, bias));
+          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream, grp, bias, umask));
           continue;
         }
       }
@@ -1027,7 +1033,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, Kt, B * K, max_length, t, nullptr, w.lse_part, nullptr,
                       stream));
       TRY(gram_lse_combine(w.lse_part, w.lse, B * Kt, m->d.vocab / 64, stream));
-      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream, grp, bias));
+      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream, grp, bias, umask));
     }
     TRY(gram_beam_finalize(&w.beam, nret, max_length, sequences, scores, w.width, stream));
   }
@@ -1051,12 +1057,13 @@ static int read_width_and_error(const Workspace& w, int32_t* width_host, void* s
   return 0;
 }
 
-// gram_generate_ex and gram_generate_items (items: the per-user item filters, NULL for gram_generate_ex)
+// gram_generate_ex, gram_generate_items (items: the per-user item filters, NULL for gram_generate_ex) and gram_generate_mask (umask:
+// the per-user item masks, in the lists' place)
 static int generate_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
                          int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp,
                          const gram_user_items_t* items, const gram_trie_tail_t* tail, void* workspace, int64_t workspace_bytes,
                          int64_t* sequences, float* scores, int32_t* width_host, void* stream, const GroupMode* grp = nullptr,
-                         const BiasMode* bias = nullptr) {
+                         const BiasMode* bias = nullptr, const gram_user_mask_t* umask = nullptr) {
   TRY(check_shapes(m, B, N, L, K, max_length));
   TRY(check_compaction(comp, B, N));
   if (!trie || nret < 1 || nret > K || !sequences || (!scores && K != 1)) return GRAM_E_ARG;
@@ -1076,7 +1083,8 @@ static int generate_call(const gram_model_t* m, const int64_t* input_ids, const 
     }
   }
   w.beam.length_penalty = length_penalty;
-  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, grp, bias, sequences, scores, stream));
+  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, grp, bias, sequences, scores, stream,
+                    umask));
   return read_width_and_error(w, width_host, stream);
 }
 
@@ -1116,6 +1124,18 @@ extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_i
   if (!items_ok(items)) return GRAM_E_ARG;
   return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
                        workspace_bytes, sequences, scores, width_host, stream);
+}
+
+// per-user item masks: gram_generate_items' call with the masks in the lists' place (no tail pass)
+extern "C" int gram_generate_mask(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K,
+                                  int nret, int max_length, float length_penalty, const gram_trie_t* trie,
+                                  const gram_compaction_t* comp, const gram_user_mask_t* umask, void* workspace,
+                                  int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
+  if (!umask || !umask->leaf_lo || !umask->leaf_hi || !umask->words || umask->n_leaves < 1 ||
+      umask->stride < (int64_t)umask->n_leaves / 32 + 1 || (reinterpret_cast<uintptr_t>(umask->words) & 7))
+    return GRAM_E_ARG;
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, nullptr, workspace,
+                       workspace_bytes, sequences, scores, width_host, stream, nullptr, nullptr, umask);
 }
 
 // group beam search: gram_generate_ex's call with the group init and the group step; items may be NULL

@@ -31,6 +31,7 @@ struct StepArgs {
   const float* __restrict__ phi = nullptr;
   long long phi_stride = 0;
   const float* phi_par = nullptr;
+  const gram_user_mask_t* um = nullptr;  // per-user item mask (the kFilterMask instantiations only; nullptr otherwise)
 };
 
 // The biased step's operand, the LAST element of a step kernel's trailing pack (behind the item filter, if any): the unbiased
@@ -48,6 +49,7 @@ __device__ __forceinline__ const gram_user_items_t* items_ptr(const StepBias&) {
 __device__ __forceinline__ const gram_user_items_t* items_ptr(const gram_user_items_t& u, const StepBias&) { return &u; }
 __device__ __forceinline__ StepBias bias_of() { return {nullptr, 0}; }
 __device__ __forceinline__ StepBias bias_of(const gram_user_items_t&) { return {nullptr, 0}; }
+__device__ __forceinline__ StepBias bias_of(const gram_user_mask_t&) { return {nullptr, 0}; }
 __device__ __forceinline__ StepBias bias_of(const StepBias& s) { return s; }
 __device__ __forceinline__ StepBias bias_of(const gram_user_items_t&, const StepBias& s) { return s; }
 
@@ -59,10 +61,12 @@ __device__ __forceinline__ float edge_bias(const StepArgs& a, int b, int k, int 
   return __fadd_rn(lp, __fsub_rn(pc, a.phi_par[k]));
 }
 
-// (the per-user item filters -- filtered(), items_ptr(), node_alive() -- are trie_dev.h's, shared with the sampling step)
-template <bool FILT>
+// (the per-user item filters -- filtered(), filter_kind(), items_ptr(), mask_ptr(), node_alive() -- are trie_dev.h's, shared with the
+// sampling step).  FILT: kFilterNone (false), kFilterLists (true) or kFilterMask
+template <int FILT>
 __device__ __forceinline__ bool child_alive(const StepArgs& a, int b, int edge) {
-  if constexpr (FILT) return node_alive(*a.ui, b, a.tr.child_node[edge]);
+  if constexpr (FILT == kFilterMask) return node_alive(*a.um, b, a.tr.child_node[edge]);
+  else if constexpr (FILT != kFilterNone) return node_alive(*a.ui, b, a.tr.child_node[edge]);
   else return true;
 }
 

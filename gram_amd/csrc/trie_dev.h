@@ -42,13 +42,24 @@ template <> struct StepPack<> : std::true_type {};
 template <> struct StepPack<gram_user_items_t> : std::true_type {};
 template <> struct StepPack<StepBias> : std::true_type {};
 template <> struct StepPack<gram_user_items_t, StepBias> : std::true_type {};
+template <> struct StepPack<gram_user_mask_t> : std::true_type {};  // (the search and greedy steps only: per-user item masks, below)
 template <typename... UI>
 constexpr bool filtered() {
-  static_assert(StepPack<UI...>::value, "a step kernel's trailing pack is empty, one gram_user_items_t, one StepBias, or the two in that order");
+  static_assert(StepPack<UI...>::value, "a step kernel's trailing pack is empty, one gram_user_items_t, one StepBias, the two in that order, or one gram_user_mask_t");
   return (false || ... || std::is_same_v<UI, gram_user_items_t>);
+}
+// which alive test a step kernel carries: none, the lists' (two binary searches) or the mask's (two record loads)
+enum : int { kFilterNone = 0, kFilterLists = 1, kFilterMask = 2 };
+template <typename... UI>
+constexpr int filter_kind() {
+  return filtered<UI...>() ? kFilterLists : (false || ... || std::is_same_v<UI, gram_user_mask_t>) ? kFilterMask : kFilterNone;
 }
 __device__ __forceinline__ const gram_user_items_t* items_ptr() { return nullptr; }
 __device__ __forceinline__ const gram_user_items_t* items_ptr(const gram_user_items_t& u) { return &u; }
+__device__ __forceinline__ const gram_user_items_t* items_ptr(const gram_user_mask_t&) { return nullptr; }
+template <typename... UI>
+__device__ __forceinline__ const gram_user_mask_t* mask_ptr(const UI&...) { return nullptr; }
+__device__ __forceinline__ const gram_user_mask_t* mask_ptr(const gram_user_mask_t& u) { return &u; }
 
 // first index in r[0, n) whose value is >= v
 __device__ __forceinline__ int rank_lower_bound(const int32_t* __restrict__ r, int n, int v) {
@@ -69,6 +80,29 @@ __device__ __forceinline__ bool node_alive(const gram_user_items_t& ui, int b, i
   n = n < 0 ? 0 : (n > ui.stride ? ui.stride : n);  // (a wrong count must not reach past the user's row)
   const int c = rank_lower_bound(r, n, hi) - rank_lower_bound(r, n, lo);
   return ui.mode == GRAM_ITEMS_ALLOW ? c > 0 : c < hi - lo;
+}
+
+// ---- per-user item masks (gram_user_mask_t): a user's set as a bitset over the leaf ranks, every 32-bit word with the
+// number of kept leaves in front of it beside it.  count(x) = the user's kept leaves below rank x: one 8-byte load.
+__device__ __forceinline__ int mask_count(const uint2* __restrict__ row, int x) {
+  const uint2 r = row[x >> 5];  // {bits, before}
+  return (int)r.y + __popc(r.x & ((1u << (x & 31)) - 1u));
+}
+// does user b keep an item below `node`?  The kept leaves inside the node's leaf range [lo, hi): two record loads, whatever the set's size
+__device__ __forceinline__ bool node_alive(const gram_user_mask_t& um, int b, int node) {
+  int lo = um.leaf_lo[node], hi = um.leaf_hi[node];
+  lo = lo < 0 ? 0 : (lo > um.n_leaves ? um.n_leaves : lo);  // (wrong tables must not reach past the user's row: its last record
+  hi = hi < 0 ? 0 : (hi > um.n_leaves ? um.n_leaves : hi);  //  is n_leaves / 32)
+  const uint2* __restrict__ row = reinterpret_cast<const uint2*>(um.words) + (size_t)b * um.stride;
+  return mask_count(row, hi) - mask_count(row, lo) > 0;
+}
+
+// the per-user masks of the *_mask entry points (gram_user_mask_t): every array present, at least one leaf, a row that holds its records
+inline int check_mask(const gram_user_mask_t* um) {
+  if (!um || !um->leaf_lo || !um->leaf_hi || !um->words || um->n_leaves < 1 || um->stride < (int64_t)um->n_leaves / 32 + 1 ||
+      (reinterpret_cast<uintptr_t>(um->words) & 7))
+    return GRAM_E_ARG;
+  return 0;
 }
 
 // the per-user lists of the *_items entry points (gram_user_items_t): every array present, stride and mode in range

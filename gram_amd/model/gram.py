@@ -1203,7 +1203,7 @@ class GRAM(nn.Module):
                  num_return_sequences=None, output_scores=True, return_dict_in_generate=True, length_penalty=1.0,
                  exclude_items=None, allowed_items=None, candidates=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  uniforms=None, generator=None, num_beam_groups=1, diversity_penalty=0.0, replacement=True, seed=None,
-                 user_keys=None, item_bias=None, bias_lookahead=True, **unused):
+                 user_keys=None, item_bias=None, bias_lookahead=True, item_mask=None, **unused):
         """GRAM.generate (gram.py:74-107) with the kwargs single_runner_gram.py:641-651 passes.
 
         input_ids (B,N,L) int64, attention_mask (B,N,L) bool on the model's device.  Returns a
@@ -1216,7 +1216,8 @@ class GRAM(nn.Module):
         takes; required with either).  User b then gets exactly what this call returns for that user alone with
         ``prefix_allowed_tokens_fn(Trie(A_b))``, A_b its remaining candidates, bit for bit -- the search walks a per-user view of
         the one shared device Trie.  Two candidates that spell the same sequence share a Trie leaf: naming
-        either names the sequence.  At most 4096 entries per user; a user left without any item is a ``ValueError``.
+        either names the sequence.  At most 4096 entries per user (larger sets: ``item_mask``, below); a user left without any
+        item is a ``ValueError``.
 
         Sampling: ``do_sample=True`` (with ``num_beams=1``) draws ``num_return_sequences`` = R <= 64 items per user from
         p(item | user) restricted to the Trie -- HF 4.26's ``sample``: the Trie mask, then ``temperature`` (> 0), ``top_k`` (None =
@@ -1268,7 +1269,20 @@ class GRAM(nn.Module):
         Trie and ignores them, the returned scores do not change.  The potentials are a float32 (rows, n_nodes) tensor with rows = 1
         or B, allocated per call NEXT TO the workspace: ``max_users_per_call`` does not know of it (n_nodes * 4 bytes per user with
         a per-user bias).  ``do_sample=True``, ``num_beam_groups`` > 1, ``num_beams`` = 1 and the callback form of
-        ``prefix_allowed_tokens_fn`` are a ``NotImplementedError``.  ``bias_lookahead`` is ignored without ``item_bias``."""
+        ``prefix_allowed_tokens_fn`` are a ``NotImplementedError``.  ``bias_lookahead`` is ignored without ``item_bias``.
+
+        Per-user item masks: ``item_mask`` = M, a (B, len(candidates)) tensor of dtype bool, uint8 or any integer type, on any device
+        and of any strides, with ``candidates`` as for the item filters: M[b, i] != 0 says user b may get
+        candidate i.  The semantics are ``allowed_items``' with the same sets -- user b gets, bit for bit, what it gets alone with
+        ``prefix_allowed_tokens_fn(Trie(A_b))`` -- but a set may have ANY size (the lists stop at 4096 entries per user), every user
+        has its own, and filters compose with torch on the device: ``cat_mask[cat] & ~seen & in_stock``.  Works with beam search
+        (``num_beams`` >= 2) and greedy search (``num_beams=1``) in every precision mode; masked calls decode step by step (no tail
+        pass).  Two candidates that spell one sequence share a leaf, which is kept iff M keeps either.  A user's set travels as a
+        bitset over the Trie's leaves with a running count beside every word; these records are allocated per call NEXT TO the
+        workspace, B * (n_leaves / 32 + 1) * 8 bytes, and ``max_users_per_call`` does not count them.  A wrong shape or dtype, a
+        missing ``candidates``, the callback form of ``prefix_allowed_tokens_fn``, ``item_mask`` together with ``exclude_items`` /
+        ``allowed_items`` (fold those into the mask) and a user whose row keeps nothing are a ``ValueError``; ``item_mask`` with
+        ``do_sample=True``, ``num_beam_groups`` > 1 or ``item_bias`` is a ``NotImplementedError``."""
         if prefix_allowed_tokens_fn is None:
             raise NotImplementedError("unconstrained generation is not on GRAM's scoring path (a Trie is always passed)")
         # HF kwargs that would change the search: refuse the ones this path does not implement instead of ignoring them
@@ -1297,6 +1311,10 @@ class GRAM(nn.Module):
                 warnings.warn(f"gram_amd.GRAM.generate ignores the keyword argument {k!r}")
         if input_ids.dim() != 3:
             raise ValueError("input_ids must be (B, N, L)")
+        masked = item_mask is not None
+        if masked:  # (every refusal of the masked search that needs no device, before anything touches one)
+            item_mask = self._mask_args(item_mask, input_ids.shape[0], G, do_sample, prefix_allowed_tokens_fn, candidates,
+                                        exclude_items is not None or allowed_items is not None, item_bias is not None)
         biased = item_bias is not None
         if biased:  # (every refusal of the biased search, before anything touches the device)
             item_bias = self._bias_args(item_bias, input_ids.shape[0], int(num_beams), G, do_sample, prefix_allowed_tokens_fn, candidates)
@@ -1337,6 +1355,8 @@ class GRAM(nn.Module):
         if filtered:  # (validated before anything below touches the passage cache or the workspace)
             allow = allowed_items is not None
             items = self._user_item_lists(allowed_items if allow else exclude_items, allow, B, flat, candidates, dev)
+        if masked:  # (as the lists: an empty user is refused before anything below touches the passage cache or the workspace)
+            item_mask = self._user_item_mask(item_mask, flat, candidates, dev)
         comp, harvest_plan = self._plan(ids, mask, B, N, Lp)
         _ctrie, (t_off, t_tok, t_node) = flat.to_device(dev)
         if do_sample and not replacement:
@@ -1392,7 +1412,7 @@ class GRAM(nn.Module):
         # the tail pass (gram_generate_tail; taken by size, GRAM_TAIL_PASS=0 switches it off: gram_tail_pass_wanted): where the Trie has a tail inside this call's
         # steps, the workspace grows by the forest's rows (gram_workspace_bytes_tail); a device that cannot hold them decodes step by
         # step -- the same results
-        d_tail, tail_steps = self._tail_plan(prefix_allowed_tokens_fn, K, int(max_length), filtered) if G == 1 and not biased else (0, 0)
+        d_tail, tail_steps = self._tail_plan(prefix_allowed_tokens_fn, K, int(max_length), filtered or masked) if G == 1 and not biased else (0, 0)
         tail = tail_steps > 0 and _lib.load().gram_tail_pass_wanted(handle, B, N, Lp) == 1
         ws = self._tail_workspace(handle, B, N, Lp, K, int(max_length), tail_steps) if tail else None
         tail = ws is not None
@@ -1416,6 +1436,10 @@ class GRAM(nn.Module):
                                                  0, bool(bias_lookahead))  # (0: the start token the search begins with)
             lists = (leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items, allow) if filtered else ()
             seqs, scores, width = torch.ops.gram.generate_bias(*args[:13], phi, *args[13:], *lists)
+        elif masked:  # per-user item masks (gram_user_mask_prepare, then gram_generate_mask): the same arguments, no tail pass
+            leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
+            seqs, scores, width, _kept = torch.ops.gram.generate_mask(*args, leaf_lo, leaf_hi, flat.leaf_items_on(dev, candidates),
+                                                                      item_mask)
         elif filtered:
             leaf_lo, leaf_hi = flat.leaf_ranges_on(dev)
             seqs, scores, width = torch.ops.gram.generate_items(*args, leaf_lo, leaf_hi, flat.item_ranks_on(dev, candidates)[1], items,
@@ -1473,6 +1497,51 @@ class GRAM(nn.Module):
         if not bool(torch.isfinite(item_bias).all()):
             raise ValueError("generate: item_bias must be finite (to rule an item out, use exclude_items)")
         return item_bias.detach().reshape(-1, n)
+
+    def _mask_args(self, item_mask, B: int, G: int, do_sample, fn, candidates, filtered: bool, biased: bool) -> torch.Tensor:
+        """The arguments of ``generate(item_mask=M)``, or the refusal; returns M detached.  Everything is checked on the host, before
+        the model is packed or a tensor is moved (the one check that reads M's values, a user without any item, is
+        ``_user_item_mask``'s)."""
+        if do_sample:
+            raise NotImplementedError("generate(item_mask=) with do_sample=True is not implemented (sampling takes exclude_items / allowed_items)")
+        if G > 1:
+            raise NotImplementedError("generate(item_mask=) with num_beam_groups > 1 is not implemented (group search takes "
+                                      "exclude_items / allowed_items)")
+        if biased:
+            raise NotImplementedError("generate(item_mask=) with item_bias is not implemented (the biased search takes "
+                                      "exclude_items / allowed_items)")
+        if filtered:
+            raise ValueError("generate: item_mask does not go with exclude_items / allowed_items: fold those into the mask")
+        if candidates is None:
+            raise ValueError("generate: item_mask has one column per entry of `candidates` (the sequences the Trie was built from): pass it")
+        if self._closure_trie(fn) is None:
+            raise ValueError("generate: item_mask needs the Trie closure form of prefix_allowed_tokens_fn "
+                             "(an arbitrary callback receives batch_id and can filter per user itself)")
+        n = len(candidates)
+        if not isinstance(item_mask, torch.Tensor) or item_mask.dtype.is_floating_point or item_mask.dtype.is_complex or \
+                tuple(item_mask.shape) != (B, n) or n < 1:
+            got = (tuple(item_mask.shape), item_mask.dtype) if isinstance(item_mask, torch.Tensor) else type(item_mask).__name__
+            raise ValueError(f"generate: item_mask must be a bool, uint8 or integer tensor of shape ({B}, {n}) = (B, len(candidates)), "
+                             f"got {got}")
+        return item_mask.detach()
+
+    @staticmethod
+    def _user_item_mask(item_mask: torch.Tensor, flat: FlatTrie, candidates, device) -> torch.Tensor:
+        """``generate``'s item_mask as the contiguous uint8 (B, len(candidates)) tensor torch.ops.gram.generate_mask takes, on
+        ``device``.  The preparation kernel looks a leaf up under the ONE candidate ``FlatTrie.leaf_items`` names for it, so where
+        the list holds several spellings of a sequence (fewer leaves than entries) their columns are folded onto that candidate
+        first.  A user whose row keeps nothing is a ``ValueError`` (one small read-back, as the lists' emptiness check)."""
+        keep = item_mask.to(device).ne(0)
+        B, n = keep.shape
+        rank = flat.item_ranks_on(device, candidates)[1].to(torch.int64)  # (a candidate that is no leaf of the Trie: ValueError)
+        if int(flat.leaf_ranges()[1][0]) < n:
+            named = flat.leaf_items_on(device, candidates).to(torch.int64)[rank]  # the candidate that names each candidate's leaf
+            keep = torch.zeros(B, n, dtype=torch.int32, device=device).index_add_(1, named, keep.to(torch.int32)).ne(0)
+        empty = ~keep.any(dim=1)
+        any_empty, first_empty = torch.stack([empty.any().long(), empty.long().argmax()]).tolist()
+        if any_empty:
+            raise ValueError(f"generate: item_mask leaves user {first_empty} without any item")
+        return keep.to(torch.uint8).contiguous()
 
     def _sample_args(self, B: int, max_length: int, num_beams, num_return_sequences, temperature, top_k, top_p, uniforms, fn):
         """The arguments of ``generate(do_sample=True)`` as (R, temperature, top_k, top_p), or the refusal: everything is checked on

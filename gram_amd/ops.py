@@ -8,6 +8,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
     torch.ops.gram.generate          GRAM.generate's whole path (gram_generate_ex) -- what ``GRAM.generate`` calls
     torch.ops.gram.generate_items    the same path with per-user item filters (gram_user_items_prepare + gram_generate_items) --
                                      ``GRAM.generate(exclude_items= / allowed_items=)``
+    torch.ops.gram.generate_mask     the same path with per-user item masks of any size (gram_user_mask_prepare + gram_generate_mask) --
+                                     ``GRAM.generate(item_mask=)``
     torch.ops.gram.generate_groups   group (diverse) beam search, with or without the per-user item filters (gram_generate_groups) --
                                      ``GRAM.generate(num_beam_groups=, diversity_penalty=)``
     torch.ops.gram.item_bias_table   the potentials of per-item score biases over the Trie (gram_item_bias_table)
@@ -38,7 +40,8 @@ PyTorch's current HIP stream, with meta ("fake") implementations so the ops trac
 Every op keeps its full explicit signature (``torch.library`` derives the schema from it).  What several ops do with the same
 arguments is stated once, in the private helpers below the ``_check`` they are built on: ``_compaction`` / ``_trie`` build the
 gram_compaction_t / gram_trie_t of a call, ``_tf_inputs`` is the validation of the three teacher-forced ops, ``_search`` the
-outputs and the C call of the two ``generate`` ops, ``_user_items`` the validated lists of the two ``*_items`` ops, ``_sample`` the
+outputs and the C call of the ``generate`` ops, ``_filter_inputs`` what the filtered ops require of the tensors they share,
+``_user_items`` the validated lists of the ``*_items`` ops, ``_sample`` the
 checks, outputs and C call of the two ``sample`` ops, ``_enc_self_attn`` / ``_cross_attn_inputs`` the short and long attention forms.
 """
 from __future__ import annotations
@@ -155,6 +158,22 @@ def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_t
 
 
 # ---------------------------------------------------------------------------------------------- generate with per-user item filters
+def _filter_inputs(input_ids: Tensor, attention_mask: Tensor, trie_child_off: Tensor, trie_child_tok: Tensor, trie_child_node: Tensor,
+                   leaf_lo: Tensor, leaf_hi: Tensor, more) -> int:
+    """What every op with a per-user filter (lists or masks) requires of the tensors they share, and of the int32 tensors in
+    ``more`` ((name, tensor, shape), ...): dtype, device, layout and shape.  input_ids is (B, N, L).  Returns n_nodes."""
+    B, N, L = input_ids.shape
+    dev = input_ids.device
+    n_nodes = trie_child_off.numel() - 1
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
+    for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),)), ("leaf_lo", leaf_lo, (n_nodes,)),
+                           ("leaf_hi", leaf_hi, (n_nodes,)), *more):
+        _check(name, t, torch.int32, shape, dev)
+    return n_nodes
+
+
 def _user_items(op: str, input_ids: Tensor, attention_mask: Tensor, trie_child_off: Tensor, trie_child_tok: Tensor,
                 trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, comp_map, comp_ids, comp_mask, cache_slot, cache_x,
                 n_cached: int, cache_L: int, leaf_lo: Tensor, leaf_hi: Tensor, item_rank: Tensor, items: Tensor, allow: bool):
@@ -167,13 +186,8 @@ def _user_items(op: str, input_ids: Tensor, attention_mask: Tensor, trie_child_o
     B, N, L = input_ids.shape
     dev = input_ids.device
     M = items.shape[1]
-    n_nodes = trie_child_off.numel() - 1
-    _check("input_ids", input_ids, torch.int64)
-    _check("attention_mask", attention_mask, torch.uint8, (B, N, L), dev)
-    for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
-                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),)), ("leaf_lo", leaf_lo, (n_nodes,)),
-                           ("leaf_hi", leaf_hi, (n_nodes,)), ("item_rank", item_rank, (None,)), ("items", items, (B, None))):
-        _check(name, t, torch.int32, shape, dev)
+    n_nodes = _filter_inputs(input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node, leaf_lo, leaf_hi,
+                             (("item_rank", item_rank, (None,)), ("items", items, (B, None))))
     if n_nodes < 1 or item_rank.numel() < 1 or not 1 <= M <= _lib.GRAM_MAX_USER_ITEMS:
         raise ValueError(f"{op}: need a Trie, at least one candidate and 1 <= M <= {_lib.GRAM_MAX_USER_ITEMS} (got M={M})")
     # candidate indices index item_rank on the device: out-of-range ones are refused here, not read there
@@ -216,6 +230,54 @@ def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_t
       trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
       cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow):
     return _search_fake(input_ids, num_beams, num_return_sequences, max_length)
+
+
+# ---------------------------------------------------------------------------------------------- generate with per-user item masks
+@torch.library.custom_op("gram::generate_mask", mutates_args=("workspace",), device_types="cuda")
+def generate_mask(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
+                  trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
+                  num_return_sequences: int, max_length: int, length_penalty: float, comp_map: Optional[Tensor],
+                  comp_ids: Optional[Tensor], comp_mask: Optional[Tensor], cache_slot: Optional[Tensor], cache_x: Optional[Tensor],
+                  n_cached: int, cache_L: int, leaf_lo: Tensor, leaf_hi: Tensor, leaf_item: Tensor,
+                  item_mask: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``generate_items`` (same inputs) with the users' sets as a mask of any size in the lists' place (gram_user_mask_t): leaf_item
+    i32 (n_leaves,) the candidate that names the leaf of every leaf rank (``FlatTrie.leaf_items``), item_mask u8 (B, n_items),
+    rows contiguous (any row stride), non-zero = the user may get the candidate.  The records -- B * (n_leaves / 32 + 1) * 8 bytes
+    -- are allocated here, next to the workspace, and written by gram_user_mask_prepare on input_ids' current stream; then
+    gram_generate_mask runs.  Returns ``generate``'s three outputs and count i32 (B,) on the device: the leaves every user keeps
+    (a user with 0 has no item: the caller's to refuse)."""
+    lib = _lib.load()
+    if input_ids.dim() != 3 or item_mask.dim() != 2 or leaf_item.dim() != 1:
+        raise ValueError("generate_mask: input_ids must be (B, N, L), item_mask (B, n_items) and leaf_item (n_leaves,)")
+    B = input_ids.shape[0]
+    dev = input_ids.device
+    n_leaves, n_items = leaf_item.numel(), item_mask.shape[1]
+    n_nodes = _filter_inputs(input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node, leaf_lo, leaf_hi,
+                             (("leaf_item", leaf_item, (n_leaves,)),))
+    if item_mask.dtype != torch.uint8 or item_mask.device != dev or item_mask.shape[0] != B:
+        raise ValueError(f"generate_mask: item_mask must be a uint8 tensor of shape ({B}, n_items) on {dev}")
+    if n_nodes < 1 or n_leaves < 1 or n_items < 1 or item_mask.stride(1) != 1 or (B > 1 and item_mask.stride(0) < n_items):
+        raise ValueError("generate_mask: need a Trie, at least one leaf and one candidate, and item_mask rows that are contiguous")
+    trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
+    comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
+    stride = int(lib.gram_user_mask_words(n_leaves))
+    words = torch.empty(B, stride, 2, dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    um = _lib.UserMask(leaf_lo.data_ptr(), leaf_hi.data_ptr(), words.data_ptr(), stride, n_leaves)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gram_user_mask_prepare(item_mask.data_ptr(), item_mask.stride(0) if B > 1 else n_items, B, n_items,
+                                              leaf_item.data_ptr(), n_leaves, words.data_ptr(), stride, count.data_ptr(),
+                                              _stream(input_ids)), "gram_user_mask_prepare")
+        return (*_search(lib.gram_generate_mask, "gram_generate_mask", input_ids, attention_mask, handle, workspace, trie, comp,
+                         num_beams, num_return_sequences, max_length, length_penalty, C.byref(um)), count)
+
+
+@generate_mask.register_fake
+def _(input_ids, attention_mask, handle, workspace, trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout,
+      trie_min_seq_len, num_beams, num_return_sequences, max_length, length_penalty, comp_map, comp_ids, comp_mask, cache_slot,
+      cache_x, n_cached, cache_L, leaf_lo, leaf_hi, leaf_item, item_mask):
+    return (*_search_fake(input_ids, num_beams, num_return_sequences, max_length),
+            input_ids.new_empty(input_ids.shape[0], dtype=torch.int32))
 
 
 # ---------------------------------------------------------------------------------------------- group (diverse) beam search

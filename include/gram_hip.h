@@ -425,7 +425,46 @@ int gram_beam_step_sparse_split_items(const gram_beam_state_t* st_host, const gr
 int gram_greedy_step_items(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const float* logits, int V, int cur_len,
                            const gram_user_items_t* items_host, void* stream);
 /* Every entry point that takes the lists returns GRAM_E_ARG before any launch for items_host == NULL, a NULL array, a stride
- * outside 1 .. GRAM_MAX_USER_ITEMS or an unknown mode. */
+ * outside 1 .. GRAM_MAX_USER_ITEMS or an unknown mode.  (Sets of more than GRAM_MAX_USER_ITEMS entries: the masks below.) */
+
+/* ---- per-user item masks: a user's item set of ANY size -----------------------------------------------------------
+ * The second representation of A_b (above): a bitset over the leaf ranks with a running count beside every word.  User b owns
+ * `stride` records of two 32-bit words {bits, before}, of which W = n_leaves / 32 + 1 are in use: bit j of record w's `bits` says
+ * that the leaf of rank 32 w + j is kept (ranks >= n_leaves: 0), `before` is the number of kept leaves in the records < w.  The kept
+ * leaves below rank x are  count(x) = before[x >> 5] + popcount(bits[x >> 5] & ((1u << (x & 31)) - 1))  -- the last record always
+ * exists, so x = n_leaves indexes inside the row -- and node n is alive for the user iff count(leaf_hi[n]) - count(leaf_lo[n]) > 0:
+ * two 8-byte loads whatever the set's size, at 2 bits per leaf.  The semantics are GRAM_ITEMS_ALLOW's with the same set: exactly
+ * what HF's PrefixConstrainedLogitsProcessor does with prefix_allowed_tokens_fn(Trie(A_b)) for that user alone, -inf fillers
+ * included.  All arrays are caller-allocated; gram_workspace_bytes does not change. */
+typedef struct gram_user_mask gram_user_mask_t;
+struct gram_user_mask {
+  const int32_t* leaf_lo; /* [n_nodes]         first leaf rank below (or at) each node (gram_user_items_t's table)  */
+  const int32_t* leaf_hi; /* [n_nodes]         one past the last                                                    */
+  const uint32_t* words;  /* [B][stride][2]    = {bits, before}; 8-byte aligned                                     */
+  int64_t stride;         /* records per user, >= n_leaves / 32 + 1                                                 */
+  int32_t n_leaves;       /* >= 1                                                                                   */
+}; /* (40 bytes; its ctypes mirror is checked by tests/test_item_mask_host.py) */
+/* Records of one user's row: n_leaves / 32 + 1 (GRAM_E_ARG for n_leaves < 1). */
+int64_t gram_user_mask_words(int n_leaves);
+/* A call's masks -> gram_user_mask_t.words and count[b] = the number of leaves user b keeps.  mask u8: row b at mask + b *
+ * mask_stride, n_items bytes, non-zero = the user may get the candidate (what `M[b] != 0` is in torch); leaf_item i32 [n_leaves]:
+ * the candidate that names the leaf of every leaf rank (gram_item_bias_table's table; a value outside [0, n_items): no candidate
+ * names the leaf, its bit is 0).  One launch, one workgroup per user, one pass over the leaf ranks; no atomics, the same words in
+ * any geometry; records [n_leaves / 32 + 1, stride) are left untouched.  1 <= n_leaves <= 2^24, mask_stride >= n_items >= 1. */
+int gram_user_mask_prepare(const uint8_t* mask, int64_t mask_stride, int B, int n_items, const int32_t* leaf_item, int n_leaves,
+                           uint32_t* words, int64_t stride, int32_t* count, void* stream);
+/* gram_beam_step_sparse / _live / _split with the masks: lm_head_bf16 / lm_head_f32 / pieces as in gram_beam_step_groups_sparse
+ * (pieces == 1 reads lm_head_bf16; two pieces, or no lm_head_bf16, lm_head_f32), rowpos != NULL: the live-row form, rows_per_user
+ * must be K.  The same launch forms as gram_beam_step_sparse_items (one-shot, chunked, the scratch logits of <= 16 users), and in
+ * GRAM_ITEMS_ALLOW mode with the same sets the same state bit for bit. */
+int gram_beam_step_sparse_mask(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const void* hidden_bf16,
+                               const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
+                               int rows_per_user, const int32_t* rowpos, int pieces, const gram_user_mask_t* mask_host, void* stream);
+/* gram_greedy_step with the masks: the argmax runs over the alive children (gram_greedy_step_items with the same sets). */
+int gram_greedy_step_mask(const gram_beam_state_t* st_host, const gram_trie_t* trie_host, const float* logits, int V, int cur_len,
+                          const gram_user_mask_t* mask_host, void* stream);
+/* Every entry point that takes the masks returns GRAM_E_ARG before any launch, the state untouched, for mask_host == NULL, a NULL
+ * array, words not 8-byte aligned, n_leaves < 1 or a stride below gram_user_mask_words(n_leaves). */
 
 /* HF 4.26 greedy_search (generate with num_beams == 1; BASELINE configs[0]) on the same state with K = 1:
  * argmax of the RAW logits over the Trie children (first maximum), finished users emit pad; finalize copies
@@ -601,6 +640,16 @@ int gram_generate_items(const gram_model_t* m, const int64_t* input_ids, const u
                         int max_length, float length_penalty, const gram_trie_t* trie_host, const gram_compaction_t* compaction_host,
                         const gram_user_items_t* items_host, void* workspace, int64_t workspace_bytes, int64_t* sequences,
                         float* scores, int32_t* width_host, void* stream);
+
+/* gram_generate_ex with per-user item masks (gram_user_mask_t, prepared by gram_user_mask_prepare on the same stream): every search
+ * step and the greedy step take the masks -- gram_generate_items' call with the masks in the lists' place: the same workspace
+ * (gram_workspace_bytes), the same step-wise launch train, the same live-row compaction, no tail pass.  Stands for HF's generate
+ * with prefix_allowed_tokens_fn(Trie(A_b)) per user, for sets of any size.  The caller guarantees every user at least one item
+ * (gram_user_mask_prepare's count).  GRAM_E_ARG for bad masks as above. */
+int gram_generate_mask(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
+                       int max_length, float length_penalty, const gram_trie_t* trie_host, const gram_compaction_t* compaction_host,
+                       const gram_user_mask_t* mask_host, void* workspace, int64_t workspace_bytes, int64_t* sequences,
+                       float* scores, int32_t* width_host, void* stream);
 
 /* ---- Group (diverse) beam search: HF 4.26 `group_beam_search` + HammingDiversityLogitsProcessor on a Trie ----------
  * K beams = num_groups groups of gs = K / num_groups; group g owns beams [g gs, (g + 1) gs) of every user.  The state is the plain

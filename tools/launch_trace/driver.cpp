@@ -41,6 +41,7 @@ struct Case {
   int forest_attn;            // 1: gram_debug_set_tail_forest_attn(1) first (0: the default -- forests this small keep the level train)
   int groups;                 // != 0: gram_generate_groups with this many beam groups and diversity_penalty = 0.5
   int bias;                   // != 0: gram_generate_bias; 1: one row of potentials shared by all users, 2: a row of 40 per user
+  bool umask;                 // gram_generate_mask: per-user item masks (gram_user_mask_t)
 };
 const Case kCases[] = {
     {"generate_p1_folded", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME},
@@ -125,6 +126,13 @@ const Case kCases[] = {
     // row) with the biased step in the search step's place
     {"generate_bias_p2_items", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, true, 0, 0, 0, 0, 0, 2},
     {"generate_bias_p1", GENERATE, 1, 1, 2, 3, 32, 4, 4, OFF, false, false, false, false, 0, false, 0, 0, 0, 0, 0, 1},
+    // gram_generate_mask: the trains of gram_generate_items at the same shapes (two pieces, one piece, greedy) with every step in
+    // its per-user-mask form (tests/test_item_mask_host.py compares each pair call for call)
+    {"generate_p2_mask", GENERATE, 2, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 0, 0, 0, 0, true},
+    {"generate_p1_items", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, true},
+    {"generate_p1_mask", GENERATE, 1, 1, 2, 3, 32, 4, 4, SOME, false, false, false, false, 0, false, 0, 0, 0, 0, 0, 0, true},
+    {"generate_greedy_items", GENERATE, 1, 1, 2, 3, 32, 1, 4, SOME, false, false, false, false, 0, true},
+    {"generate_greedy_mask", GENERATE, 1, 1, 2, 3, 32, 1, 4, SOME, false, false, false, false, 0, false, 0, 0, 0, 0, 0, 0, true},
 };
 
 gram_model_t* make_model(int pieces, int fold, int max_passages) {
@@ -215,6 +223,11 @@ int run(const Case& c) {
       if (c.groups)
         return gram_generate_groups(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, c.groups, 0.5f, nullptr, g_ws,
                                     g_ws_bytes, (int64_t*)io[0], (float*)io[1], &width, st);
+      if (c.umask) {  // (27 leaves: one record, in a row of two)
+        const gram_user_mask_t um{fake<int32_t>(), fake<int32_t>(), fake<uint32_t>(), 2, 27};
+        return gram_generate_mask(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, &um, g_ws, g_ws_bytes,
+                                  (int64_t*)io[0], (float*)io[1], &width, st);
+      }
       if (c.items) {
         const gram_user_items_t items{fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), fake<int32_t>(), 64, GRAM_ITEMS_EXCLUDE};
         return gram_generate_items(m, ids, mask, B, N, L, K, K, T, 1.f, &trie, c.comp ? &comp : nullptr, &items, g_ws, g_ws_bytes,

@@ -51,6 +51,7 @@ void put(const gram_beam_state_t* s) {
 }
 void put(const gram_trie_t* t) { fields(t->child_off, t->child_tok, t->child_node, t->n_nodes, t->n_edges, t->max_fanout, t->min_seq_len); }
 void put(const gram_user_items_t* u) { fields(u->leaf_lo, u->leaf_hi, u->ranks, u->count, u->stride, u->mode); }
+void put(const gram_user_mask_t* u) { fields(u->leaf_lo, u->leaf_hi, u->words, u->stride, u->n_leaves); }
 void put(const gram_trie_rows_t* r) {
   fields(r->tokens, r->pos, r->anc, r->row_node, r->node_row, r->node_tok, r->node_leaf, r->Q, r->Tq, r->n_nodes, r->n_leaves);
 }
@@ -221,6 +222,15 @@ int gram_beam_step_sparse_split_items(const gram_beam_state_t* s, const gram_tri
 int gram_greedy_step_items(const gram_beam_state_t* s, const gram_trie_t* trie, const float* logits, int V, int cur_len,
                            const gram_user_items_t* items, void* st) {
   REC(s, trie, logits, V, cur_len, items, st);
+}
+int gram_beam_step_sparse_mask(const gram_beam_state_t* s, const gram_trie_t* trie, const void* hidden, const void* lm16, const float* lm32,
+                               int d, const float* lse, int V, int cur_len, int rows_per_user, const int32_t* rowpos, int pieces,
+                               const gram_user_mask_t* mask, void* st) {
+  REC(s, trie, hidden, lm16, lm32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, mask, st);
+}
+int gram_greedy_step_mask(const gram_beam_state_t* s, const gram_trie_t* trie, const float* logits, int V, int cur_len,
+                          const gram_user_mask_t* mask, void* st) {
+  REC(s, trie, logits, V, cur_len, mask, st);
 }
 int gram_greedy_step(const gram_beam_state_t* s, const gram_trie_t* trie, const float* logits, int V, int cur_len, void* st) {
   REC(s, trie, logits, V, cur_len, st);
