@@ -480,6 +480,20 @@ __global__ __launch_bounds__(NTHR) void beam_step_kernel(gram_beam_state_t st, g
 constexpr int kChunkKeys = 4096;
 constexpr int kChunkLog = 2048;
 
+// One merge of the streamed forms, plain and group: kw = keys + P holds n fresh keys (all threads behind a barrier or not: one
+// follows the padding); keys[0, P) end up the best P of the carried block and the fresh ones.  GRP: the group form has always put
+// a barrier between flag_nonfinite_keys and top_p_select, here and in its one-shot path, and the plain form none; unjudged.
+template <int NTHR, int FILT, bool GRP, int MAXN>
+__device__ __forceinline__ void merge_round(const StepArgs& a, unsigned long long* keys, unsigned long long* kw, int P, int n, int tid) {
+  int na = 2 * P;  // the power of two >= P + n
+  while (na < P + n) na <<= 1;
+  for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
+  gram_sync();
+  flag_nonfinite_keys<NTHR, FILT>(a, kw, n, tid);
+  if constexpr (GRP) gram_sync();
+  top_p_select<NTHR, MAXN>(keys, na, P, tid);
+}
+
 // (UI: as in beam_step_kernel)
 template <int NTHR, typename... UI>
 __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state_t st, gram_trie_t tr, const float* __restrict__ logits,
@@ -517,15 +531,7 @@ __global__ __launch_bounds__(NTHR) void beam_step_chunked_kernel(gram_beam_state
     if (cap < 1) cap = 1;
     unsigned long long* kw = keys + P;
     for (int i = tid; i < P; i += NTHR) keys[i] = 0ull;  // nothing carried yet
-    // kw[0, n) hold fresh keys (all threads behind a barrier or not: one follows the padding)
-    auto merge = [&](int n) {
-      int na = 2 * P;  // the power of two >= P + n
-      while (na < P + n) na <<= 1;
-      for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
-      gram_sync();
-      flag_nonfinite_keys<NTHR, FILT>(a, kw, n, tid);
-      top_p_select<NTHR, kChunkKeys>(keys, na, P, tid);
-    };
+    auto merge = [&](int n) { merge_round<NTHR, FILT, false, kChunkKeys>(a, keys, kw, P, n, tid); };
     if (logits != nullptr) {
       for (int c0 = 0; c0 < C; c0 += cap) {
         const int n = C - c0 < cap ? C - c0 : cap;
@@ -623,7 +629,7 @@ __global__ __launch_bounds__(NTHR) void beam_group_step_kernel(gram_beam_state_t
         }
         gram_sync();
         flag_nonfinite_keys<NTHR, FILT>(a, keys, Cg, tid);
-        gram_sync();
+        gram_sync();  // (the group forms' barrier that beam_step_kernel does not have: merge_round's GRP, unjudged)
         top_p_select<NTHR, MAXN>(keys, NC, P, tid);
       } else {
         int cp = cap;
@@ -631,15 +637,7 @@ __global__ __launch_bounds__(NTHR) void beam_group_step_kernel(gram_beam_state_t
         if (cp < 1) cp = 1;
         unsigned long long* kw = keys + P;
         for (int i = tid; i < P; i += NTHR) keys[i] = 0ull;  // nothing carried yet
-        auto merge = [&](int n) {
-          int na = 2 * P;  // the power of two >= P + n
-          while (na < P + n) na <<= 1;
-          for (int i = n + tid; i < na - P; i += NTHR) kw[i] = 0ull;
-          gram_sync();
-          flag_nonfinite_keys<NTHR, FILT>(a, kw, n, tid);
-          gram_sync();
-          top_p_select<NTHR, MAXN>(keys, na, P, tid);
-        };
+        auto merge = [&](int n) { merge_round<NTHR, FILT, true, MAXN>(a, keys, kw, P, n, tid); };
         if (logits != nullptr) {
           for (int o = 0; o < Cg; o += cp) {
             const int n = Cg - o < cp ? Cg - o : cp;
@@ -1268,106 +1266,147 @@ static int launch_step_pair(bool wide, int B, size_t smem, hipStream_t stream, c
   return 0;
 }
 
-// items != nullptr: the step's form with per-user item filters (the <NTHR, gram_user_items_t> instantiations of the step kernels);
-// nullptr: exactly the launches of before.  bias != nullptr: the biased form (the <NTHR, [gram_user_items_t,] StepBias> instantiations).
-// um != nullptr (alone): the step's form with per-user item masks (the <NTHR, gram_user_mask_t> instantiations)
-static int launch_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
-                            int cur_len, int rows_per_user, const void* hd, const void* emb, int d, const int32_t* rowpos,
-                            void* stream, int pieces = 1, const float* emb32 = nullptr, const gram_user_items_t* items = nullptr,
-                            const StepBias* bias = nullptr, const gram_user_mask_t* um = nullptr) {
+// One call of the search step, as its entry points hand it to the launcher.
+struct StepCall {
+  const gram_beam_state_t* st = nullptr;
+  const gram_trie_t* tr = nullptr;
+  const float *logits = nullptr, *lse = nullptr;  // logits: the dense step's [rows][V]; nullptr: sparse, hd . emb / emb32 at the allowed tokens
+  int V = 0, cur_len = 0, rows_per_user = 0;
+  void* stream = nullptr;
+  const void *hd = nullptr, *emb = nullptr;
+  const float* emb32 = nullptr;
+  int d = 0, pieces = 1, num_groups = 0;  // num_groups 0: the plain step; G >= 1: the group step (beam_group_step_kernel; lists only)
+  const int32_t* rowpos = nullptr;
+  // the step's form, i.e. the kernels' trailing pack: per-user lists, potentials (phi == nullptr: none), per-user masks (alone)
+  const gram_user_items_t* items = nullptr;
+  StepBias bias{nullptr, 0};
+  const gram_user_mask_t* mask = nullptr;
+  float diversity_penalty = 0.f;
+};
+static StepCall dense_call(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V, int cur_len,
+                           int rows_per_user, void* stream) {
+  return {st, tr, logits, lse, V, cur_len, rows_per_user, stream};  // (the struct's first fields, in its order)
+}
+// the lm_head operand: pieces == 1 reads lm_head_bf16, two pieces (or no lm_head_bf16) lm_head_f32
+static StepCall sparse_call(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden, const void* lm_head_bf16,
+                            const float* lm_head_f32, int d, const float* lse, int V, int cur_len, int rows_per_user,
+                            const int32_t* rowpos, int pieces, void* stream) {
+  StepCall c = dense_call(st, tr, nullptr, lse, V, cur_len, rows_per_user, stream);
+  const bool use32 = pieces > 1 || !lm_head_bf16;
+  c.hd = hidden, c.emb = use32 ? nullptr : lm_head_bf16, c.emb32 = use32 ? lm_head_f32 : nullptr, c.d = d, c.rowpos = rowpos, c.pieces = pieces;
+  return c;
+}
+
+// the (K, G, lambda) of a group search: G groups of K / G beams, a finite penalty >= 0
+static int check_groups(int K, int num_groups, float diversity_penalty) {
+  const bool ok = num_groups >= 1 && num_groups <= K && K % num_groups == 0 && diversity_penalty >= 0.f && diversity_penalty < INFINITY;
+  return ok ? 0 : GRAM_E_ARG;
+}
+
+// The search step, plain or group.  Which form runs is decided by kb, the beams per selection (K, or K / G for a group step): a
+// selection's kb * max_fanout candidates in LDS at once, or streamed.  Where the two steps differ today, a branch says so.
+static int launch_search_step(const StepCall& c) {
+  const gram_beam_state_t* st = c.st;
+  const gram_trie_t* tr = c.tr;
+  const bool group = c.num_groups != 0;
+  hipStream_t stream = (hipStream_t)c.stream;
   if (int e = check_state(st)) return e;
-  if (!tr || !lse || cur_len < 1 || cur_len >= st->Tmax || V < 2 || (rows_per_user != 1 && rows_per_user != st->K)) return GRAM_E_ARG;
-  if (!logits && (!hd || (!emb && !emb32) || d < 64 || (d & 63))) return GRAM_E_ARG;
-  if (pieces < 1 || pieces > GRAM_MAX_PIECES || (pieces > 1 && (!emb32 || (d & 63)))) return GRAM_E_ARG;  // (8 lanes x 8-element loads inside 32-column blocks)
+  if (group && check_groups(st->K, c.num_groups, c.diversity_penalty)) return GRAM_E_ARG;
+  if (group && c.items && check_items(c.items)) return GRAM_E_ARG;  // (the plain step's entry points judge their lists themselves)
+  if (!tr || !c.lse || c.cur_len < 1 || c.cur_len >= st->Tmax || c.V < 2 || (c.rows_per_user != 1 && c.rows_per_user != st->K)) return GRAM_E_ARG;
+  if (group && c.rowpos && c.rows_per_user != st->K) return GRAM_E_ARG;  // (the plain step's entry points judge it, or do not, themselves)
+  if (!c.logits && (!c.hd || (!c.emb && !c.emb32) || c.d < 64 || (c.d & 63))) return GRAM_E_ARG;
+  // (the plain step alone judges d for two pieces on a dense call too -- which no entry point makes today: dense calls have one piece)
+  if (c.pieces < 1 || c.pieces > GRAM_MAX_PIECES || (c.pieces > 1 && (!c.emb32 || (!group && (c.d & 63))))) return GRAM_E_ARG;
   if (tr->max_fanout < 0) return GRAM_E_ARG;
-  long long need = (long long)st->K * tr->max_fanout;
+  const int kb = group ? st->K / c.num_groups : st->K;
+  const long long need = (long long)kb * tr->max_fanout;
   int nc = 64;
   while (nc < need && nc < kOneShotMaxKeys) nc <<= 1;
+  const int nlog_one = (tr->max_fanout + 3) / 4 * 4;
   const size_t seq_bytes = (size_t)2 * st->K * st->Tmax * 4;
-  const size_t smem_one = (size_t)nc * 8 + ((size_t)tr->max_fanout * 4 + 15) / 16 * 16 + seq_bytes;
-  // one-shot: every candidate of a user in LDS at once (+ ~3 KB of static arrays: the CU's 160 KB); everything else streams
+  const size_t smem_one = (size_t)nc * 8 + (size_t)nlog_one * 4 + seq_bytes;
+  // one-shot: every candidate of a selection in LDS at once (+ ~3 KB of static arrays: the CU's 160 KB); everything else streams
   const bool chunked = g_beam_chunked == 1 || need > kOneShotMaxKeys || smem_one > 152 * 1024;
-  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
+  // 32-bit scalar state of the kernels: the flat index k * V + tok < K * V, and the candidate count and its prefix sums <= K * V
+  // (a node has at most V children).  The group step refuses always, the plain step only where it streams.
+  if ((group || chunked) && ((long long)st->K * c.V > INT32_MAX || tr->max_fanout > c.V)) return GRAM_E_ARG;
+  gram_prof::Scope prof(GRAM_K_BEAM, stream, 0.0);
   // few users: one workgroup per user leaves the chip empty and the step is that workgroup's latency -> 1 024 threads per user
   // (same per-candidate arithmetic, same total order of the keys: identical results; GRAM_BEAM_WIDE_MAXB: A/B hook, 0 = never)
   static const int wide_max_b = getenv("GRAM_BEAM_WIDE_MAXB") ? atoi(getenv("GRAM_BEAM_WIDE_MAXB")) : 128;
   const bool wide = st->B <= wide_max_b;
-  if (chunked) {
-    // 32-bit scalar state of the kernel: the flat index k * V + tok < K * V, and the candidate count and its prefix sums <= K * V
-    // (a node has at most V children)
-    if ((long long)st->K * V > INT32_MAX || tr->max_fanout > V) return GRAM_E_ARG;
-    int P = 64;
-    while (P < 2 * st->K) P <<= 1;
-    int cap = kChunkKeys - P;
-    if (g_beam_chunk_cap > 0 && g_beam_chunk_cap < cap) cap = g_beam_chunk_cap;
-    const size_t smem = (size_t)kChunkKeys * 8 + (size_t)kChunkLog * 4 + seq_bytes;  // <= 40 KB + 64 KB
-    auto launch = [&](auto... ui) {
-      return launch_step_pair<beam_step_chunked_kernel<256, decltype(ui)...>, beam_step_chunked_kernel<1024, decltype(ui)...>>(
-          wide, st->B, smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, cap, rows_per_user, (const p16*)hd, (const p16*)emb, d,
-          rowpos, pieces, emb32, ui...);
+  int P = 64;  // (P and cap: the streamed forms and the group kernel only)
+  while (P < 2 * kb) P <<= 1;
+  int cap = kChunkKeys - P;
+  if (g_beam_chunk_cap > 0 && g_beam_chunk_cap < cap) cap = g_beam_chunk_cap;
+  const size_t smem = chunked ? (size_t)kChunkKeys * 8 + (size_t)kChunkLog * 4 + seq_bytes : smem_one;  // chunked: <= 40 KB + 64 KB
+  const p16 *hd = (const p16*)c.hd, *emb = (const p16*)c.emb;
+  if (group) {
+    // (the small-batch sparse_logits_kernel is not used: the group step computes its logits itself at every batch size)
+    const int nkeys = chunked ? kChunkKeys : nc, nlog = chunked ? kChunkLog : nlog_one;
+    auto launch = [&](auto form, auto... ui) {
+      constexpr bool CH = decltype(form)::value;
+      return launch_step_pair<beam_group_step_kernel<256, CH, decltype(ui)...>, beam_group_step_kernel<1024, CH, decltype(ui)...>>(
+          wide, st->B, smem, stream, *st, *tr, c.logits, c.lse, c.V, c.cur_len, nkeys, nlog, cap, c.rows_per_user, hd, emb, c.d, c.rowpos,
+          c.pieces, c.emb32, c.num_groups, c.diversity_penalty, ui...);
     };
-    if (um) return launch(*um);
-    if (bias) return items ? launch(*items, *bias) : launch(*bias);
-    return items ? launch(*items) : launch();
+    if (chunked) return c.items ? launch(std::true_type{}, *c.items) : launch(std::true_type{});
+    return c.items ? launch(std::false_type{}, *c.items) : launch(std::false_type{});
   }
-  // a handful of users: the sparse logits by their own kernel over many CUs (sparse_logits_kernel), the search step reads them
-  // (gram_beam_state_t.cand_logits: caller-provided scratch; GRAM_BEAM_PRE_MAXB: A/B hook, 0 = never)
+  auto with_form = [&](auto launch) {
+    if (c.mask) return launch(*c.mask);
+    if (c.bias.phi) return c.items ? launch(*c.items, c.bias) : launch(c.bias);
+    return c.items ? launch(*c.items) : launch();
+  };
+  if (chunked)
+    return with_form([&](auto... ui) {
+      return launch_step_pair<beam_step_chunked_kernel<256, decltype(ui)...>, beam_step_chunked_kernel<1024, decltype(ui)...>>(
+          wide, st->B, smem, stream, *st, *tr, c.logits, c.lse, c.V, c.cur_len, cap, c.rows_per_user, hd, emb, c.d, c.rowpos, c.pieces,
+          c.emb32, ui...);
+    });
+  // the plain one-shot step alone, for a handful of users: the sparse logits by their own kernel over many CUs (sparse_logits_kernel),
+  // the search step reads them (gram_beam_state_t.cand_logits: caller-provided scratch; GRAM_BEAM_PRE_MAXB: A/B hook, 0 = never)
   static const int pre_max_b = getenv("GRAM_BEAM_PRE_MAXB") ? atoi(getenv("GRAM_BEAM_PRE_MAXB")) : 16;
   const float* pre = nullptr;
-  if (!logits && st->cand_logits && st->B <= pre_max_b && st->B <= st->cand_logits_users && (long long)nc <= st->cand_logits_stride) {
-    const int chunks = (int)((need + 31) / 32);
-    hipLaunchKernelGGL(sparse_logits_kernel, dim3(chunks, st->B), dim3(256), 0, (hipStream_t)stream, *st, *tr, nc,
-                       rows_per_user, (const p16*)hd, (const p16*)emb, d, rowpos, pieces, emb32, st->cand_logits);
+  if (!c.logits && st->cand_logits && st->B <= pre_max_b && st->B <= st->cand_logits_users && (long long)nc <= st->cand_logits_stride) {
+    hipLaunchKernelGGL(sparse_logits_kernel, dim3((int)((need + 31) / 32), st->B), dim3(256), 0, stream, *st, *tr, nc, c.rows_per_user,
+                       hd, emb, c.d, c.rowpos, c.pieces, c.emb32, st->cand_logits);
     GRAM_CHECK_LAUNCH();
     pre = st->cand_logits;
   }
-  auto launch = [&](auto... ui) {
+  return with_form([&](auto... ui) {
     return launch_step_pair<beam_step_kernel<256, decltype(ui)...>, beam_step_kernel<1024, decltype(ui)...>>(
-        wide, st->B, smem_one, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nc, rows_per_user, (const p16*)hd, (const p16*)emb, d,
-        rowpos, pieces, emb32, pre, ui...);
-  };
-  if (um) return launch(*um);
-  if (bias) return items ? launch(*items, *bias) : launch(*bias);
-  return items ? launch(*items) : launch();
+        wide, st->B, smem, stream, *st, *tr, c.logits, c.lse, c.V, c.cur_len, nc, c.rows_per_user, hd, emb, c.d, c.rowpos, c.pieces, c.emb32, pre,
+        ui...);
+  });
 }
 
-// the potentials of a biased step: present, and one row for all users or a row of at least n_nodes entries per user
-static int check_bias(const gram_trie_t* tr, const float* phi, int64_t phi_stride) {
+// the potentials of a biased step: present, and one row for all users or a row of at least n_nodes entries per user; then its lists, if any
+static int check_bias(const gram_trie_t* tr, const float* phi, int64_t phi_stride, const gram_user_items_t* items) {
   if (!tr || !phi || (phi_stride != 0 && phi_stride < tr->n_nodes)) return GRAM_E_ARG;
-  return 0;
+  return items ? check_items(items) : 0;
 }
 
 extern "C" int gram_beam_step_bias(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                                    int cur_len, int rows_per_user, const float* phi, int64_t phi_stride,
                                    const gram_user_items_t* items, void* stream) {
-  if (int e = check_bias(tr, phi, phi_stride)) return e;
-  if (items)
-    if (int e = check_items(items)) return e;
+  if (int e = check_bias(tr, phi, phi_stride, items)) return e;
   if (!logits) return GRAM_E_ARG;
-  const StepBias bias{phi, (long long)phi_stride};
-  return launch_beam_step(st, tr, logits, lse, V, cur_len, rows_per_user, nullptr, nullptr, 0, nullptr, stream, 1, nullptr, items, &bias);
+  StepCall c = dense_call(st, tr, logits, lse, V, cur_len, rows_per_user, stream);
+  c.items = items, c.bias = {phi, (long long)phi_stride};
+  return launch_search_step(c);
 }
 
 extern "C" int gram_beam_step_bias_sparse(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
                                           const void* lm_head_bf16, const float* lm_head_f32, int d, const float* lse, int V, int cur_len,
                                           int rows_per_user, const int32_t* rowpos, int pieces, const float* phi, int64_t phi_stride,
                                           const gram_user_items_t* items, void* stream) {
-  if (int e = check_bias(tr, phi, phi_stride)) return e;
-  if (items)
-    if (int e = check_items(items)) return e;
+  if (int e = check_bias(tr, phi, phi_stride, items)) return e;
   if (!hidden_bf16 || !st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
-  // pieces == 1 reads lm_head_bf16, two pieces (or no lm_head_bf16) lm_head_f32: as gram_beam_step_groups_sparse
-  const bool use32 = pieces > 1 || !lm_head_bf16;
-  const StepBias bias{phi, (long long)phi_stride};
-  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, use32 ? nullptr : lm_head_bf16, d, rowpos, stream,
-                          pieces, use32 ? lm_head_f32 : nullptr, items, &bias);
-}
-
-// the (K, G, lambda) of a group search: G groups of K / G beams, a finite penalty >= 0
-static int check_groups(int K, int num_groups, float diversity_penalty) {
-  if (num_groups < 1 || num_groups > K || K % num_groups != 0) return GRAM_E_ARG;
-  if (!(diversity_penalty >= 0.f && diversity_penalty < INFINITY)) return GRAM_E_ARG;
-  return 0;
+  StepCall c = sparse_call(st, tr, hidden_bf16, lm_head_bf16, lm_head_f32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, stream);
+  c.items = items, c.bias = {phi, (long long)phi_stride};
+  return launch_search_step(c);
 }
 
 extern "C" int gram_beam_init_groups(const gram_beam_state_t* st, const gram_trie_t* tr, int start_token, int num_groups, void* stream) {
@@ -1380,55 +1419,14 @@ extern "C" int gram_beam_init_groups(const gram_beam_state_t* st, const gram_tri
   return 0;
 }
 
-// The group step (beam_group_step_kernel): which form runs is decided as for the plain step, with a group's gs * max_fanout
-// candidates in the place of K * max_fanout.  (The small-batch sparse_logits_kernel is not used: the group step computes its logits
-// itself at every batch size.)
-static int launch_group_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V, int cur_len,
-                             int rows_per_user, const void* hd, const void* emb, const float* emb32, int d, const int32_t* rowpos,
-                             int pieces, int num_groups, float diversity_penalty, const gram_user_items_t* items, void* stream) {
-  if (int e = check_state(st)) return e;
-  if (int e = check_groups(st->K, num_groups, diversity_penalty)) return e;
-  if (items)
-    if (int e = check_items(items)) return e;
-  if (!tr || !lse || cur_len < 1 || cur_len >= st->Tmax || V < 2 || (rows_per_user != 1 && rows_per_user != st->K)) return GRAM_E_ARG;
-  if (rowpos && rows_per_user != st->K) return GRAM_E_ARG;
-  if (!logits && (!hd || (!emb && !emb32) || d < 64 || (d & 63))) return GRAM_E_ARG;
-  if (pieces < 1 || pieces > GRAM_MAX_PIECES || (pieces > 1 && !emb32)) return GRAM_E_ARG;
-  if (tr->max_fanout < 0 || (long long)st->K * V > INT32_MAX || tr->max_fanout > V) return GRAM_E_ARG;
-  const int gs = st->K / num_groups;
-  const long long need = (long long)gs * tr->max_fanout;
-  int nc = 64;
-  while (nc < need && nc < kOneShotMaxKeys) nc <<= 1;
-  const int nlog_one = (tr->max_fanout + 3) / 4 * 4;
-  const size_t seq_bytes = (size_t)2 * st->K * st->Tmax * 4;
-  const size_t smem_one = (size_t)nc * 8 + (size_t)nlog_one * 4 + seq_bytes;
-  const bool chunked = g_beam_chunked == 1 || need > kOneShotMaxKeys || smem_one > 152 * 1024;
-  gram_prof::Scope prof(GRAM_K_BEAM, (hipStream_t)stream, 0.0);
-  static const int wide_max_b = getenv("GRAM_BEAM_WIDE_MAXB") ? atoi(getenv("GRAM_BEAM_WIDE_MAXB")) : 128;
-  const bool wide = st->B <= wide_max_b;
-  int P = 64;
-  while (P < 2 * gs) P <<= 1;
-  int cap = kChunkKeys - P;
-  if (g_beam_chunk_cap > 0 && g_beam_chunk_cap < cap) cap = g_beam_chunk_cap;
-  const int nkeys = chunked ? kChunkKeys : nc, nlog = chunked ? kChunkLog : nlog_one;
-  const size_t smem = chunked ? (size_t)kChunkKeys * 8 + (size_t)kChunkLog * 4 + seq_bytes : smem_one;
-  auto launch = [&](auto form, auto... ui) {
-    constexpr bool CH = decltype(form)::value;
-    return launch_step_pair<beam_group_step_kernel<256, CH, decltype(ui)...>, beam_group_step_kernel<1024, CH, decltype(ui)...>>(
-        wide, st->B, smem, (hipStream_t)stream, *st, *tr, logits, lse, V, cur_len, nkeys, nlog, cap, rows_per_user, (const p16*)hd,
-        (const p16*)emb, d, rowpos, pieces, emb32, num_groups, diversity_penalty, ui...);
-  };
-  if (chunked) return items ? launch(std::true_type{}, *items) : launch(std::true_type{});
-  return items ? launch(std::false_type{}, *items) : launch(std::false_type{});
-}
-
 extern "C" int gram_beam_step_groups(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                                      int cur_len, int rows_per_user, int num_groups, float diversity_penalty, void* stream) {
   if (int e = check_state(st)) return e;
   if (int e = check_groups(st->K, num_groups, diversity_penalty)) return e;
   if (!logits) return GRAM_E_ARG;
-  return launch_group_step(st, tr, logits, lse, V, cur_len, rows_per_user, nullptr, nullptr, nullptr, 0, nullptr, 1, num_groups,
-                           diversity_penalty, nullptr, stream);
+  StepCall c = dense_call(st, tr, logits, lse, V, cur_len, rows_per_user, stream);
+  c.num_groups = num_groups, c.diversity_penalty = diversity_penalty;
+  return launch_search_step(c);
 }
 
 extern "C" int gram_beam_step_groups_sparse(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
@@ -1438,36 +1436,35 @@ extern "C" int gram_beam_step_groups_sparse(const gram_beam_state_t* st, const g
   if (int e = check_state(st)) return e;
   if (int e = check_groups(st->K, num_groups, diversity_penalty)) return e;
   if (!hidden_bf16) return GRAM_E_ARG;
-  // pieces == 1 reads lm_head_bf16, two pieces (or no lm_head_bf16) lm_head_f32: as gram_sample_step
-  const bool use32 = pieces > 1 || !lm_head_bf16;
-  return launch_group_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, use32 ? nullptr : lm_head_bf16,
-                           use32 ? lm_head_f32 : nullptr, d, rowpos, pieces, num_groups, diversity_penalty, items, stream);
+  StepCall c = sparse_call(st, tr, hidden_bf16, lm_head_bf16, lm_head_f32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, stream);
+  c.items = items, c.num_groups = num_groups, c.diversity_penalty = diversity_penalty;
+  return launch_search_step(c);
 }
 
 extern "C" int gram_beam_step(const gram_beam_state_t* st, const gram_trie_t* tr, const float* logits, const float* lse, int V,
                               int cur_len, int rows_per_user, void* stream) {
   if (!logits) return GRAM_E_ARG;
-  return launch_beam_step(st, tr, logits, lse, V, cur_len, rows_per_user, nullptr, nullptr, 0, nullptr, stream);
+  return launch_search_step(dense_call(st, tr, logits, lse, V, cur_len, rows_per_user, stream));
 }
 
 extern "C" int gram_beam_step_sparse(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
                                      const void* lm_head_bf16, int d, const float* lse, int V, int cur_len, int rows_per_user,
                                      void* stream) {
-  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, lm_head_bf16, d, nullptr, stream);
+  return launch_search_step(sparse_call(st, tr, hidden_bf16, lm_head_bf16, nullptr, d, lse, V, cur_len, rows_per_user, nullptr, 1, stream));
 }
 
 extern "C" int gram_beam_step_sparse_live(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
                                           const void* lm_head_bf16, int d, const float* lse, int V, int cur_len,
                                           const int32_t* rowpos, void* stream) {
   if (!rowpos || !st) return GRAM_E_ARG;
-  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, st->K, hidden_bf16, lm_head_bf16, d, rowpos, stream);
+  return launch_search_step(sparse_call(st, tr, hidden_bf16, lm_head_bf16, nullptr, d, lse, V, cur_len, st->K, rowpos, 1, stream));
 }
 
 extern "C" int gram_beam_step_sparse_split(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
                                            const float* lm_head_f32, int d, const float* lse, int V, int cur_len, int rows_per_user,
                                            const int32_t* rowpos, int pieces, void* stream) {
   if (!lm_head_f32) return GRAM_E_ARG;
-  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, nullptr, d, rowpos, stream, pieces, lm_head_f32);
+  return launch_search_step(sparse_call(st, tr, hidden_bf16, nullptr, lm_head_f32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, stream));
 }
 
 extern "C" int gram_beam_step_sparse_items(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
@@ -1475,7 +1472,9 @@ extern "C" int gram_beam_step_sparse_items(const gram_beam_state_t* st, const gr
                                            const int32_t* rowpos, const gram_user_items_t* items, void* stream) {
   if (int e = check_items(items)) return e;
   if (!st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
-  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, lm_head_bf16, d, rowpos, stream, 1, nullptr, items);
+  StepCall c = sparse_call(st, tr, hidden_bf16, lm_head_bf16, nullptr, d, lse, V, cur_len, rows_per_user, rowpos, 1, stream);
+  c.items = items;
+  return launch_search_step(c);
 }
 
 extern "C" int gram_beam_step_sparse_split_items(const gram_beam_state_t* st, const gram_trie_t* tr, const void* hidden_bf16,
@@ -1484,8 +1483,9 @@ extern "C" int gram_beam_step_sparse_split_items(const gram_beam_state_t* st, co
                                                  void* stream) {
   if (int e = check_items(items)) return e;
   if (!lm_head_f32 || !st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
-  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, nullptr, d, rowpos, stream, pieces, lm_head_f32,
-                          items);
+  StepCall c = sparse_call(st, tr, hidden_bf16, nullptr, lm_head_f32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, stream);
+  c.items = items;
+  return launch_search_step(c);
 }
 
 extern "C" int gram_user_items_prepare(const int32_t* item_rank, int n_items, const int32_t* items, int B, int M, int32_t* ranks,
@@ -1519,10 +1519,9 @@ extern "C" int gram_beam_step_sparse_mask(const gram_beam_state_t* st, const gra
                                           void* stream) {
   if (int e = check_mask(mask)) return e;
   if (!hidden_bf16 || !st || (rowpos && rows_per_user != st->K)) return GRAM_E_ARG;
-  // pieces == 1 reads lm_head_bf16, two pieces (or no lm_head_bf16) lm_head_f32: as gram_beam_step_groups_sparse
-  const bool use32 = pieces > 1 || !lm_head_bf16;
-  return launch_beam_step(st, tr, nullptr, lse, V, cur_len, rows_per_user, hidden_bf16, use32 ? nullptr : lm_head_bf16, d, rowpos, stream,
-                          pieces, use32 ? lm_head_f32 : nullptr, nullptr, nullptr, mask);
+  StepCall c = sparse_call(st, tr, hidden_bf16, lm_head_bf16, lm_head_f32, d, lse, V, cur_len, rows_per_user, rowpos, pieces, stream);
+  c.mask = mask;
+  return launch_search_step(c);
 }
 
 extern "C" int gram_live_rows(const gram_beam_state_t* st, const gram_trie_t* tr, const gram_live_rows_t* out, void* stream) {

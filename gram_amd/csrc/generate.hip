@@ -536,34 +536,31 @@ int decode_step(const gram_model* m, const Workspace& w, const int32_t* tokens, 
   return lm_head(m, w, R, logits, lse_part, st);
 }
 
-// the search mode of gram_generate_groups (NULL everywhere else: the plain search)
-struct GroupMode {
-  int num_groups;
-  float diversity_penalty;
+// The search mode of a whole-path call; all of it empty: the plain search of gram_generate_ex.
+struct SearchMode {
+  const gram_user_items_t* items = nullptr;  // per-user item lists (gram_generate_items; optional beside groups or potentials)
+  const gram_user_mask_t* umask = nullptr;   // per-user item masks (gram_generate_mask): they come alone
+  const gram_trie_tail_t* tail = nullptr;    // the tail pass (gram_generate_tail): the plain search only
+  int num_groups = 0;                        // > 0: group beam search (gram_generate_groups), its init and its step
+  float diversity_penalty = 0.f;
+  const float* phi = nullptr;                // the biased search (gram_generate_bias): the caller's potentials (gram_item_bias_table)
+  int64_t phi_stride = 0;                    //   and their row stride
 };
 
-// the search mode of gram_generate_bias (NULL everywhere else): the caller's potentials (gram_item_bias_table) and their row stride
-struct BiasMode {
-  const float* phi;
-  int64_t stride;
-};
-
-// the search step on the hidden states decode_step left in w.dec.h (rowpos: live-row step, else NULL; items: per-user item filters of
-// gram_generate_items, else NULL; grp: the group step, else NULL; bias: the biased step, else NULL; umask: per-user item masks of
-// gram_generate_mask, else NULL -- they come alone)
+// the search step on the hidden states decode_step left in w.dec.h (rowpos: live-row step, else NULL)
 int search_step(const gram_model* m, const Workspace& w, const gram_trie_t* trie, int cur_len, int rows_per_user, const int32_t* rowpos,
-                const gram_user_items_t* items, void* st, const GroupMode* grp = nullptr, const BiasMode* bias = nullptr,
-                const gram_user_mask_t* umask = nullptr) {
+                const SearchMode& sm, void* st) {
   const gram_model_desc_t& c = m->d;
-  if (umask)
+  const gram_user_items_t* items = sm.items;
+  if (sm.umask)
     return gram_beam_step_sparse_mask(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
-                                      rows_per_user, rowpos, w.pieces, umask, st);
-  if (bias)
+                                      rows_per_user, rowpos, w.pieces, sm.umask, st);
+  if (sm.phi)
     return gram_beam_step_bias_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
-                                      rows_per_user, rowpos, w.pieces, bias->phi, bias->stride, items, st);
-  if (grp)
+                                      rows_per_user, rowpos, w.pieces, sm.phi, sm.phi_stride, items, st);
+  if (sm.num_groups)
     return gram_beam_step_groups_sparse(&w.beam, trie, w.dec.h, c.lm_head_bf16, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len,
-                                        rows_per_user, rowpos, w.pieces, grp->num_groups, grp->diversity_penalty, items, st);
+                                        rows_per_user, rowpos, w.pieces, sm.num_groups, sm.diversity_penalty, items, st);
   if (items) {
     if (w.pieces > 1)
       return gram_beam_step_sparse_split_items(&w.beam, trie, w.dec.h, c.lm_head_f32, c.d_model, w.lse, c.vocab, cur_len, rows_per_user,
@@ -944,20 +941,20 @@ namespace {
 // 14.1 vs 12.8 ms, 11.5 vs 10.65 ms eager: the chain is bound by the GPU-side dependency between ~950 tiny kernels, not by the host's
 // launch cost, and a captured train cannot take the live-row step, whose row counts travel through the host -- and removed in round 4.)
 int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
-                  int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
-                  const gram_trie_tail_t* tail, const GroupMode* grp, const BiasMode* bias, int64_t* sequences, float* scores,
-                  void* stream, const gram_user_mask_t* umask = nullptr) {
+                  int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const SearchMode& sm, int64_t* sequences,
+                  float* scores, void* stream) {
+  const gram_trie_tail_t* tail = sm.tail;
   TRY(encode_call(m, w, input_ids, mask, B, N, L, comp, stream));
-  // grp: group beam search (gram_generate_groups): its init and its search step, the same loop (a -inf beam has no node, so
+  // group beam search (gram_generate_groups): its init and its search step, the same loop (a -inf beam has no node, so
   // gram_live_rows' liveness test holds unchanged); the caller passes no tail
-  // bias: the biased search (gram_generate_bias): the plain init and the biased search step, the same loop; no tail either
-  if (grp) TRY(gram_beam_init_groups(&w.beam, trie, /*decoder_start_token_id=*/0, grp->num_groups, stream));
+  // the biased search (gram_generate_bias): the plain init and the biased search step, the same loop; no tail either
+  if (sm.num_groups) TRY(gram_beam_init_groups(&w.beam, trie, /*decoder_start_token_id=*/0, sm.num_groups, stream));
   else TRY(gram_beam_init(&w.beam, trie, /*decoder_start_token_id=*/0, stream));
   if (K == 1) {  // HF: num_beams == 1 -> greedy_search (raw logits, no hypotheses, no scores)
     for (int t = 0; t + 1 < max_length; ++t) {
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, 1, B, max_length, t, w.logits, nullptr, nullptr, stream));
-      if (umask) TRY(gram_greedy_step_mask(&w.beam, trie, w.logits, m->d.vocab, t + 1, umask, stream));
-      else if (items) TRY(gram_greedy_step_items(&w.beam, trie, w.logits, m->d.vocab, t + 1, items, stream));
+      if (sm.umask) TRY(gram_greedy_step_mask(&w.beam, trie, w.logits, m->d.vocab, t + 1, sm.umask, stream));
+      else if (sm.items) TRY(gram_greedy_step_items(&w.beam, trie, w.logits, m->d.vocab, t + 1, sm.items, stream));
       else TRY(gram_greedy_step(&w.beam, trie, w.logits, m->d.vocab, t + 1, stream));
     }
     TRY(gram_greedy_finalize(&w.beam, max_length, sequences, w.width, stream));
@@ -1001,7 +998,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
       }
       if (replay) {
         TRY(gram_tail_rowpos(&w.beam, trie, &wt.forest, stream));
-        TRY(search_step(m, wt, trie, t + 1, K, wt.forest.rowpos, nullptr, stream));
+        TRY(search_step(m, wt, trie, t + 1, K, wt.forest.rowpos, SearchMode{}, stream));
         continue;
       }
       // step 0: every beam of a user holds the same start token and an empty cache, so the decoder,
@@ -1025,7 +1022,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
                             stream));
             TRY(gram_lse_combine(w.lse_part, w.lse, counts[0], m->d.vocab / 64, stream));
           }  // else: no beam can be extended; the search step below reads no decoder row
-          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, items, stream, grp, bias, umask));
+          TRY(search_step(m, w, trie, t + 1, K, w.live.rowpos, sm, stream));
           continue;
         }
       }
@@ -1033,7 +1030,7 @@ int generate_body(const gram_model* m, Workspace& w, const int64_t* input_ids, c
       TRY(decode_step(m, w, w.beam.tokens, w.beam.anc, mask, B, N, L, Kt, B * K, max_length, t, nullptr, w.lse_part, nullptr,
                       stream));
       TRY(gram_lse_combine(w.lse_part, w.lse, B * Kt, m->d.vocab / 64, stream));
-      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, items, stream, grp, bias, umask));
+      TRY(search_step(m, w, trie, t + 1, Kt, nullptr, sm, stream));
     }
     TRY(gram_beam_finalize(&w.beam, nret, max_length, sequences, scores, w.width, stream));
   }
@@ -1057,13 +1054,10 @@ static int read_width_and_error(const Workspace& w, int32_t* width_host, void* s
   return 0;
 }
 
-// gram_generate_ex, gram_generate_items (items: the per-user item filters, NULL for gram_generate_ex) and gram_generate_mask (umask:
-// the per-user item masks, in the lists' place)
+// every whole-path beam-search entry point: gram_generate_ex's call in the search mode sm (checked by the entry point)
 static int generate_call(const gram_model_t* m, const int64_t* input_ids, const uint8_t* mask, int B, int N, int L, int K, int nret,
-                         int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp,
-                         const gram_user_items_t* items, const gram_trie_tail_t* tail, void* workspace, int64_t workspace_bytes,
-                         int64_t* sequences, float* scores, int32_t* width_host, void* stream, const GroupMode* grp = nullptr,
-                         const BiasMode* bias = nullptr, const gram_user_mask_t* umask = nullptr) {
+                         int max_length, float length_penalty, const gram_trie_t* trie, const gram_compaction_t* comp, SearchMode sm,
+                         void* workspace, int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
   TRY(check_shapes(m, B, N, L, K, max_length));
   TRY(check_compaction(comp, B, N));
   if (!trie || nret < 1 || nret > K || !sequences || (!scores && K != 1)) return GRAM_E_ARG;
@@ -1072,19 +1066,18 @@ static int generate_call(const gram_model_t* m, const int64_t* input_ids, const 
   // the tail pass where the Trie has a tail inside this call's steps and the call is one it covers (beam search, no item filters,
   // the short cross-attention); everything else is the step-wise train, launch for launch
   memset(g_tail_last, 0, sizeof(g_tail_last));  // (gram_debug_tail_last speaks of the last generate call of any kind)
-  if (tail) {
-    const bool on = tail->d_tail >= 2 && tail->d_tail < max_length && tail->sub_rows && K > 1 && !items && !m->long_xattn() &&
-                    tail_shape_ok(B, K, tail->steps) && tail_wanted(m, B, N, L);
+  if (sm.tail) {
+    const bool on = sm.tail->d_tail >= 2 && sm.tail->d_tail < max_length && sm.tail->sub_rows && K > 1 && !sm.items &&
+                    !m->long_xattn() && tail_shape_ok(B, K, sm.tail->steps) && tail_wanted(m, B, N, L);
     if (on) {
-      carve_tail(m, workspace, w, B, K, tail->steps);
+      carve_tail(m, workspace, w, B, K, sm.tail->steps);
       if (workspace_bytes < w.tail_bytes) return GRAM_E_WORKSPACE;
     } else {
-      tail = nullptr;
+      sm.tail = nullptr;
     }
   }
   w.beam.length_penalty = length_penalty;
-  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, items, tail, grp, bias, sequences, scores, stream,
-                    umask));
+  TRY(generate_body(m, w, input_ids, mask, B, N, L, K, nret, max_length, trie, comp, sm, sequences, scores, stream));
   return read_width_and_error(w, width_host, stream);
 }
 
@@ -1092,7 +1085,7 @@ extern "C" int gram_generate_ex(const gram_model_t* m, const int64_t* input_ids,
                                 int nret, int max_length, float length_penalty, const gram_trie_t* trie,
                                 const gram_compaction_t* comp, void* workspace, int64_t workspace_bytes, int64_t* sequences,
                                 float* scores, int32_t* width_host, void* stream) {
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, nullptr, workspace,
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, SearchMode{}, workspace,
                        workspace_bytes, sequences, scores, width_host, stream);
 }
 
@@ -1107,11 +1100,13 @@ extern "C" int gram_generate_tail(const gram_model_t* m, const int64_t* input_id
                                   int nret, int max_length, float length_penalty, const gram_trie_t* trie,
                                   const gram_compaction_t* comp, const gram_trie_tail_t* tail, void* workspace,
                                   int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, tail, workspace,
-                       workspace_bytes, sequences, scores, width_host, stream);
+  SearchMode sm;
+  sm.tail = tail;
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, sm, workspace, workspace_bytes,
+                       sequences, scores, width_host, stream);
 }
 
-// the per-user lists of the beam-search entries that take them (gram_user_items_t): every array present, stride and mode in range
+// the per-user lists of every whole-path entry that takes them (gram_user_items_t): every array present, stride and mode in range
 static bool items_ok(const gram_user_items_t* items) {
   return items && items->leaf_lo && items->leaf_hi && items->ranks && items->count && items->stride >= 1 &&
          items->stride <= GRAM_MAX_USER_ITEMS && (items->mode == GRAM_ITEMS_EXCLUDE || items->mode == GRAM_ITEMS_ALLOW);
@@ -1122,8 +1117,10 @@ extern "C" int gram_generate_items(const gram_model_t* m, const int64_t* input_i
                                    const gram_compaction_t* comp, const gram_user_items_t* items, void* workspace,
                                    int64_t workspace_bytes, int64_t* sequences, float* scores, int32_t* width_host, void* stream) {
   if (!items_ok(items)) return GRAM_E_ARG;
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
-                       workspace_bytes, sequences, scores, width_host, stream);
+  SearchMode sm;
+  sm.items = items;
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, sm, workspace, workspace_bytes,
+                       sequences, scores, width_host, stream);
 }
 
 // per-user item masks: gram_generate_items' call with the masks in the lists' place (no tail pass)
@@ -1134,8 +1131,10 @@ extern "C" int gram_generate_mask(const gram_model_t* m, const int64_t* input_id
   if (!umask || !umask->leaf_lo || !umask->leaf_hi || !umask->words || umask->n_leaves < 1 ||
       umask->stride < (int64_t)umask->n_leaves / 32 + 1 || (reinterpret_cast<uintptr_t>(umask->words) & 7))
     return GRAM_E_ARG;
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, nullptr, nullptr, workspace,
-                       workspace_bytes, sequences, scores, width_host, stream, nullptr, nullptr, umask);
+  SearchMode sm;
+  sm.umask = umask;
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, sm, workspace, workspace_bytes,
+                       sequences, scores, width_host, stream);
 }
 
 // group beam search: gram_generate_ex's call with the group init and the group step; items may be NULL
@@ -1147,9 +1146,10 @@ extern "C" int gram_generate_groups(const gram_model_t* m, const int64_t* input_
   if (K < 2 || num_groups < 1 || num_groups > K || K % num_groups != 0 || !(diversity_penalty >= 0.f && diversity_penalty < INFINITY))
     return GRAM_E_ARG;
   if (items && !items_ok(items)) return GRAM_E_ARG;
-  const GroupMode grp{num_groups, diversity_penalty};
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
-                       workspace_bytes, sequences, scores, width_host, stream, &grp);
+  SearchMode sm;
+  sm.items = items, sm.num_groups = num_groups, sm.diversity_penalty = diversity_penalty;
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, sm, workspace, workspace_bytes,
+                       sequences, scores, width_host, stream);
 }
 
 // beam search with per-item score biases: gram_generate_ex's call with the biased search step; items may be NULL.
@@ -1161,9 +1161,10 @@ extern "C" int gram_generate_bias(const gram_model_t* m, const int64_t* input_id
                                   void* stream) {
   if (K < 2 || !trie || !phi || (phi_stride != 0 && phi_stride < trie->n_nodes)) return GRAM_E_ARG;
   if (items && !items_ok(items)) return GRAM_E_ARG;
-  const BiasMode bias{phi, phi_stride};
-  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, items, nullptr, workspace,
-                       workspace_bytes, sequences, scores, width_host, stream, nullptr, &bias);
+  SearchMode sm;
+  sm.items = items, sm.phi = phi, sm.phi_stride = phi_stride;
+  return generate_call(m, input_ids, mask, B, N, L, K, nret, max_length, length_penalty, trie, comp, sm, workspace, workspace_bytes,
+                       sequences, scores, width_host, stream);
 }
 
 // ---- Trie-constrained sampling (gram_sample) ------------------------------------------------------------------------
@@ -1264,9 +1265,7 @@ extern "C" int gram_sample_items(const gram_model_t* m, const int64_t* input_ids
                                  int max_length, const gram_trie_t* trie, const gram_compaction_t* comp, const gram_user_items_t* items,
                                  const gram_sample_params_t* params, const float* uniforms, void* workspace, int64_t workspace_bytes,
                                  int64_t* sequences, float* seq_logprobs, float* sample_logprobs, int32_t* width_host, void* stream) {
-  if (!items || !items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
-      items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW))
-    return GRAM_E_ARG;
+  if (!items_ok(items)) return GRAM_E_ARG;
   return sample_call(m, input_ids, mask, B, N, L, R, max_length, trie, comp, items, params, uniforms, workspace, workspace_bytes,
                      sequences, seq_logprobs, sample_logprobs, width_host, stream);
 }
@@ -1356,9 +1355,7 @@ extern "C" int gram_generate_sbs_items(const gram_model_t* m, const int64_t* inp
                                        const gram_user_items_t* items, float temperature, uint64_t seed, const int64_t* user_keys,
                                        void* workspace, int64_t workspace_bytes, int64_t* sequences, float* seq_logprobs,
                                        float* sample_logprobs, float* perturbed_scores, int32_t* width_host, void* stream) {
-  if (!items || !items->leaf_lo || !items->leaf_hi || !items->ranks || !items->count || items->stride < 1 ||
-      items->stride > GRAM_MAX_USER_ITEMS || (items->mode != GRAM_ITEMS_EXCLUDE && items->mode != GRAM_ITEMS_ALLOW))
-    return GRAM_E_ARG;
+  if (!items_ok(items)) return GRAM_E_ARG;
   return sbs_call(m, input_ids, mask, B, N, L, R, max_length, trie, comp, items, temperature, seed, user_keys, workspace, workspace_bytes,
                   sequences, seq_logprobs, sample_logprobs, perturbed_scores, width_host, stream);
 }

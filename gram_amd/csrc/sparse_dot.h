@@ -8,7 +8,7 @@
 namespace {
 
 // h[row] . E[tok] on 8 lanes (sub = lane & 7): the same sums in the same order wherever a candidate is computed -- inside the search
-// step's workgroup or, for a handful of users, by sparse_logits_kernel's many workgroups (launch_beam_step)
+// step's workgroup or, for a handful of users, by sparse_logits_kernel's many workgroups (launch_search_step)
 __device__ __forceinline__ float sparse_dot(bool act, int lr, int tok, int sub, const p16* __restrict__ hd, const p16* __restrict__ emb,
                                             const float* __restrict__ emb32, int d, int pieces) {
   const int per = d >> 3;  // elements per lane

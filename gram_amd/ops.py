@@ -206,6 +206,32 @@ def _user_items(op: str, input_ids: Tensor, attention_mask: Tensor, trie_child_o
     return trie, comp, ui, (ranks, count)
 
 
+def _optional_user_items(op: str, input_ids: Tensor, attention_mask: Tensor, trie_child_off: Tensor, trie_child_tok: Tensor,
+                         trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, comp_map, comp_ids, comp_mask, cache_slot,
+                         cache_x, n_cached: int, cache_L: int, leaf_lo, leaf_hi, item_rank, items, allow: bool):
+    """The optional lists of ``generate_groups`` and ``generate_bias``: the four list tensors come together -- then ``_user_items`` --
+    or not at all -- then the plain inputs are validated here.  Returns (gram_trie_t, gram_compaction_t or None, the argument for
+    the call's ``items`` -- a reference to the gram_user_items_t or None --, what it points into: keep it until the call returns)."""
+    lists = (leaf_lo, leaf_hi, item_rank, items)
+    if any(t is not None for t in lists):
+        if any(t is None for t in lists):
+            raise ValueError(f"{op}: leaf_lo, leaf_hi, item_rank and items come together")
+        trie, comp, ui, keep = _user_items(op, input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node,
+                                           trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached,
+                                           cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
+        return trie, comp, C.byref(ui), (ui, keep)
+    if input_ids.dim() != 3:
+        raise ValueError(f"{op}: input_ids must be (B, N, L)")
+    dev = input_ids.device
+    _check("input_ids", input_ids, torch.int64)
+    _check("attention_mask", attention_mask, torch.uint8, tuple(input_ids.shape), dev)
+    for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
+                           ("trie_child_node", trie_child_node, (trie_child_tok.numel(),))):
+        _check(name, t, torch.int32, shape, dev)
+    return (_trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len),
+            _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L), None, None)
+
+
 @torch.library.custom_op("gram::generate_items", mutates_args=("workspace",), device_types="cuda")
 def generate_items(input_ids: Tensor, attention_mask: Tensor, handle: int, workspace: Tensor, trie_child_off: Tensor,
                    trie_child_tok: Tensor, trie_child_node: Tensor, trie_max_fanout: int, trie_min_seq_len: int, num_beams: int,
@@ -306,26 +332,9 @@ def generate_groups(input_ids: Tensor, attention_mask: Tensor, handle: int, work
     _check_groups("generate_groups", num_beams, num_beam_groups, diversity_penalty)
     if not 1 <= num_return_sequences <= num_beams:
         raise ValueError("generate_groups: need 1 <= num_return_sequences <= num_beams")
-    lists = (leaf_lo, leaf_hi, item_rank, items)
-    if any(t is not None for t in lists):
-        if any(t is None for t in lists):
-            raise ValueError("generate_groups: leaf_lo, leaf_hi, item_rank and items come together")
-        trie, comp, ui, _keep = _user_items("generate_groups", input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node,
-                                            trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot, cache_x,
-                                            n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
-        ui_ref = C.byref(ui)
-    else:
-        if input_ids.dim() != 3:
-            raise ValueError("generate_groups: input_ids must be (B, N, L)")
-        dev = input_ids.device
-        _check("input_ids", input_ids, torch.int64)
-        _check("attention_mask", attention_mask, torch.uint8, tuple(input_ids.shape), dev)
-        for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
-                               ("trie_child_node", trie_child_node, (trie_child_tok.numel(),))):
-            _check(name, t, torch.int32, shape, dev)
-        trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
-        comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
-        ui_ref = None
+    trie, comp, ui_ref, _keep = _optional_user_items("generate_groups", input_ids, attention_mask, trie_child_off, trie_child_tok,
+                                                     trie_child_node, trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask,
+                                                     cache_slot, cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
     with torch.cuda.device(input_ids.device):
         return _search(_lib.load().gram_generate_groups, "gram_generate_groups", input_ids, attention_mask, handle, workspace, trie, comp,
                        num_beams, num_return_sequences, max_length, length_penalty, int(num_beam_groups), float(diversity_penalty), ui_ref)
@@ -395,23 +404,9 @@ def generate_bias(input_ids: Tensor, attention_mask: Tensor, handle: int, worksp
     if phi.dim() != 2 or phi.shape[0] not in (1, input_ids.shape[0]):
         raise ValueError(f"generate_bias: phi must be (1, n_nodes) or (B, n_nodes), got {tuple(phi.shape)}")
     _check("phi", phi, torch.float32, (None, n_nodes), dev)
-    lists = (leaf_lo, leaf_hi, item_rank, items)
-    if any(t is not None for t in lists):
-        if any(t is None for t in lists):
-            raise ValueError("generate_bias: leaf_lo, leaf_hi, item_rank and items come together")
-        trie, comp, ui, _keep = _user_items("generate_bias", input_ids, attention_mask, trie_child_off, trie_child_tok, trie_child_node,
-                                            trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask, cache_slot, cache_x,
-                                            n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
-        ui_ref = C.byref(ui)
-    else:
-        _check("input_ids", input_ids, torch.int64)
-        _check("attention_mask", attention_mask, torch.uint8, tuple(input_ids.shape), dev)
-        for name, t, shape in (("trie_child_off", trie_child_off, None), ("trie_child_tok", trie_child_tok, None),
-                               ("trie_child_node", trie_child_node, (trie_child_tok.numel(),))):
-            _check(name, t, torch.int32, shape, dev)
-        trie = _trie(trie_child_off, trie_child_tok, trie_child_node, trie_max_fanout, trie_min_seq_len)
-        comp = _compaction(comp_map, comp_ids, comp_mask, cache_slot, cache_x, n_cached, cache_L)
-        ui_ref = None
+    trie, comp, ui_ref, _keep = _optional_user_items("generate_bias", input_ids, attention_mask, trie_child_off, trie_child_tok,
+                                                     trie_child_node, trie_max_fanout, trie_min_seq_len, comp_map, comp_ids, comp_mask,
+                                                     cache_slot, cache_x, n_cached, cache_L, leaf_lo, leaf_hi, item_rank, items, allow)
     with torch.cuda.device(dev):
         return _search(_lib.load().gram_generate_bias, "gram_generate_bias", input_ids, attention_mask, handle, workspace, trie, comp,
                        num_beams, num_return_sequences, max_length, length_penalty, phi.data_ptr(),

@@ -1,6 +1,6 @@
 """The per-user item-filter kernels of gram_amd/csrc/beam.hip, driven directly through the C ABI (tests/gpu_util.py, _lib.UserItems)
 at every launch form.  tests/test_gpu_user_items.py covers them through whole generate() calls on a tiny model; here the shapes
-are chosen so that every instantiation runs.  launch_beam_step picks the form from B and the Trie alone:
+are chosen so that every instantiation runs.  launch_search_step picks the form from B and the Trie alone:
 
     B <= 16 and a state with cand_logits ("scratch")   sparse_logits_kernel, then beam_step_kernel<1024, gram_user_items_t> reading
                                                        its logits

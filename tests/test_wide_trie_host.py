@@ -33,7 +33,7 @@ def golden_cands(name):
 
 
 def one_shot_lds_bytes(K, fan, Tmax):
-    """dynamic LDS of the one-shot kernel (launch_beam_step): keys + step-0 logits + new_seq/new_anc"""
+    """dynamic LDS of the one-shot kernel (launch_search_step): keys + step-0 logits + new_seq/new_anc"""
     nc = 64
     while nc < K * fan:
         nc <<= 1
